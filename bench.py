@@ -14,20 +14,29 @@ The workloads are BASELINE.json's configs, selected with --conf
 With N GPUs every rank owns its own streams (no collective on the data path: streams are independent), so
 scaling is weak and `value` is the whole-job frames/s.  The PCM is the deterministic generator of
 csrc/pcm_synth_core.h run on the device (md5-pinned by tests/test_synth.py).  A sample of the timed batch's
-streams is compared byte for byte with the CPU oracle and with the unmodified reference binary; a mismatch
+streams is compared byte for byte with the CPU oracle and with the unmodified reference binary (--full); a mismatch
 makes the run FAIL (exit 1, value null).  tools/full_parity.py compares every stream.
 
 --layer 1|2 runs the same contract over the Layer I / Layer II path (include/mp3mi_l12.h) at the
 reference's default bitrate for the layer (src/musicin.c:371-372: 288 / 160 kbps): 4096 streams x 10 s of 44.1 kHz stereo.
 The default (--layer 3) is the metric of BASELINE.json.
 
-The default line (N = 1, configs[1], Layer III) also carries `end_to_end` -- the same K steps with PCM and bytes in page-locked
-host memory, crossing PCIe beside the kernels; `value` stays the resident rate -- and `other_workloads`:
-two steps each of configs[2], configs[3], configs[4] and of the Layer II batch and one Layer I step, each with its own oracle
-spot check.  `collective_backend` says what carried the ranks' barrier / maximum / votes (RCCL, or gloo where RCCL did not come up or
-MP3MI_BENCH_BACKEND=gloo asked for it); `roofline.clock_ghz_measured` is the engine clock the driver reported during the timed region.
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes the outputs (--dump-outputs DIR)
+and prints the line.  --full adds everything else: the oracle / reference parity spot check, the timed CPU baseline
+(`cpu_baseline`), the engine clock during the timed region (`roofline.clock_ghz_measured`) and, on the Layer III line,
+`end_to_end` -- the same K steps with PCM and bytes in page-locked host memory, crossing PCIe beside the kernels (SURVEY.md
+8(d)); `value` stays the resident rate -- and, on the default line (N = 1, configs[1]), `other_workloads`: two steps each of
+configs[2], configs[3], configs[4] and of the Layer II batch and one Layer I step, each with its own oracle spot check.
+`collective_backend` says what carried the ranks' barrier / maximum / votes (RCCL, or gloo where RCCL did not come up or
+MP3MI_BENCH_BACKEND=gloo asked for it).
+
+--dump-outputs DIR writes what the last timed step returned to its caller (rank 0's batch), as float64 / float32 .npy files:
+stream_lengths.npy (the byte count of every stream), sample_streams.npy (a fixed, seeded sample of the streams) and
+sample_bytes.npy (those streams' bytes, zero past each stream's length).  The PCM is seeded, so two builds run with the same
+arguments can be compared output for output.
 
     python bench.py --gpus 1 --steps 2 --warmup 1
+    python bench.py --gpus 1 --steps 2 --warmup 1 --full   (the line with every figure and check above)
     python bench.py --gpus N --steps K --warmup W          (starts its own N ranks, one per GPU, and relays rank 0's line)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -445,6 +454,24 @@ def all_host_cores():
     return max(1, n)
 
 
+DUMP_BYTES = 56 << 20  # the dump's budget (64 MB at most): sample_bytes.npy holds float32 bytes of this many / 4 output bytes
+
+
+def dump_outputs(dirname, out, out_len):
+    """--dump-outputs: what a caller of the timed path receives -- the byte count of every stream and, for a fixed seeded sample of
+    the streams (as many as fit DUMP_BYTES, at most 64), their bytes up to the output stride, zero past the stream's length."""
+    os.makedirs(dirname, exist_ok=True)
+    S, stride = out.shape
+    lens = out_len.cpu().numpy().astype(np.int64)
+    k = max(1, min(S, 64, DUMP_BYTES // (4 * stride)))
+    idx = np.sort(np.random.default_rng(SEED).choice(S, size=k, replace=False))
+    rows = out[torch.from_numpy(idx).to(out.device)].cpu().numpy()
+    rows[np.arange(stride)[None, :] >= lens[idx][:, None]] = 0
+    np.save(os.path.join(dirname, "stream_lengths.npy"), lens.astype(np.float64))
+    np.save(os.path.join(dirname, "sample_streams.npy"), idx.astype(np.float64))
+    np.save(os.path.join(dirname, "sample_bytes.npy"), rows.astype(np.float32))
+
+
 def main_l12(args, mp3, dev, coll, rank, world, affinity):
     """The Layer I / II path under the same contract: a step = one mp3mi_l12_batch_encode call over the batch."""
     import hashlib
@@ -476,33 +503,36 @@ def main_l12(args, mp3, dev, coll, rank, world, affinity):
     dt = time.perf_counter() - t0
     k_after = batch.kernel_timing()
     dt = float(coll.reduce(dt, "max"))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, out_len)
 
-    timed_baseline = rank == 0 and not args.no_cpu_baseline
+    timed_baseline = args.full and rank == 0 and not args.no_cpu_baseline
     cores = all_host_cores() if timed_baseline else 8
     n_sample = max(4, cores * 2) if timed_baseline else 8
     idx = sorted(set(np.linspace(0, S - 1, n_sample).astype(int).tolist()))
-    pcm_sample = [pcm[i].cpu().numpy() for i in idx]
     out_h, len_h = out[idx].cpu().numpy(), out_len[idx].cpu().numpy()
     got = [out_h[k, : len_h[k]].tobytes() for k in range(len(idx))]
-    orc = Oracle()
-    oracle_l12(orc, layer, rate, kbps, mode, pcm_sample[0][: spf * C * 4])
-    t1 = time.perf_counter()
-    with ThreadPoolExecutor(max_workers=cores) as ex:
-        refs = list(ex.map(lambda p: oracle_l12(orc, layer, rate, kbps, mode, p)[0], pcm_sample))
-    fps = len(idx) * nf / (time.perf_counter() - t1)
-    bad = [int(idx[k]) for k in range(len(idx)) if got[k] != refs[k]]
-    cpu = None
-    if timed_baseline:
-        cpu = {"value": round(fps, 1), "unit": "frames/s", "cores": cores, "kind": "port",
-               "sample": "%d of this batch's streams x %d frames, oracle/liboracle.so (mp12_oracle.inc), one thread per stream" % (len(idx), nf)}
-        ref = reference_baseline(pcm_sample, rate, [kbps] * len(idx), C, cores, layer=layer)
-        if ref is not None:
-            rfps, routs = ref
-            fbl = mp3.frame_bytes_l12(layer, rate, kbps)
-            bad += [int(idx[k]) for k in range(len(idx)) if without_private_bit(got[k], fbl) != without_private_bit(routs[k], fbl) and int(idx[k]) not in bad]
-            cpu = {"value": round(rfps, 1), "unit": "frames/s", "cores": cores, "kind": "reference",
-                   "sample": "%d of this batch's streams x %d frames, oracle/_ref/encode -l %d (unmodified reference, gcc -O2), one process per stream" % (len(idx), nf, layer),
-                   "port_value": round(fps, 1)}
+    bad, cpu = [], None
+    if args.full:  # the parity spot check against the oracle (and the reference binary, where the baseline is timed)
+        pcm_sample = [pcm[i].cpu().numpy() for i in idx]
+        orc = Oracle()
+        oracle_l12(orc, layer, rate, kbps, mode, pcm_sample[0][: spf * C * 4])
+        t1 = time.perf_counter()
+        with ThreadPoolExecutor(max_workers=cores) as ex:
+            refs = list(ex.map(lambda p: oracle_l12(orc, layer, rate, kbps, mode, p)[0], pcm_sample))
+        fps = len(idx) * nf / (time.perf_counter() - t1)
+        bad = [int(idx[k]) for k in range(len(idx)) if got[k] != refs[k]]
+        if timed_baseline:
+            cpu = {"value": round(fps, 1), "unit": "frames/s", "cores": cores, "kind": "port",
+                   "sample": "%d of this batch's streams x %d frames, oracle/liboracle.so (mp12_oracle.inc), one thread per stream" % (len(idx), nf)}
+            ref = reference_baseline(pcm_sample, rate, [kbps] * len(idx), C, cores, layer=layer)
+            if ref is not None:
+                rfps, routs = ref
+                fbl = mp3.frame_bytes_l12(layer, rate, kbps)
+                bad += [int(idx[k]) for k in range(len(idx)) if without_private_bit(got[k], fbl) != without_private_bit(routs[k], fbl) and int(idx[k]) not in bad]
+                cpu = {"value": round(rfps, 1), "unit": "frames/s", "cores": cores, "kind": "reference",
+                       "sample": "%d of this batch's streams x %d frames, oracle/_ref/encode -l %d (unmodified reference, gcc -O2), one process per stream" % (len(idx), nf, layer),
+                       "port_value": round(fps, 1)}
     n_bad = int(coll.reduce(len(bad), "sum"))
     per_rank = coll.gather([rank, rank * S, S, int(hashlib.md5(b"".join(got)).hexdigest()[:15], 16)])
     parity_ok = n_bad == 0
@@ -550,7 +580,8 @@ def main_l12(args, mp3, dev, coll, rank, world, affinity):
                          "source_hash": mp3.lib().mp3mi_source_hash().decode()},
             "cpu_baseline": cpu, "ranks": ranks, "collective_backend": coll.backend, "cpu_affinity_rank0": affinity,
             "parity_spot_check": {"streams_per_rank": len(idx), "bit_exact": parity_ok, "mismatching_streams_rank0": bad,
-                                  "witness": "oracle/liboracle.so" + (" + oracle/_ref/encode" if cpu and cpu["kind"] == "reference" else "")},
+                                  "witness": "oracle/liboracle.so" + (" + oracle/_ref/encode" if cpu and cpu["kind"] == "reference" else "")}
+                                 if args.full else None,
         }
         print(json.dumps(result), flush=True)
     batch.close()
@@ -721,15 +752,20 @@ def main():
     ap.add_argument("--host-io", action="store_true",
                     help="after the resident measurement (which stays `value`), time the same K steps through "
                          "mp3mi_batch_encode_host_async -- PCM in page-locked host memory, file bytes back to it, both crossing PCIe "
-                         "chunk by chunk beside the kernels -- and add an `end_to_end` object to the line (SURVEY 8(d)).  On by default "
-                         "for the Layer III line; this flag forces it where --no-cpu-baseline would drop it")
+                         "chunk by chunk beside the kernels -- and add an `end_to_end` object to the line (SURVEY 8(d)).  On with --full "
+                         "for the Layer III line; this flag forces it where a plain run or --no-cpu-baseline would drop it")
     ap.add_argument("--no-host-io", action="store_true", help="skip the end_to_end leg")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="skip the short runs of configs[3], configs[4] and Layer II that the default line (N = 1, configs[1] at its own "
+                    help="skip the short runs of configs[3], configs[4] and Layer II that the --full line (N = 1, configs[1] at its own "
                          "size) carries as `other_workloads`")
     ap.add_argument("--no-cpu-baseline", action="store_true",
                     help="profiling pass: skip the timed CPU baseline, the end_to_end leg and the other workloads (only the "
-                         "headline pipeline's kernels are launched); a small oracle parity check remains")
+                         "headline pipeline's kernels are launched); with --full, a small oracle parity check remains")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the parity spot check against the oracle and the reference binary, the timed CPU "
+                         "baseline, the engine clock, the end_to_end leg and the other workloads (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0's batch) to DIR as .npy files")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be at least 1")
@@ -793,7 +829,7 @@ def main():
         wl.step()
     barrier()
     t_before = wl.batch.total_timing()
-    clock = ClockSampler(dev_index).start() if rank == 0 else None
+    clock = ClockSampler(dev_index).start() if rank == 0 and args.full else None
     t0 = time.perf_counter()
     for _ in range(args.steps):
         if sync_each:
@@ -808,10 +844,12 @@ def main():
     loop_ms, all_ms, launches = t_after[0] - t_before[0], t_after[1] - t_before[1], t_after[2] - t_before[2]
     assert t_after[3] - t_before[3] == args.steps
     dt = float(coll.reduce(dt, "max"))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl.out, wl.out_len)
 
     # End to end with PCIe (--host-io): the same K steps with the PCM in page-locked host memory and the bytes delivered to it.
     end_to_end = None
-    if args.host_io or not (args.no_host_io or args.no_cpu_baseline):
+    if args.host_io or (args.full and not (args.no_host_io or args.no_cpu_baseline)):
         # (every rank page-locks its own copy -- 7.9 GB at the default size; a rank that cannot says so, and ALL ranks then leave the
         # leg out together: a rank missing at the barriers below would hang the others)
         h_pcm = h_out = h_len = None
@@ -864,30 +902,31 @@ def main():
     # parity spot check on the exact device bytes of THIS rank (every rank checks its own streams; the CPU baseline is
     # timed on rank 0 -- at every N, AFTER the timed region: the other ranks do their small check and wait at the
     # parity vote below -- so that every bench line carries it)
-    timed_baseline = rank == 0 and not args.no_cpu_baseline
+    timed_baseline = args.full and rank == 0 and not args.no_cpu_baseline
     cores = all_host_cores() if timed_baseline else 8  # (all of the host's cores, whatever the rank was pinned to for its GPU)
     n_sample = max(4, cores * 2) if timed_baseline else 8
     idx = sorted(set(np.linspace(0, S - 1, n_sample).astype(int).tolist()))
-    pcm_sample = [wl.pcm[i].cpu().numpy() for i in idx]
-    kb_sample = [wl.kbps[i] for i in idx]
     out_h, len_h = wl.out[idx].cpu().numpy(), wl.out_len[idx].cpu().numpy()
     got = [out_h[k, : len_h[k]].tobytes() for k in range(len(idx))]
-    fps, refs = cpu_baseline(pcm_sample, rate, kb_sample, C, cores)
-    bad = [int(idx[k]) for k in range(len(idx)) if got[k] != refs[k]]
-    if end_to_end is not None and not end_to_end["bytes_equal_resident_path"]:
+    bad, cpu = [], None
+    if args.full:  # the parity spot check against the oracle (and the reference binary, where the baseline is timed)
+        pcm_sample = [wl.pcm[i].cpu().numpy() for i in idx]
+        kb_sample = [wl.kbps[i] for i in idx]
+        fps, refs = cpu_baseline(pcm_sample, rate, kb_sample, C, cores)
+        bad = [int(idx[k]) for k in range(len(idx)) if got[k] != refs[k]]
+        if timed_baseline:
+            cpu = {"value": round(fps, 1), "unit": "frames/s", "cores": cores, "kind": "port",
+                   "sample": "%d of this batch's streams x %d frames, oracle/liboracle.so, one thread per stream" % (len(idx), nf)}
+            ref = reference_baseline(pcm_sample, rate, kb_sample, C, cores)
+            if ref is not None:  # the reference binary itself: the baseline proper, and a second parity witness
+                rfps, routs = ref
+                fb3 = [mp3.frame_bytes(rate, k) for k in kb_sample]
+                bad += [int(idx[k]) for k in range(len(idx)) if without_private_bit(got[k], fb3[k]) != without_private_bit(routs[k], fb3[k]) and int(idx[k]) not in bad]
+                cpu = {"value": round(rfps, 1), "unit": "frames/s", "cores": cores, "kind": "reference",
+                       "sample": "%d of this batch's streams x %d frames, oracle/_ref/encode (unmodified reference, gcc -O2), one process per stream" % (len(idx), nf),
+                       "port_value": round(fps, 1)}
+    if end_to_end is not None and not end_to_end.get("bytes_equal_resident_path", True):
         bad.append(-1)  # the host path delivered other bytes than the device path: a parity failure like any other
-    cpu = None
-    if timed_baseline:
-        cpu = {"value": round(fps, 1), "unit": "frames/s", "cores": cores, "kind": "port",
-               "sample": "%d of this batch's streams x %d frames, oracle/liboracle.so, one thread per stream" % (len(idx), nf)}
-        ref = reference_baseline(pcm_sample, rate, kb_sample, C, cores)
-        if ref is not None:  # the reference binary itself: the baseline proper, and a second parity witness
-            rfps, routs = ref
-            fb3 = [mp3.frame_bytes(rate, k) for k in kb_sample]
-            bad += [int(idx[k]) for k in range(len(idx)) if without_private_bit(got[k], fb3[k]) != without_private_bit(routs[k], fb3[k]) and int(idx[k]) not in bad]
-            cpu = {"value": round(rfps, 1), "unit": "frames/s", "cores": cores, "kind": "reference",
-                   "sample": "%d of this batch's streams x %d frames, oracle/_ref/encode (unmodified reference, gcc -O2), one process per stream" % (len(idx), nf),
-                   "port_value": round(fps, 1)}
     # which streams each rank encoded, and a digest of what it produced (the ranks' ranges must be disjoint, their bytes differ)
     import hashlib
     n_bad = int(coll.reduce(len(bad), "sum"))
@@ -954,15 +993,16 @@ def main():
             "collective_backend": coll.backend,
             "cpu_affinity_rank0": affinity,
             "parity_spot_check": {"streams_per_rank": len(idx), "bit_exact": parity_ok, "mismatching_streams_rank0": bad,
-                                  "witness": "oracle/liboracle.so" + (" + oracle/_ref/encode" if cpu and cpu["kind"] == "reference" else "")},
+                                  "witness": "oracle/liboracle.so" + (" + oracle/_ref/encode" if cpu and cpu["kind"] == "reference" else "")}
+                                 if args.full else None,
         }
     wl.close()
     del wl
     others_ok = True
     if rank == 0:
         # The other workloads, driver-visible (short runs; the headline above is untouched by them: its batch is closed).
-        # Only on the default line: one GPU, configs[1] at its own size.
-        if world == 1 and cfg_id == 1 and default_size and not (args.no_other_workloads or args.no_cpu_baseline):
+        # Only on the default line with --full: one GPU, configs[1] at its own size.
+        if args.full and world == 1 and cfg_id == 1 and default_size and not (args.no_other_workloads or args.no_cpu_baseline):
             # (whatever happens in here -- no memory for a batch of 16 384 streams, an oracle error --, the finished headline
             # measurement is printed; the failure is recorded in the line and in the exit code)
             try:

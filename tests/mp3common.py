@@ -44,12 +44,24 @@ GRSIDE_DT = np.dtype([
 SIDE_DT = np.dtype([("main_data_begin", "<i4"), ("resvDrain", "<i4"), ("scfsi", "<i4", (2, 4)), ("gr", GRSIDE_DT, (2, 2))])
 
 
+def _build_once(subdir, so, *targets):
+    """make `so` where it is missing, one process at a time: pytest-xdist workers that all find it missing would otherwise
+    compile, link and load the same files at once (a worker then loads a library another one is still writing)"""
+    import fcntl
+    d = os.path.join(ROOT, subdir, "_build")
+    os.makedirs(d, exist_ok=True)
+    with open(os.path.join(d, ".build.lock"), "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        if not os.path.exists(so):
+            subprocess.run(["make", "-s", "-C", os.path.join(ROOT, subdir)] + list(targets), check=True)
+
+
 def build_oracle():
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "oracle"], check=True)
+    _build_once("oracle", ORACLE_SO, "oracle")
 
 
 def build_emu():
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "hipemu")], check=True)
+    _build_once(os.path.join("tests", "hipemu"), EMU_SO)
 
 
 class ReferenceAborts(Exception):
@@ -63,8 +75,7 @@ class ReferenceAborts(Exception):
 
 class Oracle:
     def __init__(self):
-        if not os.path.exists(ORACLE_SO):
-            build_oracle()
+        build_oracle()  # (a no-op where it is built)
         self.lib = ctypes.CDLL(ORACLE_SO)
         self.lib.mp3o_encode_pcm_ex.restype = ctypes.c_size_t
         self.lib.mp3o_encode_pcm_ex.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p,
@@ -130,8 +141,8 @@ class Mp3mi:
 
     def __init__(self, emu=False):
         path = EMU_SO if emu else PRODUCT_SO
-        if emu and not os.path.exists(path):
-            build_emu()
+        if emu:
+            build_emu()  # (a no-op where it is built)
         self.lib = ctypes.CDLL(path)
         L = self.lib
         L.mp3mi_batch_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.c_int,

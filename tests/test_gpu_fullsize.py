@@ -92,7 +92,7 @@ def test_schedule_between_the_tuned_sizes(product, oracle):
 
 @pytest.mark.parametrize("layer", [3, 2])
 def test_two_ranks_share_the_gpu(layer):
-    """bench.py's N > 1 path rehearsed on the one-GPU box, as the driver would start it: plain `python bench.py --gpus 2`.
+    """bench.py's N > 1 path rehearsed on the one-GPU box, as the driver would start it: plain `python bench.py --gpus 2 --full`.
     bench.py itself starts the two ranks (gloo for the barrier and the max-over-ranks time, both on device 0:
     MP3MI_BENCH_ONE_GPU=1); each encodes its own stream range and checks it against the oracle; the line says n_gpus 2,
     bit_exact, and names two disjoint ranges with different bytes.  A child process: this one is not replaced."""
@@ -101,7 +101,7 @@ def test_two_ranks_share_the_gpu(layer):
     env = dict(os.environ, MP3MI_BENCH_ONE_GPU="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--full",
                         "--streams", "1024", "--frames", "48", "--layer", str(layer)], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
@@ -134,7 +134,7 @@ def test_four_ranks_rehearse_the_eight_gpu_command_on_one_gpu():
     env = dict(os.environ, MP3MI_BENCH_ONE_GPU="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "1", "--warmup", "0", "--streams", "512", "--frames", "48"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "1", "--warmup", "0", "--full", "--streams", "512", "--frames", "48"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]

@@ -6,7 +6,7 @@ cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 for r in $(seq 1 $R); do
   for x in $A $B; do
     export $V=$x
-    ms=$(python3 bench.py --no-cpu-baseline --steps 3 --warmup 1 "$@" 2>/dev/null | python3 -c "import json,sys;d=json.loads(sys.stdin.read().strip().splitlines()[-1]);print('%.2f ms/step exact %s' % (d['ms_per_step'], d['parity_spot_check']['bit_exact']))")
+    ms=$(python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 "$@" 2>/dev/null | python3 -c "import json,sys;d=json.loads(sys.stdin.read().strip().splitlines()[-1]);print('%.2f ms/step exact %s' % (d['ms_per_step'], d['parity_spot_check']['bit_exact']))")
     rm -rf /tmp/ab_tl
     timeout 240 rocprofv3 --kernel-trace --output-format csv -d /tmp/ab_tl -o tl -- python3 bench.py --no-cpu-baseline --steps 1 --warmup 1 "$@" > /dev/null 2>&1
     python3 - "$V=$x" "$r" "$ms" <<'PY'

@@ -15,7 +15,7 @@ export TMPDIR=/tmp
 for r in $(seq 1 $R); do
   for n in $A $B; do
     export MP3MI_LIB=$GRAFT_REPO_ROOT/mp3-enc-bsd_amd/ab_now/lib$n.so
-    python3 bench.py --no-cpu-baseline --steps 3 --warmup 1 "$@" > $out/bench_${n}_$r.json 2> $out/bench_${n}_$r.err || { echo "bench failed for $n"; tail -5 $out/bench_${n}_$r.err; }
+    python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 "$@" > $out/bench_${n}_$r.json 2> $out/bench_${n}_$r.err || { echo "bench failed for $n"; tail -5 $out/bench_${n}_$r.err; }
     ms=$(python3 -c "import json;d=json.loads(open('$out/bench_${n}_$r.json').read().strip().splitlines()[-1]);print('%.2f ms/step  value %s  exact %s' % (d['ms_per_step'], d['value'], d['parity_spot_check']['bit_exact']))" 2>/dev/null)
     rm -rf /tmp/ab_tl
     timeout 240 rocprofv3 --kernel-trace --output-format csv -d /tmp/ab_tl -o tl -- python3 bench.py --no-cpu-baseline --steps 1 --warmup 1 "$@" > /dev/null 2> $out/tl.err

@@ -15,7 +15,7 @@ for r in $(seq 1 $R); do
   for c in "${cfgs[@]}"; do
     n=${c%%:*}; e=${c#*:}
     envs=(); IFS=',' read -ra kv <<< "$e"; for x in "${kv[@]}"; do [ -n "$x" ] && envs+=("$x"); done
-    env "${envs[@]}" python3 bench.py --no-cpu-baseline --steps 4 --warmup 1 "$@" > $out/bench_${n}_$r.json 2> $out/bench_${n}_$r.err || { echo "bench failed for $n"; tail -5 $out/bench_${n}_$r.err; }
+    env "${envs[@]}" python3 bench.py --full --no-cpu-baseline --steps 4 --warmup 1 "$@" > $out/bench_${n}_$r.json 2> $out/bench_${n}_$r.err || { echo "bench failed for $n"; tail -5 $out/bench_${n}_$r.err; }
     ms=$(python3 -c "import json;d=json.loads(open('$out/bench_${n}_$r.json').read().strip().splitlines()[-1]);print('%.2f ms/step  value %s  exact %s' % (d['ms_per_step'], d['value'], d['parity_spot_check']['bit_exact']))" 2>/dev/null)
     gaps=""
     if [ $r -eq 1 ]; then

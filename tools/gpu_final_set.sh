@@ -3,7 +3,7 @@
 # 20 minutes; every stage writes under gpurun_out/<tag>/ and stamps what it writes with the library's source hash):
 #   a  profile   kernel trace + FETCH / WRITE passes + four SQ passes of the default bench command -> profile.json, kernel_stats.csv;
 #                the kernel TIMELINE of the last step of two calls issued back to back -> timeline.txt
-#   b  bench     the bench lines: the default command (20 steps: value, roofline, cpu_baseline, end_to_end, other_workloads),
+#   b  bench     the bench lines: the --full command (20 steps: value, roofline, cpu_baseline, end_to_end, other_workloads),
 #                configs 2 / 3 / 4, Layers II / I, two ranks on one GPU (plain `bench.py --gpus 2`)
 #   c  diag      k_loop's phase profile and the one-ulp census (diagnostic builds in /tmp, never the product library)
 #   d  parity    every stream of the four workloads against the oracle, every 32nd against the reference binary
@@ -52,11 +52,11 @@ PY
   tail -2 $out/timeline.txt
 ;; esac
 case $stages in *b*)
-  python3 bench.py --steps 20 --warmup 2 > $out/bench_config1.json 2> $out/bench_config1.err; echo "config 1: rc $?"; stamp $out/bench_config1.json
-  for c in 2 3 4; do python3 bench.py --config $c --steps 6 --warmup 1 > $out/bench_config$c.json 2> $out/bench_config$c.err; echo "config $c: rc $?"; stamp $out/bench_config$c.json; done
-  for l in 2 1; do python3 bench.py --layer $l --steps 6 --warmup 1 > $out/bench_layer$l.json 2> $out/bench_layer$l.err; echo "layer $l: rc $?"; stamp $out/bench_layer$l.json; done
-  MP3MI_BENCH_ONE_GPU=1 python3 bench.py --gpus 2 --steps 3 --warmup 1 --streams 2048 > $out/bench_two_ranks_one_gpu.json 2> $out/bench_two_ranks.err; echo "two ranks: rc $?"; stamp $out/bench_two_ranks_one_gpu.json
-  MP3MI_BENCH_ONE_GPU=1 python3 bench.py --gpus 4 --steps 2 --warmup 1 --streams 1024 > $out/bench_four_ranks_one_gpu.json 2> $out/bench_four_ranks.err; echo "four ranks: rc $?"; stamp $out/bench_four_ranks_one_gpu.json
+  python3 bench.py --full --steps 20 --warmup 2 > $out/bench_config1.json 2> $out/bench_config1.err; echo "config 1: rc $?"; stamp $out/bench_config1.json
+  for c in 2 3 4; do python3 bench.py --full --config $c --steps 6 --warmup 1 > $out/bench_config$c.json 2> $out/bench_config$c.err; echo "config $c: rc $?"; stamp $out/bench_config$c.json; done
+  for l in 2 1; do python3 bench.py --full --layer $l --steps 6 --warmup 1 > $out/bench_layer$l.json 2> $out/bench_layer$l.err; echo "layer $l: rc $?"; stamp $out/bench_layer$l.json; done
+  MP3MI_BENCH_ONE_GPU=1 python3 bench.py --full --gpus 2 --steps 3 --warmup 1 --streams 2048 > $out/bench_two_ranks_one_gpu.json 2> $out/bench_two_ranks.err; echo "two ranks: rc $?"; stamp $out/bench_two_ranks_one_gpu.json
+  MP3MI_BENCH_ONE_GPU=1 python3 bench.py --full --gpus 4 --steps 2 --warmup 1 --streams 1024 > $out/bench_four_ranks_one_gpu.json 2> $out/bench_four_ranks.err; echo "four ranks: rc $?"; stamp $out/bench_four_ranks_one_gpu.json
   python3 - $out <<'PY'
 import json, sys, glob, os
 for p in sorted(glob.glob(sys.argv[1] + "/bench_*.json")):
