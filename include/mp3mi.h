@@ -57,20 +57,14 @@ enum {
                                  out_len is 0, every other stream's output is valid -- see mp3mi_batch_stream_status */
 };
 
-/* Scheduling and scratch options of a batch.  The defaults are right for production use; the fields exist for
- * measurements (tools/) and tests.  Zero-initialise, set struct_size = sizeof, or call mp3mi_batch_options_default. */
+/* Scratch, scheduling and drop-in options of a batch.  The defaults are right for production use.  Fill the struct with
+ * mp3mi_batch_options_default (or mp3mi_batch_options_from_env), then change fields: it sets struct_size and abi, and a
+ * struct without them -- a zero-initialised one among them -- is refused. */
 typedef struct mp3mi_batch_options {
     uint32_t struct_size;     /* sizeof(mp3mi_batch_options) of the caller's build */
     uint32_t scratch_mb;      /* budget of the per-chunk scratch buffers in MiB (~78 KB per frame and stream); 0 = 32768 */
     int32_t chunk_frames;     /* upper limit of a chunk's length in frames; 0 = whatever the budget allows */
     uint32_t test_flags;      /* MP3MI_TEST_*: force the exact tier of the two-tier decisions (as mp3mi_batch_set_test_flags) */
-    int32_t call_overlap;     /* a call's feed-forward kernels may start beside the loop kernels of the call before: -1 default (on), 0, 1 */
-    int32_t gate;             /* the start census that orders the two HIP streams' kernels on the chip: -1 default (on), 0, 1 */
-    int32_t placement;        /* streams placed on SIMDs by their cost in the chunk before: -1 default (on for >= 2 streams per SIMD), 0, 1 */
-    int32_t loop_part_streams; /* streams per part (multiple of 64); 0 = the resident wavefronts of the device */
-    int32_t y_after_loop;     /* the filterbank / MDCT / prep kernels of a chunk wait for the loop kernel before it: -1 default (only for a part larger than the resident wavefronts), 0, 1 */
-    int32_t psy_beside;       /* what of the psychoacoustic stage runs beside a loop kernel: -1 default (k_cw + k_part + k_psy beside a
-                                 resident loop kernel), 0 nothing, 1 k_cw + k_part + k_psy, 2 k_psy only */
     int32_t dropin_lookahead; /* the drop-in symbols' look-ahead (mp3mi_dropin.h): -1 default = 2 the filterbank's (and mdct_sub behind it: memory of the current frame only), 0 none, 1 all (buffer lifetime requirement: mp3mi_dropin.h),
                                  3 L3psycho_anal's only, 4 all but iteration_loop's / III_format_bitstream's.  Not a property of a batch: the hidden default stream of the drop-in symbols
                                  reads it through mp3mi_batch_options_from_env (MP3MI_DROPIN_LOOKAHEAD) */
@@ -83,14 +77,13 @@ typedef struct mp3mi_batch_options {
                                  layouts apart (round 5 replaced a field in the middle and kept the size): a caller built against another layout is
                                  refused (MP3MI_ERR_ARG) instead of having its fields read as their neighbours */
 } mp3mi_batch_options;
-#define MP3MI_OPTIONS_ABI 6u  /* raised whenever the struct's layout or a field's meaning changes; new fields go at the END */
-/* mp3mi_batch_create_ex returns MP3MI_ERR_ARG for a value outside the ranges named above (the three-state fields take
- * -1, 0, 1; psy_beside -1 .. 2; dropin_lookahead -1 .. 4; loop_part_streams a multiple of 64; unknown test flags). */
+#define MP3MI_OPTIONS_ABI 7u  /* raised whenever the struct's layout or a field's meaning changes; new fields go at the END */
+/* mp3mi_batch_create_ex returns MP3MI_ERR_ARG for a value outside the ranges named above (chunk_frames >= 0; call_hold
+ * -1, 0, 1; dropin_lookahead -1 .. 4; dropin_stats 0, 1; unknown test flags). */
 void mp3mi_batch_options_default(mp3mi_batch_options *opt);
 /* The same, then overridden by the MP3MI_* environment variables that tools/ and tests/ use (MP3MI_SCRATCH_MB,
- * MP3MI_CHUNK_FRAMES, MP3MI_{NOISE,PHASE,PSY,QUANT,PREP,CW}_EXACT, MP3MI_CALL_OVERLAP, MP3MI_NO_GATE, MP3MI_NO_PLACE,
- * MP3MI_LOOP_PART_STREAMS, MP3MI_CALL_HOLD, MP3MI_Y_AFTER_LOOP, MP3MI_PSY_BESIDE, MP3MI_DROPIN_LOOKAHEAD, MP3MI_DROPIN_STATS).  This is the ONLY place the library
- * reads its environment: mp3mi_batch_create calls it once; mp3mi_batch_create_ex never does. */
+ * MP3MI_CHUNK_FRAMES, MP3MI_{NOISE,PHASE,PSY,QUANT,PREP,CW}_EXACT, MP3MI_CALL_HOLD, MP3MI_DROPIN_LOOKAHEAD, MP3MI_DROPIN_STATS).
+ * This is the ONLY place the library reads its environment: mp3mi_batch_create calls it once; mp3mi_batch_create_ex never does. */
 void mp3mi_batch_options_from_env(mp3mi_batch_options *opt);
 
 /* Creates an encoder for n_streams independent streams that share sample rate and channel

@@ -54,7 +54,6 @@ struct mp3mi_batch {
     hipEvent_t ev_done;      // everything of the previous encode call is done
     hipEvent_t ev_hist;      // the front stream's last work of a call (the PCM history hand-over) is enqueued
     bool have_done;
-    bool overlap_calls;      // a call's front stream does not wait for the call before it (MP3MI_CALL_OVERLAP=0: it does)
     // The last k_loop of a call is HELD on the device (k_hold, k_loop.hip) until the next call's first transforms are through:
     // hold_flag is one word of host memory mapped into the device's address space, hold_seq the ticket of the hold in
     // force (tickets only grow), held = a hold is in force that neither a next call nor the host has let go yet
@@ -62,13 +61,12 @@ struct mp3mi_batch {
     unsigned hold_seq;
     bool held, hold_calls;
     int slot_base;           // parity of the double-buffer slot the next call's chunk 0 takes
-    unsigned *gate_count;    // start census of k_loop's wavefronts (device memory, only ever grows), NULL = gate off
+    unsigned *gate_count;    // start census of k_loop's wavefronts (device memory, only ever grows)
     unsigned gate_total;     // census value once every wavefront launched so far has started
     unsigned gate_first;     // ... the same (kept for the gate's target: the census once the LAST launch is resident)
     int *place_order, *place_cost; // k_loop stream placement (mp3mi_loop_place), NULL = off
     unsigned *place_zero;    // taken[n] + simd_slots + simd_idx + ticket + scan, zeroed before every k_loop
     int n_simd;
-    mp3mi_batch_options opt; // as given at create time (defaults resolved where a field says "-1 default")
     unsigned *voided;        // device counter: streams whose file a call voided (the reference dies on them), since the last sync
     int32_t *status_dev;     // [S]: what mp3mi_batch_stream_status copies out; between a flush and the next encode / reset it HOLDS the ended streams' status
     bool status_kept;        // status_dev holds the status of the streams the last flush ended (their state is reset)
@@ -199,7 +197,7 @@ extern "C" void mp3mi_batch_options_default(mp3mi_batch_options *o)
     memset(o, 0, sizeof(*o));
     o->struct_size = (uint32_t) sizeof(*o);
     o->abi = MP3MI_OPTIONS_ABI;
-    o->call_overlap = o->gate = o->placement = o->y_after_loop = o->psy_beside = o->dropin_lookahead = o->call_hold = -1;
+    o->dropin_lookahead = o->call_hold = -1;
 }
 
 // The one place the library reads its environment (mp3mi.h): the knobs of tools/ and tests/.
@@ -217,12 +215,6 @@ extern "C" void mp3mi_batch_options_from_env(mp3mi_batch_options *o)
     if (on(getenv("MP3MI_QUANT_EXACT"))) o->test_flags |= MP3MI_TEST_QUANT_EXACT;
     if (on(getenv("MP3MI_PREP_EXACT"))) o->test_flags |= MP3MI_TEST_PREP_EXACT;
     if (on(getenv("MP3MI_CW_EXACT"))) o->test_flags |= MP3MI_TEST_CW_EXACT;
-    if ((e = getenv("MP3MI_CALL_OVERLAP"))) o->call_overlap = atoi(e) != 0;
-    if (on(getenv("MP3MI_NO_GATE"))) o->gate = 0;
-    if (on(getenv("MP3MI_NO_PLACE"))) o->placement = 0;
-    if ((e = getenv("MP3MI_LOOP_PART_STREAMS")) && atoi(e) >= 64) o->loop_part_streams = atoi(e) / 64 * 64;
-    if ((e = getenv("MP3MI_Y_AFTER_LOOP"))) o->y_after_loop = atoi(e) != 0;
-    if ((e = getenv("MP3MI_PSY_BESIDE"))) o->psy_beside = atoi(e) == 2 ? 2 : (atoi(e) ? 1 : 0);
     if ((e = getenv("MP3MI_CALL_HOLD"))) o->call_hold = atoi(e) != 0;
     if (on(getenv("MP3MI_DROPIN_STATS"))) o->dropin_stats = 1;
     if ((e = getenv("MP3MI_DROPIN_LOOKAHEAD")) && atoi(e) >= 0 && atoi(e) <= 4) o->dropin_lookahead = atoi(e);
@@ -262,7 +254,6 @@ static int batch_build(mp3mi_batch *b, int n_streams, int rate_hz, int channels,
     const size_t per_gc = MP3MI_HBLK_P * 4 + MP3MI_PART_P * 12 + 3 * MP3MI_HBLK_S * 4 + MP3MI_FFT_BINS * 4 + 50 * 8 + 12 * 4 +
                           2 * (sizeof(mp3mi_psy_out) + sizeof(mp3mi_loop_prep) + 576 * 8) + 576 * 8 + 576 * 2;
     const size_t per_frame = per_gc * 2 * (size_t) channels + sizeof(mp3mi_frame_side);
-    b->opt = opt;
     const size_t budget = (size_t) (opt.scratch_mb ? opt.scratch_mb : 32768u) << 20;
     long cf = (long) (budget / (per_frame * (size_t) n_streams));
     if (cf < 1) cf = 1;
@@ -284,12 +275,10 @@ static int batch_build(mp3mi_batch *b, int n_streams, int rate_hz, int channels,
         CHK(hipStreamCreateWithPriority(&b->stream, hipStreamDefault, least));
         CHK(hipStreamCreateWithPriority(&b->lstream, hipStreamDefault, greatest));
     }
-    {   // parts: as few as hold the batch with at most mp3mi_loop_resident() streams each, equal in size (a multiple of
-        // 64); options.loop_part_streams overrides (tests)
+    {   // parts: as few as hold the batch with at most mp3mi_loop_resident() streams each, equal in size (a multiple of 64)
         const int resident = mp3mi_loop_resident();
-        int np = (n_streams + resident - 1) / resident;
-        int ps = ((n_streams + np - 1) / np + 63) / 64 * 64;
-        if (opt.loop_part_streams >= 64) ps = opt.loop_part_streams;
+        const int np = (n_streams + resident - 1) / resident;
+        const int ps = ((n_streams + np - 1) / np + 63) / 64 * 64;
         b->part_streams = ps;
         b->n_parts = (n_streams + ps - 1) / ps;
         b->ev_front.assign(2 * (size_t) b->n_parts, (hipEvent_t) 0);
@@ -304,24 +293,21 @@ static int batch_build(mp3mi_batch *b, int n_streams, int rate_hz, int channels,
     CHK(hipEventCreateWithFlags(&b->ev_hist, hipEventDisableTiming));
     b->have_done = false;
     b->last_slot = 0;
-    b->overlap_calls = opt.call_overlap != 0;
     b->slot_base = 0;
     b->test_flags = (int) (opt.test_flags & 15u) | ((opt.test_flags & MP3MI_TEST_CW_EXACT) ? 16 : 0) | ((opt.test_flags & MP3MI_TEST_PREP_LIST) ? 32 : 0);
     b->prep_exact = (opt.test_flags & MP3MI_TEST_PREP_EXACT) ? 1 : 0;
     b->hdr_flags = 0;
     b->hdr_mode = (channels == 1) ? 3 : 0;
     b->crc = 0;
-    b->gate_count = NULL; b->gate_total = 0; b->gate_first = 0;
-    b->hold_calls = opt.call_hold != 0 && opt.call_overlap != 0 && opt.gate != 0;
+    b->gate_total = 0; b->gate_first = 0;
+    b->hold_calls = opt.call_hold != 0;
     if (b->hold_calls) {
         CHK(hipHostMalloc((void **) &b->hold_flag_h, 64, hipHostMallocMapped));
         for (int i = 0; i < 16; i++) b->hold_flag_h[i] = 0;
         CHK(hipHostGetDevicePointer((void **) &b->hold_flag_d, b->hold_flag_h, 0));
     }
-    if (opt.gate != 0) {
-        CHK(hipMalloc((void **) &b->gate_count, 2 * sizeof(unsigned))); // [0] start census, [1] frames finished in this launch
-        CHK(hipMemset(b->gate_count, 0, 2 * sizeof(unsigned)));
-    }
+    CHK(hipMalloc((void **) &b->gate_count, 2 * sizeof(unsigned))); // [0] start census, [1] frames finished in this launch
+    CHK(hipMemset(b->gate_count, 0, 2 * sizeof(unsigned)));
     CHK(hipMalloc((void **) &b->voided, sizeof(unsigned)));
     CHK(hipMemset(b->voided, 0, sizeof(unsigned)));
     CHK(hipMalloc((void **) &b->status_dev, sizeof(int32_t) * (size_t) n_streams));
@@ -332,7 +318,7 @@ static int batch_build(mp3mi_batch *b, int n_streams, int rate_hz, int channels,
         CHK(hipGetDevice(&dev));
         CHK(hipGetDeviceProperties(&prop, dev));
         b->n_simd = prop.multiProcessorCount * 4;
-        if (opt.placement != 0 && (n_streams >= 2 * b->n_simd || opt.placement == 1)) { // placement only matters when SIMDs hold several streams
+        if (n_streams >= 2 * b->n_simd) { // placement only matters when SIMDs hold several streams
             CHK(hipMalloc((void **) &b->place_order, sizeof(int) * n_streams));
             CHK(hipMalloc((void **) &b->place_cost, sizeof(int) * n_streams));
             CHK(hipMalloc((void **) &b->place_zero, sizeof(unsigned) * ((size_t) n_streams + 2 * MP3MI_PLACE_KEYS + 2)));
@@ -411,10 +397,8 @@ extern "C" int mp3mi_batch_create_ex(mp3mi_batch **out, int n_streams, int rate_
     if (opt_in) {
         if (opt_in->struct_size != sizeof(opt) || opt_in->abi != MP3MI_OPTIONS_ABI) return MP3MI_ERR_ARG; // another version of the header
         opt = *opt_in;
-        auto tri = [](int v) { return v >= -1 && v <= 1; }; // -1 default, 0 off, 1 on
-        if ((opt.test_flags & ~(unsigned) (MP3MI_TEST_ALL_EXACT | MP3MI_TEST_PREP_LIST)) || opt.chunk_frames < 0 || opt.loop_part_streams < 0 ||
-            (opt.loop_part_streams % 64) != 0 || opt.psy_beside < -1 || opt.psy_beside > 2 || opt.dropin_lookahead < -1 || opt.dropin_lookahead > 4 || (opt.dropin_stats != 0 && opt.dropin_stats != 1) || !tri(opt.call_overlap) || !tri(opt.gate) ||
-            !tri(opt.placement) || !tri(opt.y_after_loop) || !tri(opt.call_hold))
+        if ((opt.test_flags & ~(unsigned) (MP3MI_TEST_ALL_EXACT | MP3MI_TEST_PREP_LIST)) || opt.chunk_frames < 0 || opt.dropin_lookahead < -1 ||
+            opt.dropin_lookahead > 4 || (opt.dropin_stats != 0 && opt.dropin_stats != 1) || opt.call_hold < -1 || opt.call_hold > 1)
             return MP3MI_ERR_ARG;
     }
     // argument errors first: they are the caller's, whatever the machine
@@ -641,11 +625,6 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
     // go on alternating from call to call, and a slot's writer waits for the k_loop that read it last, ev_loop).  So
     // this call's feed-forward kernels start at once and fill the chip while the last k_loop of the call before -- 4096
     // wavefronts, serial, nothing beside them -- runs out: back-to-back calls lose no pipeline fill.
-    // (options.call_overlap = 0: the front stream waits for the whole call before, as reset / flush still do.)
-    if (b->have_done && !b->overlap_calls) {
-        hold_release(b);
-        CHK(hipStreamWaitEvent(b->stream, b->ev_done, 0));
-    }
     // a whole-file call starts every stream afresh; a streaming call continues (the first one after create / reset /
     // flush / a whole-file call starts afresh too)
     if (whole_file || (b->frames_done == 0 && !b->fresh)) {
@@ -754,50 +733,43 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         }
     }
     const size_t psy_state_bytes = mp3mi_psy_state_size() * (size_t) C, loop_state_bytes = mp3mi_loop_state_size();
-    // which: 1 the FFTs, 2 k_cw, 4 the partition sums (k_part), 8 k_psy
+    // which: 1 the FFTs, 2 k_cw, the partition sums (k_part) and k_psy (passed on as mp3mi_launch_fft's which, whose bit 1 is k_cw)
     auto stage_x = [&](int k, int which) -> int {
         const item_view v = view(k);
         const size_t r = v.rec0;
         if (hc && (which & 1) && k % P == 0) CHK(hipStreamWaitEvent(b->stream, b->hio.t_up[hc->slot][2 * (k / P) + 1], 0)); // the chunk's PCM is up
-        if (which & 3) {
-            mp3mi_launch_fft(b->T, v.g, pcm_dev + v.s0 * pcm_pitch, b->energy_l + r * MP3MI_HBLK_P, b->energy_s + r * 3 * MP3MI_HBLK_S,
-                             b->fft_bins + r * MP3MI_FFT_BINS, b->cw_mid + r * 50, b->hist6 + r * 12, b->stream, which & 3);
-            CHK(hipGetLastError());
-        }
-        // the k_loop that read this region of the slot last (two chunks ago, maybe in the call before)
-        if ((which & 8) && b->slot_used[v.ev]) CHK(hipStreamWaitEvent(b->stream, b->ev_loop[v.ev], 0));
-        if (which & 12) {
+        mp3mi_launch_fft(b->T, v.g, pcm_dev + v.s0 * pcm_pitch, b->energy_l + r * MP3MI_HBLK_P, b->energy_s + r * 3 * MP3MI_HBLK_S,
+                         b->fft_bins + r * MP3MI_FFT_BINS, b->cw_mid + r * 50, b->hist6 + r * 12, b->stream, which);
+        CHK(hipGetLastError());
+        if (which & 2) {
+            // the k_loop that read this region of the slot last (two chunks ago, maybe in the call before)
+            if (b->slot_used[v.ev]) CHK(hipStreamWaitEvent(b->stream, b->ev_loop[v.ev], 0));
             mp3mi_launch_psy(b->T, v.g, b->energy_l + r * MP3MI_HBLK_P, b->energy_s + r * 3 * MP3MI_HBLK_S, b->cw_mid + r * 50, b->hist6 + r * 12,
                              b->fft_bins + r * MP3MI_FFT_BINS, b->cw_fix, (char *) b->psy_state + v.s0 * psy_state_bytes, b->part_eb + r * MP3MI_PART_P,
-                             b->part_cb + r * MP3MI_PART_P, b->psy[v.slot] + r, b->stream, (which >> 2) & 3);
+                             b->part_cb + r * MP3MI_PART_P, b->psy[v.slot] + r, b->stream);
             CHK(hipGetLastError());
         }
         return MP3MI_OK;
     };
-    // which of stage X runs beside the k_loop before the item's own, and whether the item's stage Y waits for that k_loop (below)
-    auto y_after = [&](const item_view &iv) {
-        return b->opt.y_after_loop >= 0 ? b->opt.y_after_loop != 0 : iv.g.n_streams > mp3mi_loop_resident();
-    };
-    auto beside_of = [&](const item_view &iv) {
-        int bs = y_after(iv) ? 0 : 14;
-        if (b->opt.psy_beside >= 0) bs = b->opt.psy_beside == 2 ? 8 : (b->opt.psy_beside ? 14 : 0);
-        return bs;
-    };
+    // A part larger than the resident wavefronts (on the emulator, whose single CU holds 16) keeps every SIMD full to its end,
+    // so the feed-forward kernels of the next item find no freed slots beside it, only cycles to take: there the item's
+    // stage Y waits for the k_loop before it, and nothing of stage X runs beside that k_loop.
+    auto y_after = [&](const item_view &iv) { return iv.g.n_streams > mp3mi_loop_resident(); };
     // The call before this one may have left its last k_loop HELD (k_hold): this call's first item then takes the place
     // "the next item" has inside a call -- its transforms run now, in front of that k_loop, the hold is let go behind them,
     // and the rest of the item runs beside that k_loop, behind the gate, like every item after it.
     bool joined = false;
     {
         const item_view v0 = view(0);
-        if (b->held && !y_after(v0) && b->gate_count) {
-            if (stage_x(0, 15 & ~beside_of(v0)) != MP3MI_OK) return MP3MI_ERR_HIP;
+        if (b->held && !y_after(v0)) {
+            if (stage_x(0, 1) != MP3MI_OK) return MP3MI_ERR_HIP;
             mp3mi_launch_hold_release(b->hold_flag_d, b->hold_seq, b->stream);
             CHK(hipGetLastError());
             b->held = false;
             joined = true;
         } else {
             hold_release(b);
-            if (stage_x(0, 15) != MP3MI_OK) return MP3MI_ERR_HIP;
+            if (stage_x(0, 3) != MP3MI_OK) return MP3MI_ERR_HIP;
         }
     }
     for (int k = 0; k < n_items; k++) {
@@ -805,22 +777,17 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         const mp3mi_geom &g = v.g;
         const size_t r = v.rec0;
         const bool follows = k >= 1 || joined; // a k_loop runs (or is about to) that this item's kernels go beside
-        // A part larger than the resident wavefronts (options.loop_part_streams, tests only) keeps every SIMD full to its
-        // end, so the feed-forward kernels of the next item find no freed slots beside it, only cycles to take: there
-        // stage Y waits for k_loop.
-        const bool y_after_loop = y_after(v);
-        // what of stage X runs beside k_loop (bits as for stage_x): all but the FFTs -- k_cw, k_part, k_psy are small in
-        // registers and LDS, the item's FFTs were done before that launch started, and the region k_psy writes was read
-        // last by the launch before it: 238.2 vs 247.2 ms per 4096 x 383 step with them between the launches.
-        // options.psy_beside = 0 / 1 / 2: nothing / all three / k_psy only.
-        const int beside = beside_of(v);
+        // what of stage X runs beside k_loop: all but the FFTs -- k_cw, k_part, k_psy are small in registers and LDS, the
+        // item's FFTs were done before that launch started, and the region k_psy writes was read last by the launch before
+        // it: 238.2 vs 247.2 ms per 4096 x 383 step with them between the launches.
+        const bool beside = !y_after(v);
         // ---- front stream: everything that does not depend on the bit reservoir ----
-        if (k >= 1 && y_after_loop) { // (the k_loop before this item's: view(k - 1))
+        if (k >= 1 && !beside) { // (the k_loop before this item's: view(k - 1))
             const item_view pv = view(k - 1);
             CHK(hipStreamWaitEvent(b->stream, b->ev_loop[pv.ev], 0));
-        } else if (follows && b->gate_count) // this item's kernels run behind k_loop(k - 1), once that is resident (<= 300 us)
+        } else if (follows) // this item's kernels run behind k_loop(k - 1), once that is resident (<= 300 us)
             mp3mi_launch_gate(b->gate_count, b->gate_first - 16u, 30000u, b->stream);
-        if (beside && follows && stage_x(k, beside) != MP3MI_OK) return MP3MI_ERR_HIP;
+        if (beside && follows && stage_x(k, 2) != MP3MI_OK) return MP3MI_ERR_HIP;
         mp3mi_launch_filter(b->T, g, pcm_dev + v.s0 * pcm_pitch, b->sbs + v.s0 * (size_t) (g.n_gran + 1) * (size_t) C * 576,
                             b->debug ? b->sb_dbg + r * 576 : NULL, b->stream);
         CHK(hipGetLastError());
@@ -837,7 +804,7 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
             // a busy chip sees to that -- this item's kernels take longer than the k_loop they run beside -- and an explicit wait
             // for that k_loop's end costs 1.4 ms per step, because the transforms then no longer slip in as its last CUs drain:
             // profiles/r05_experiments.txt, E7.)
-            if (stage_x(k + 1, 15 & ~beside_of(view(k + 1))) != MP3MI_OK) return MP3MI_ERR_HIP;
+            if (stage_x(k + 1, y_after(view(k + 1)) ? 3 : 1) != MP3MI_OK) return MP3MI_ERR_HIP;
         }
         CHK(hipEventRecord(b->ev_front[v.ev], b->stream));
         // ---- loop stream: the serial search and the formatter ----
@@ -854,7 +821,7 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
             place.ticket = place.simd_idx + MP3MI_PLACE_KEYS; place.scan = place.ticket + 1;
             place.n_simd = b->n_simd;
         }
-        if (b->gate_count) CHK(hipMemsetAsync(b->gate_count + 1, 0, sizeof(unsigned), b->lstream));
+        CHK(hipMemsetAsync(b->gate_count + 1, 0, sizeof(unsigned), b->lstream));
         CHK(hipStreamWaitEvent(b->lstream, b->ev_front[v.ev], 0));
         if (b->hold_calls && k == n_items - 1) {
             // the call's LAST k_loop: held until the next call's first transforms are through (its first item then runs beside

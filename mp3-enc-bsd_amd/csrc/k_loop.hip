@@ -1551,7 +1551,7 @@ static int loop_wg_cap(void) { return mp3mi_current_cu_count() * 4; }
 int mp3mi_loop_resident(void) { return loop_wg_cap() * LOOP_W; }
 
 // A wavefront per stream.  batch.cpp cuts a batch into parts of at most mp3mi_loop_resident() streams, so that a launch is
-// resident at once; a larger launch (options.loop_part_streams, tests) is valid all the same: the hardware starts the
+// resident at once; a larger launch (the emulator's parts of 64 streams) is valid all the same: the hardware starts the
 // workgroups beyond the resident ones as others end.
 void mp3mi_launch_loop(const mp3mi_tables *T, const mp3mi_geom &g, const double *xr, const mp3mi_psy_out *psy,
                        const mp3mi_loop_prep *prep, const int32_t *bits_per_frame, void *loop_state, int16_t *ix,

@@ -2,12 +2,17 @@
 its CPU-emulated test build (tests/hipemu/_build/libmp3mi_emu.so) and the oracle
 (oracle/_build/liboracle.so), plus numpy views of the records they exchange."""
 import ctypes
+import importlib
 import os
 import subprocess
+import sys
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+BatchOptions = importlib.import_module("mp3-enc-bsd_amd").BatchOptions  # include/mp3mi.h: mp3mi_batch_options (the package's one copy)
 # MP3MI_LIB: a diagnostic build of the same library (tools/gpu_ulp_census*.sh), as mp3-enc-bsd_amd/__init__.py honours it
 PRODUCT_SO = os.environ.get("MP3MI_LIB") or os.path.join(ROOT, "mp3-enc-bsd_amd", "libmp3mi.so")
 EMU_SO = os.path.join(ROOT, "tests", "hipemu", "_build", "libmp3mi_emu.so")
@@ -117,15 +122,6 @@ class Oracle:
 
 
 ERR_REFERENCE_ABORT = -6  # include/mp3mi.h
-
-
-class BatchOptions(ctypes.Structure):
-    """include/mp3mi.h: mp3mi_batch_options"""
-    _fields_ = [("struct_size", ctypes.c_uint32), ("scratch_mb", ctypes.c_uint32), ("chunk_frames", ctypes.c_int32),
-                ("test_flags", ctypes.c_uint32), ("call_overlap", ctypes.c_int32), ("gate", ctypes.c_int32),
-                ("placement", ctypes.c_int32), ("loop_part_streams", ctypes.c_int32),
-                ("y_after_loop", ctypes.c_int32), ("psy_beside", ctypes.c_int32), ("dropin_lookahead", ctypes.c_int32), ("call_hold", ctypes.c_int32), ("dropin_stats", ctypes.c_int32),
-                ("abi", ctypes.c_uint32)]
 
 
 class Mp3mi:
@@ -363,6 +359,12 @@ class BatchRun:
         a = ctypes.c_int()
         assert self.mp.lib.mp3mi_batch_debug_prep_fixups(self.b, ctypes.byref(a)) == 0
         return a.value
+
+    def last_timing(self):
+        """mp3mi_batch_last_timing: (ms inside k_loop, ms inside all kernels, k_loop launches) of the last call"""
+        loop, tot, n = ctypes.c_float(), ctypes.c_float(), ctypes.c_int()
+        assert self.mp.lib.mp3mi_batch_last_timing(self.b, ctypes.byref(loop), ctypes.byref(tot), ctypes.byref(n)) == 0
+        return loop.value, tot.value, n.value
 
     def cw_fixups(self):
         """(records listed for the second tier of the unpredictability, records) of the last call's last chunk"""

@@ -71,12 +71,12 @@ def test_a_streaming_call_reports_the_abort_when_it_happens(emu, oracle):
     abort_cases.streaming_case(emu, oracle)
 
 
-def test_options_out_of_range_are_refused(emu):
+def test_option_values_out_of_range_are_refused(emu):
     import ctypes
     from mp3common import BatchOptions
     L = emu.lib
-    for field, bad in (("gate", 2), ("gate", -2), ("placement", 5), ("call_overlap", -3), ("y_after_loop", 2), ("psy_beside", -2),
-                       ("psy_beside", 3), ("loop_part_streams", 100), ("loop_part_streams", -64), ("call_hold", 2)):
+    for field, bad in (("call_hold", 2), ("call_hold", -2), ("chunk_frames", -1), ("dropin_lookahead", -2), ("dropin_lookahead", 5),
+                       ("dropin_stats", 2), ("test_flags", 128)):
         o = BatchOptions()
         L.mp3mi_batch_options_default(ctypes.byref(o))
         setattr(o, field, bad)
@@ -111,11 +111,9 @@ def test_two_streams_mixed_bitrate_and_chunking(emu, oracle, monkeypatch):
         assert got[s] == oracle.encode(pcm[s], rate, kb, ch)[0]
 
 
-@pytest.mark.parametrize("mode", ["0", "1", "2"])
-def test_stage_x_schedules(emu, oracle, monkeypatch, mode):
-    """what of stage X is launched beside k_loop (MP3MI_PSY_BESIDE: nothing / k_cw, k_part, k_psy / k_psy only) is a
-    matter of launch order only: four chunks under each order, against the oracle"""
-    monkeypatch.setenv("MP3MI_PSY_BESIDE", mode)
+def test_stage_x_schedules(emu, oracle, monkeypatch):
+    """stage X split between the k_loop launches (the FFTs) and beside them (k_cw, k_part, k_psy) is a matter of launch
+    order only: four chunks, against the oracle"""
     monkeypatch.setenv("MP3MI_CHUNK_FRAMES", "1")
     nf, rate, ch = 4, 44100, 2
     pcm = np.stack([emu.synth(nf * 1152, ch, rate, 60 + s) for s in range(2)])
@@ -125,17 +123,23 @@ def test_stage_x_schedules(emu, oracle, monkeypatch, mode):
 
 
 def test_loop_in_parts(emu, oracle, monkeypatch):
-    """a batch of more streams than k_loop holds resident goes through it in parts (batch.cpp): 70 mono streams in
-    parts of 64 and 6, two chunks; every stream against the oracle"""
-    monkeypatch.setenv("MP3MI_LOOP_PART_STREAMS", "64")
+    """a batch of more streams than k_loop holds resident goes through it in parts (batch.cpp): 70 mono streams on the
+    emulator (16 resident) in parts of 64 and 6, two chunks -- a k_loop launch per part and chunk; every stream against
+    the oracle"""
+    from mp3common import BatchRun
     monkeypatch.setenv("MP3MI_CHUNK_FRAMES", "1")
     S, nf, rate, ch = 70, 2, 32000, 1
     base = np.stack([emu.synth(nf * 1152, ch, rate, 40 + s) for s in range(7)])
     pcm = np.stack([np.round(base[s % 7].astype(np.float64) * (1 + s // 7) / 10.0).astype(np.int16) for s in range(S)])
     kb = [(64, 96)[s % 2] for s in range(S)]
-    got = emu.encode_host(pcm, rate, ch, kb, nf)
+    run = BatchRun(emu, S, rate, ch, kb, nf, pcm=pcm)
+    try:
+        out, lens = run.encode()
+        assert run.last_timing()[2] == 2 * 2  # k_loop launches: 2 parts x 2 chunks
+    finally:
+        run.close()
     for s in range(S):
-        assert got[s] == oracle.encode(pcm[s], rate, kb[s], ch)[0], "stream %d" % s
+        assert out[s, :lens[s]].tobytes() == oracle.encode(pcm[s], rate, kb[s], ch)[0], "stream %d" % s
 
 
 def test_prep_exact_tier_matches_fast_tier(emu, oracle, monkeypatch):

@@ -5,8 +5,5 @@ run MP3MI_CHUNK_FRAMES=64
 run MP3MI_CHUNK_FRAMES=96
 run MP3MI_CHUNK_FRAMES=128
 run MP3MI_CHUNK_FRAMES=192
-run MP3MI_PSY_BESIDE=0
-run MP3MI_PSY_BESIDE=2
-run MP3MI_Y_AFTER_LOOP=1
 run MP3MI_SCRATCH_MB=65536
 run A=2
