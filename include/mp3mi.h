@@ -279,6 +279,21 @@ int mp3mi_debug_fastmath_bounds(double out[3]);
  * range the quantiser feeds it (csrc/k_debug.hip): out[0] = max |n - a * 65535| (the proof in csrc/k_loop.hip needs <= 0.5),
  * out[1] = non-monotone neighbours, out[2] = clamp / half mismatches (both 0). */
 int mp3mi_debug_pknorm_bound(double out[3]);
+/* Self-test hook: one quantise+count pass of k_loop (csrc/k_loop.hip), on n_gran granules of 576 xr each (rate_hz one of
+ * 44100 / 48000 / 32000).  gran[4 i ..]: the step q (MP3MI_STEP_MIN .. +800, the reference's quantizerStepSize), the block type
+ * (0..3), a rescale plan -- n_amp (0..16) amplifications of every scalefactor band by sqrt(2) and, before them, pre (0 / 1) one
+ * pre-emphasis (not with block type 2) -- applied by the kernel's own statements to xr in double and to its cached |xr|^(3/4) in
+ * float.  Out per granule: ix[576] (magnitudes), the rescaled xr[576] and MP3MI_QC_FIELDS words indexed by MP3MI_QC_*.  The
+ * last four are diagnostics: the all-zero shortcut was taken, the rare (exact-table) tier ran, the number of lines whose upper
+ * and lower estimates differ, the clamp at the table's end (`over`) was armed.  MP3MI_ERR_NO_DEVICE without a GPU. */
+enum {
+    MP3MI_QC_N_NZ, MP3MI_QC_N_BIG, MP3MI_QC_M1, MP3MI_QC_M2, MP3MI_QC_BITS, MP3MI_QC_BIG_VALUES, MP3MI_QC_COUNT1,
+    MP3MI_QC_COUNT1TABLE_SELECT, MP3MI_QC_TABLE_SELECT0, MP3MI_QC_TABLE_SELECT1, MP3MI_QC_TABLE_SELECT2,
+    MP3MI_QC_REGION0_COUNT, MP3MI_QC_REGION1_COUNT, MP3MI_QC_ADDRESS1, MP3MI_QC_ADDRESS2, MP3MI_QC_ADDRESS3,
+    MP3MI_QC_ALL_ZERO, MP3MI_QC_RARE_TIER, MP3MI_QC_N_DIFFER, MP3MI_QC_OVER, MP3MI_QC_FIELDS
+};
+int mp3mi_debug_quantize_count(int rate_hz, int n_gran, const double *xr, const int32_t *gran, int16_t *ix, double *xr_out,
+                               int32_t *fields);
 /* diagnostics: of the (granule, channel) records of the last call's LAST chunk, how many needed the second tier of
  * the unpredictability (k_part's check); *n_records receives their number.  Call after
  * mp3mi_batch_sync. */

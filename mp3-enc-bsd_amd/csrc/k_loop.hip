@@ -28,6 +28,7 @@
 // ~54 words of side information out.
 #include "mp3mi_host.h"
 #include "dmath.h"
+#include "mp3mi.h"
 #include <stdlib.h>
 
 typedef struct {
@@ -705,6 +706,10 @@ MP3MI_DEVFN int loop_count_bits(const mp3mi_tables *T, const loop_regs &R, loop_
     return bits;
 }
 
+// k_loop_qc.hip includes this file with MP3MI_LOOP_PASS_ONLY defined: it takes the pass above (quantiser and bit count) and
+// the self-test hook at the end of the file, and nothing of the search below.  (A second kernel in THIS translation unit that
+// calls the pass functions changes how the compiler allocates k_loop's registers.)
+#if !defined(MP3MI_LOOP_PASS_ONLY)
 // scfsi_m: bit b = scfsi[ch][b] of this frame when gr == 1, 0 for gr == 0 (whose scalefactors are always sent)
 MP3MI_DEVFN int loop_part2_length(const loop_gr &g, int scfsi_m)
 { // src/loop.c:731-780
@@ -1624,3 +1629,193 @@ void mp3mi_launch_hold_release(unsigned *flag, unsigned ticket, hipStream_t st)
 }
 
 ULP_CENSUS_ACCESSOR(mp3mi_debug_ulp_census_loop)
+
+#else // MP3MI_LOOP_PASS_ONLY
+// ---- self-test hook: one quantise+count pass of k_loop on given granules (include/mp3mi.h, mp3mi_debug_quantize_count) ----
+// A wavefront per granule runs what a pass of loop_stream runs, with these functions, in this order: loop_power34, a rescale
+// plan, loop_all_zero, loop_quantize (first tier and rare tier as in the product) and loop_count_bits.  The two rescale blocks
+// below restate loop_stream's pre-emphasis and amplification statements with every band marked (they are written inline there,
+// and moving them into functions would have to leave k_loop's instruction stream as it is; this copy keeps it untouched).
+// Compiled only in k_loop_qc.hip's translation unit: nothing here is reached by k_loop.
+struct loop_qc_gran { int32_t q, block_type, n_amp, pre; };
+__global__ void __launch_bounds__(64) k_debug_quantize_count(const mp3mi_tables *__restrict__ T, const double *__restrict__ xr_in,
+                                                             const loop_qc_gran *__restrict__ gin, int16_t *__restrict__ ix_out,
+                                                             double *__restrict__ xr_out, int32_t *__restrict__ f_out)
+{
+    __shared__ loop_lds L;
+    __shared__ uint16_t GL[928];
+    for (int i = (int) threadIdx.x; i < 928; i += 64) GL[i] = T->glut[i];
+    __syncthreads();
+    const size_t gi = blockIdx.x;
+    const int lane = wave_lane();
+    const loop_qc_gran in = gin[gi];
+    loop_regs R;
+    loop_desc_init(T, lane, &R.desc_a, &R.desc_b);
+    L.ix[576 + lane] = 0; L.ix[640 + lane] = 0; // (the padding, as loop_stream sets it)
+    if (lane < 2) L.xr[576 + lane] = 0.0;
+    loop_gr g = {};
+    g.block_type = in.block_type;
+    g.wsf = g.block_type != 0;
+    const bool shortb = g.wsf && g.block_type == 2;
+    g.sfb_lmax = shortb ? 0 : 21;
+    g.sfb_smax = shortb ? 0 : 12;
+    g.q = in.q;
+    const int nband = shortb ? 36 : 21;
+    float y34[LOOP_NV], y34max;
+    {
+        double xr[LOOP_NV];
+#pragma unroll
+        for (int k = 0; k < LOOP_SLOTS; k++) {
+            const int pr = loop_pair_of(lane, k);
+            const bool there = k < 4 || pr < 288;
+            xr[2 * k] = there ? xr_in[gi * 576 + 2 * pr] : 0.0;
+            xr[2 * k + 1] = there ? xr_in[gi * 576 + 2 * pr + 1] : 0.0;
+        }
+        y34max = loop_power34(xr, y34);
+#pragma unroll
+        for (int k = 0; k < LOOP_SLOTS; k++) {
+            const int pr = loop_pair_of(lane, k);
+            if (k < 4 || pr < 288) { L.xr[2 * pr] = xr[2 * k]; L.xr[2 * pr + 1] = xr[2 * k + 1]; }
+        }
+    }
+    wave_sync();
+    const unsigned long long bandpack = T->lane_bands[shortb][lane];
+    if (in.pre && !shortb) { // preemphasis with every one of sfb 17..20 violating (loop_stream)
+#pragma unroll
+        for (int k = 0; k < LOOP_SLOTS; k++) {
+            const int b = (int) (((unsigned) bandpack >> (6 * k)) & 63u);
+            const int line = 2 * loop_pair_of(lane, k);
+            if (b < g.sfb_lmax) {
+                const double f = T->pretab_xr[LOOP_PRETAB[b]];
+                L.xr[line] = L.xr[line] * f;
+                L.xr[line + 1] = L.xr[line + 1] * f;
+                y34[2 * k] = loop_rescale34(y34[2 * k], LOOP_PRETAB[b]);
+                y34[2 * k + 1] = loop_rescale34(y34[2 * k + 1], LOOP_PRETAB[b]);
+            }
+        }
+        y34max = y34max * LOOP_Y34MAX_GROW;
+    }
+    wave_sync();
+    const double ifqstep = T->sqrt2;
+    const unsigned long long ampmask = (1ull << nband) - 1ull; // amp_scalefac_bands with every band amplified (loop_stream)
+    for (int a = 0; a < in.n_amp; a++) {
+        if (!shortb) {
+            const unsigned amp32 = (unsigned) ampmask;
+#pragma unroll
+            for (int k = 0; k < LOOP_SLOTS; k++) {
+                const unsigned b = ((unsigned) bandpack >> (6 * k)) & 63u;
+                const int line = 2 * loop_pair_of(lane, k);
+                if (b < 32u && ((amp32 >> b) & 1u)) {
+                    L.xr[line] = L.xr[line] * ifqstep;
+                    L.xr[line + 1] = L.xr[line + 1] * ifqstep;
+                    y34[2 * k] = y34[2 * k] * 1.2968395546510096f;
+                    y34[2 * k + 1] = y34[2 * k + 1] * 1.2968395546510096f;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < LOOP_NV; j++) {
+                const unsigned b = (unsigned) ((bandpack >> (6 * j)) & 63ull);
+                const bool f = ((ampmask >> b) & 1ull) != 0;
+                const int line = 2 * loop_pair_of(lane, j >> 1) + (j & 1);
+                if (f) {
+                    L.xr[line] = L.xr[line] * ifqstep;
+                    y34[j] = y34[j] * 1.2968395546510096f;
+                }
+            }
+        }
+        y34max = y34max * LOOP_Y34MAX_AMP;
+        wave_sync();
+    }
+    // diagnostics, from the same estimates the quantiser forms (never part of the result)
+    const bool az = loop_all_zero(y34max, g.q);
+    const loop_qscale qs = loop_quant_scale(g.q);
+    unsigned differ = 0u;
+    int n_differ = 0;
+#pragma unroll
+    for (int k = 0; k < LOOP_SLOTS; k++) {
+        const unsigned hi = loop_quant_pair(y34[2 * k], y34[2 * k + 1], qs.a_hi, (float) LOOP_Q_CHI);
+        const unsigned lo = loop_quant_pair(y34[2 * k], y34[2 * k + 1], qs.a_lo, (float) LOOP_Q_CLO);
+        differ |= hi ^ lo;
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            unsigned a = (hi >> (16 * h)) & 0xffffu, b = (lo >> (16 * h)) & 0xffffu;
+            a = a < 2047u ? a : 2047u;
+            b = b < 2047u ? b : 2047u;
+            n_differ += (a != b && 2 * loop_pair_of(lane, k) + h < 576) ? 1 : 0;
+        }
+    }
+    const bool over = !(loop_estimate(y34max, qs.a_hi * 65535.0f) < 2047.0f);
+    const bool rare = !az && (over || wave_any(differ != 0u));
+    n_differ = wave_sum_i32(n_differ);
+    // the pass
+    const loop_qinfo qi = loop_quantize(T, L, y34, y34max, g.q, az, false, shortb);
+    const int bits = loop_count_bits(T, R, L, GL, g, qi, az CBPROF_PASS);
+    wave_sync();
+    for (int i = lane; i < 576; i += 64) {
+        ix_out[gi * 576 + i] = L.ix[i];
+        xr_out[gi * 576 + i] = L.xr[i];
+    }
+    const int m1 = wave_max_i32(qi.m1), m2 = wave_max_i32(qi.m2);
+    if (lane == 0) {
+        int32_t *f = f_out + gi * MP3MI_QC_FIELDS;
+        f[MP3MI_QC_N_NZ] = qi.n_nz; f[MP3MI_QC_N_BIG] = qi.n_big; f[MP3MI_QC_M1] = m1; f[MP3MI_QC_M2] = m2;
+        f[MP3MI_QC_BITS] = bits; f[MP3MI_QC_BIG_VALUES] = g.big_values; f[MP3MI_QC_COUNT1] = g.count1;
+        f[MP3MI_QC_COUNT1TABLE_SELECT] = g.count1table_select;
+        f[MP3MI_QC_TABLE_SELECT0] = g.table_select[0]; f[MP3MI_QC_TABLE_SELECT1] = g.table_select[1]; f[MP3MI_QC_TABLE_SELECT2] = g.table_select[2];
+        f[MP3MI_QC_REGION0_COUNT] = g.region0_count; f[MP3MI_QC_REGION1_COUNT] = g.region1_count;
+        f[MP3MI_QC_ADDRESS1] = g.address1; f[MP3MI_QC_ADDRESS2] = g.address2; f[MP3MI_QC_ADDRESS3] = g.address3;
+        f[MP3MI_QC_ALL_ZERO] = az; f[MP3MI_QC_RARE_TIER] = rare; f[MP3MI_QC_N_DIFFER] = n_differ; f[MP3MI_QC_OVER] = !az && over;
+    }
+}
+
+extern "C" int mp3mi_debug_quantize_count(int rate_hz, int n_gran, const double *xr, const int32_t *gran, int16_t *ix,
+                                          double *xr_out, int32_t *fields)
+{
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return MP3MI_ERR_NO_DEVICE;
+    const int ri = rate_hz == 44100 ? 0 : (rate_hz == 48000 ? 1 : (rate_hz == 32000 ? 2 : -1));
+    if (ri < 0 || n_gran < 0 || (n_gran > 0 && (!xr || !gran || !ix || !xr_out || !fields))) return MP3MI_ERR_ARG;
+    for (int i = 0; i < n_gran; i++) {
+        const int32_t *p = gran + 4 * i;
+        if (p[0] < MP3MI_STEP_MIN || p[0] >= MP3MI_STEP_MIN + MP3MI_STEP_N || p[1] < 0 || p[1] > 3 || p[2] < 0 || p[2] > 16 ||
+            p[3] < 0 || p[3] > 1 || (p[3] && p[1] == 2))
+            return MP3MI_ERR_ARG;
+    }
+    if (n_gran == 0) return MP3MI_OK;
+    mp3mi_tables *Th = (mp3mi_tables *) malloc(sizeof(mp3mi_tables));
+    if (!Th) return MP3MI_ERR_NOMEM;
+    const int trc = mp3mi_build_tables(Th, ri);
+    if (trc != 0) {
+        free(Th);
+        return trc == -8 ? MP3MI_ERR_TABLES : MP3MI_ERR_ARG;
+    }
+    const size_t n = (size_t) n_gran;
+    mp3mi_tables *dT = NULL;
+    double *dxr = NULL, *dxo = NULL;
+    loop_qc_gran *dg = NULL;
+    int16_t *dix = NULL;
+    int32_t *df = NULL;
+    int rc = MP3MI_ERR_HIP;
+    if (hipMalloc((void **) &dT, sizeof(mp3mi_tables)) == hipSuccess && hipMalloc((void **) &dxr, n * 576 * 8) == hipSuccess &&
+        hipMalloc((void **) &dxo, n * 576 * 8) == hipSuccess && hipMalloc((void **) &dg, n * sizeof(loop_qc_gran)) == hipSuccess &&
+        hipMalloc((void **) &dix, n * 576 * 2) == hipSuccess && hipMalloc((void **) &df, n * MP3MI_QC_FIELDS * 4) == hipSuccess &&
+        hipMemcpy(dT, Th, sizeof(mp3mi_tables), hipMemcpyHostToDevice) == hipSuccess &&
+        hipMemcpy(dxr, xr, n * 576 * 8, hipMemcpyHostToDevice) == hipSuccess &&
+        hipMemcpy(dg, gran, n * sizeof(loop_qc_gran), hipMemcpyHostToDevice) == hipSuccess) {
+        hipLaunchKernelGGL(k_debug_quantize_count, dim3((unsigned) n), dim3(64), 0, 0, dT, dxr, dg, dix, dxo, df);
+        if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(ix, dix, n * 576 * 2, hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(xr_out, dxo, n * 576 * 8, hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(fields, df, n * MP3MI_QC_FIELDS * 4, hipMemcpyDeviceToHost) == hipSuccess)
+            rc = MP3MI_OK;
+    }
+    if (dT) hipFree(dT);
+    if (dxr) hipFree(dxr);
+    if (dxo) hipFree(dxo);
+    if (dg) hipFree(dg);
+    if (dix) hipFree(dix);
+    if (df) hipFree(df);
+    free(Th);
+    return rc;
+}
+#endif // MP3MI_LOOP_PASS_ONLY

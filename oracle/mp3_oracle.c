@@ -1674,6 +1674,46 @@ static void format_frame(mp3o_stream *s, double xr[2][2][576])
 /* ------------------------------------------------------------------------- */
 /* public interface                                                          */
 /* ------------------------------------------------------------------------- */
+/* Test entry (tests/test_quant_edges.py): one quantise + count_bits on granules given as xr, through the functions above as the
+ * iteration loop calls them.  The rescale plan is the loop's own: preemphasis() and then n_amp times amp_scalefac_bands(), with
+ * every band's noise above its allowed distortion (granule 0, channel 0: no scfsi). */
+int mp3o_quantize_count(int rate_hz, int n_gran, const double *xr_in, const int32_t *gran, int32_t *ix_out, double *xr_out,
+                        int32_t *fields)
+{
+    mp3o_stream *s = mp3o_open(rate_hz, 128, 1);
+    int i, k, a;
+    if (!s) return -1;
+    for (i = 0; i < n_gran; i++) {
+        const int32_t *p = gran + 4 * i;
+        gr_info_t *g = &s->side.gr[0][0];
+        double *xr = xr_out + (size_t) i * 576, xfsf[4][21];
+        int ix[576], bits;
+        int32_t *f = fields + (size_t) i * MP3O_QC_FIELDS;
+        xmin_t xm;
+        if (p[1] < 0 || p[1] > 3 || p[2] < 0 || p[2] > 16 || p[3] < 0 || p[3] > 1 || (p[3] && p[1] == 2)) { mp3o_close(s); return -1; }
+        memset(g, 0, sizeof(*g));
+        g->block_type = (unsigned) p[1];
+        g->window_switching_flag = p[1] != 0;
+        g->quantizerStepSize = (double) p[0];
+        gr_deco(g);
+        memcpy(xr, xr_in + (size_t) i * 576, 576 * sizeof(double));
+        for (k = 0; k < 4; k++)
+            for (a = 0; a < 21; a++) xfsf[k][a] = 1.0;
+        memset(&xm, 0, sizeof(xm));
+        if (p[3]) preemphasis(s, xr, xfsf, &xm, 0, 0);
+        for (a = 0; a < p[2]; a++) amp_scalefac_bands(s, xr, xfsf, &xm, 0, 0, 1);
+        quantize(s, xr, ix, g);
+        bits = count_bits(s, ix, g);
+        for (k = 0; k < 576; k++) ix_out[(size_t) i * 576 + k] = ix[k];
+        f[0] = bits; f[1] = (int32_t) g->big_values; f[2] = (int32_t) g->count1; f[3] = (int32_t) g->count1table_select;
+        f[4] = (int32_t) g->table_select[0]; f[5] = (int32_t) g->table_select[1]; f[6] = (int32_t) g->table_select[2];
+        f[7] = (int32_t) g->region0_count; f[8] = (int32_t) g->region1_count;
+        f[9] = (int32_t) g->address1; f[10] = (int32_t) g->address2; f[11] = (int32_t) g->address3;
+    }
+    mp3o_close(s);
+    return 0;
+}
+
 mp3o_stream *mp3o_open(int rate_hz, int kbps, int channels)
 {
     static const double s_freq[3] = {44.1, 48, 32}; /* src/common.c:113 */
