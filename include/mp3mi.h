@@ -147,13 +147,45 @@ int mp3mi_batch_stream_status(mp3mi_batch *b, int32_t *status_host);
  *   mp3mi_batch_flush        III_FlushBitstream + close_bit_stream_w (musicin.c:802-805): delivers what is left and
  *                            ends the streams.  out_stride >= 2049 here.
  *   mp3mi_batch_reset        abandons the current streams: fresh encoder state.
- * mp3mi_batch_encode (above) is the same encoder run over a whole stream in one call.  Ragged batches and
- * streaming do not combine: a stream's last partial frame is zero-filled by the caller (src/encode.c:162-166).
- * out_stride >= mp3mi_batch_out_stride(b, n_frames). */
+ * mp3mi_batch_encode (above) is the same encoder run over a whole stream in one call.  With these three calls all
+ * streams of the batch begin and end together; mp3mi_batch_encode_slots (below) lets them begin and end in different
+ * calls, and end on a partial frame.  out_stride >= mp3mi_batch_out_stride(b, n_frames). */
 int mp3mi_batch_encode_next(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, uint8_t *out_dev,
                             size_t out_stride, uint32_t *out_len_dev);
 int mp3mi_batch_flush(mp3mi_batch *b, uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev);
 int mp3mi_batch_reset(mp3mi_batch *b);
+
+/* Continuous batching: every stream index of a batch is a SLOT through which one stream after another passes, each
+ * beginning and ending in a call of its own while the other slots go on encoding.
+ *   mp3mi_batch_encode_slots  one streaming call (pcm_dev [n_streams][n_frames*1152][channels], as for encode_next) with
+ *                             per-slot control in two HOST arrays, which the library copies before it returns:
+ *     ctl_host[s]             MP3MI_SLOT_START: slot s begins a new stream with this call's first sample, from fresh state (a
+ *                             stream still open there is abandoned, as by mp3mi_batch_reset: its pending bytes are not
+ *                             delivered).  MP3MI_SLOT_END: this call holds the stream's last samples; the call also flushes
+ *                             and closes it (src/formatBitstream.c:87-120, src/common.c:843-868) and the slot is closed
+ *                             afterwards.  START | END: a one-call file.  0: an open stream goes on, a closed slot stays closed.
+ *     n_samples_host[s]       valid samples per channel of slot s in the call: n_frames*1152 for an open or starting stream
+ *                             that does not end, 0 .. n_frames*1152 for one that ends (the last partial frame is zero-filled,
+ *                             src/encode.c:162-166), 0 for a closed slot.  NULL: n_frames*1152 for every open or starting
+ *                             slot, 0 for the others.
+ *                             out_len_dev[s] receives the bytes of slot s's file that became final with the call, in file
+ *                             order (0 for a closed slot): the outputs of the START call through the END call, concatenated,
+ *                             are the stream's file -- the bytes mp3mi_batch_encode_ragged gives for its samples.  Any broken
+ *                             rule (unknown ctl bits, END on a closed slot, a wrong sample count, a NULL pointer other than
+ *                             n_samples_host, n_frames outside 1..max_frames, out_stride < mp3mi_batch_out_stride(b, n_frames))
+ *                             returns MP3MI_ERR_ARG before anything is enqueued, and the batch is unchanged.
+ *                             mp3mi_batch_stream_status reports per slot the status of the open stream, or of the stream
+ *                             that last ended there, until the slot's next START; an abort is reported by the next sync as for
+ *                             encode_next, and the final flush's one (MP3MI_STREAM_ABORT_FLUSH_SLOT) is found at an END.
+ *   mp3mi_batch_slot_frames   host-side only, no wait: frames_host[s] = frames encoded so far by the stream open in slot s,
+ *                             -1 if none is.  Returns the number of open slots.
+ * Alongside: encode_next starts every slot when none is open and otherwise continues the open ones (closed slots stay
+ * closed, out_len 0); flush ends every open slot (out_len 0 for the closed ones); after reset and after a whole-file,
+ * ragged or host-buffer call every slot is closed. */
+enum { MP3MI_SLOT_START = 1, MP3MI_SLOT_END = 2 };
+int mp3mi_batch_encode_slots(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, const uint8_t *ctl_host,
+                             const int32_t *n_samples_host, uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev);
+int mp3mi_batch_slot_frames(const mp3mi_batch *b, int64_t *frames_host);
 
 /* Ragged batch: stream s has n_samples_dev[s] valid samples per channel (0 <= n <= n_frames*1152) in
  * its row of pcm_dev (row pitch n_frames*1152*channels as above).  As the reference's get_audio /

@@ -96,6 +96,19 @@ struct mp3mi_batch {
     uint8_t *carry;          // [S][MP3MI_CARRY_BYTES]: file bytes formatted but not final yet
     int32_t *carry_len;      // [S]
     int debug, last_nf;
+    // per-slot streaming (mp3mi_batch_encode_slots): a stream index is a SLOT through which one stream after another passes.
+    // While slots_on is false the slots are as frames_done says (all open at frames_done when it is > 0, else all closed) and
+    // every call runs the whole-batch path above; a per-slot call sets slots_on, and the slots are as slot_frames_h says.
+    bool slots_on;
+    std::vector<int64_t> slot_frames_h; // frames encoded by the stream open in each slot, -1: no stream open there
+    // the control block of a per-slot call -- fabs_s int64[S] | n_samples int32[S] | START list int32[S] | ctl uint8[S] -- in
+    // pinned staging and on the device, twice (by the parity of the per-slot call: ctl_calls & 1); ev_ctl[p] is recorded behind the
+    // last reader of copy p, and the host waits for it before it writes staging p again (the per-slot call two before)
+    uint8_t *ctl_stage[2], *ctl_dev[2];
+    size_t ctl_bytes;
+    hipEvent_t ev_ctl[2], ev_ctl_up;
+    bool ctl_used[2];
+    unsigned ctl_calls;
     // Host-buffer calls (mp3mi_batch_encode_host_async): the call's PCM goes up and its file bytes come down chunk by
     // chunk on two copy streams of their own, beside the kernels; two calls may be in flight, so the device copies of
     // PCM and output exist twice (slot = call number & 1).  Created with the first such call.
@@ -360,11 +373,27 @@ static int batch_build(mp3mi_batch *b, int n_streams, int rate_hz, int channels,
     CHK(hipMalloc((void **) &b->out_base, sizeof(int64_t) * (size_t) n_streams));
     CHK(hipMalloc((void **) &b->carry, (size_t) MP3MI_CARRY_BYTES * (size_t) n_streams));
     CHK(hipMalloc((void **) &b->carry_len, sizeof(int32_t) * (size_t) n_streams));
+    // (zero state from the start: a per-slot call runs every slot's stream through the kernels, the closed ones on silence, and a
+    // slot that never had a stream must hold a valid -- fresh -- encoder state for that)
+    CHK(hipMemset(b->psy_state, 0, mp3mi_psy_state_size() * (size_t) n_streams * channels));
+    CHK(hipMemset(b->loop_state, 0, mp3mi_loop_state_size() * (size_t) n_streams));
+    CHK(hipMemset(b->pcm_hist, 0, sizeof(int16_t) * MP3MI_PCM_HIST * (size_t) channels * (size_t) n_streams));
     CHK(hipMemset(b->out_base, 0, sizeof(int64_t) * (size_t) n_streams)); // a flush before the first encode delivers nothing
     CHK(hipMemset(b->carry_len, 0, sizeof(int32_t) * (size_t) n_streams));
     b->frames_done = 0;
     b->fresh = false;
     b->sb_dbg = NULL;
+    b->slots_on = false;
+    b->slot_frames_h.assign((size_t) n_streams, -1);
+    b->ctl_bytes = ((size_t) n_streams * 17 + 255) & ~(size_t) 255;
+    for (int i = 0; i < 2; i++) {
+        CHK(hipHostMalloc((void **) &b->ctl_stage[i], b->ctl_bytes, 0));
+        CHK(hipMalloc((void **) &b->ctl_dev[i], b->ctl_bytes));
+        CHK(hipEventCreateWithFlags(&b->ev_ctl[i], hipEventDisableTiming));
+        b->ctl_used[i] = false;
+    }
+    CHK(hipEventCreateWithFlags(&b->ev_ctl_up, hipEventDisableTiming));
+    b->ctl_calls = 0;
     for (int i = 0; i < 2; i++) {
         CHK(hipEventCreate(&b->ts[i].ev0));
         CHK(hipEventCreate(&b->ts[i].ev1));
@@ -435,12 +464,15 @@ extern "C" void mp3mi_batch_destroy(mp3mi_batch *b)
     if (b->lstream) hipStreamSynchronize(b->lstream);
     void *bufs[] = {b->T, b->bits_per_frame, b->bitrate_index, b->energy_l, b->energy_s, b->hist6, b->fft_bins, b->cw_mid, b->cw_fix,
                     b->part_eb, b->part_cb, b->xr[0], b->xr[1], b->psy[0], b->psy[1], b->prep[0], b->prep[1], b->prep_fix, b->sbs, b->ix, b->side,
-                    b->psy_state, b->loop_state, b->pcm_hist, b->out_base, b->carry, b->carry_len, b->gate_count, b->place_order, b->place_cost, b->place_zero, b->sb_dbg, b->voided, b->status_dev};
+                    b->psy_state, b->loop_state, b->pcm_hist, b->out_base, b->carry, b->carry_len, b->gate_count, b->place_order, b->place_cost, b->place_zero, b->sb_dbg, b->voided, b->status_dev,
+                    b->ctl_dev[0], b->ctl_dev[1]};
     for (void *p : bufs)
         if (p) hipFree(p);
     for (hipEvent_t e : b->ev_front) if (e) hipEventDestroy(e);
     for (hipEvent_t e : b->ev_loop) if (e) hipEventDestroy(e);
-    hipEvent_t evs[] = {b->ts[0].ev0, b->ts[0].ev1, b->ts[1].ev0, b->ts[1].ev1, b->ev_done, b->ev_hist};
+    for (int i = 0; i < 2; i++)
+        if (b->ctl_stage[i]) hipHostFree(b->ctl_stage[i]);
+    hipEvent_t evs[] = {b->ts[0].ev0, b->ts[0].ev1, b->ts[1].ev0, b->ts[1].ev1, b->ev_done, b->ev_hist, b->ev_ctl[0], b->ev_ctl[1], b->ev_ctl_up};
     for (hipEvent_t e : evs)
         if (e) hipEventDestroy(e);
     for (int k = 0; k < 2; k++)
@@ -516,8 +548,17 @@ struct host_call { // a call on host buffers (mp3mi_batch_encode_host_async): wh
     uint32_t *out_len;
     int slot;
 };
+struct slot_call { // a per-slot call (mp3mi_batch_encode_slots): its control block on the device (mp3mi_batch::ctl_dev)
+    const int64_t *fabs;  // [S] index of the call's first frame in the stream of each slot
+    const int32_t *ns;    // [S] valid samples per channel of each slot in the call
+    const int32_t *list;  // [n_start] the slots that START
+    const uint8_t *ctl;   // [S] MP3MI_SLOT_DEV_* bits
+    int n_start;
+    bool any_continue;    // a stream that earlier calls began goes on in the call: its carried bytes lead its row
+    int par;              // which copy of the control block
+};
 static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_samples_dev, int n_frames, uint8_t *out_dev,
-                       size_t out_stride, uint32_t *out_len_dev, bool whole_file, const host_call *hc = NULL);
+                       size_t out_stride, uint32_t *out_len_dev, bool whole_file, const host_call *hc = NULL, const slot_call *sc = NULL);
 
 // reads a timing set out (waits for its call to finish)
 static int harvest_timing(mp3mi_batch *b, int k)
@@ -551,6 +592,7 @@ static int reset_impl(mp3mi_batch *b)
     CHK(hipMemsetAsync(b->carry_len, 0, sizeof(int32_t) * (size_t) S, b->stream));
     b->frames_done = 0;
     b->fresh = true;
+    b->slots_on = false;
     return MP3MI_OK;
 }
 
@@ -576,9 +618,127 @@ extern "C" int mp3mi_batch_encode_ragged(mp3mi_batch *b, const int16_t *pcm_dev,
     return encode_impl(b, pcm_dev, n_samples_dev, n_frames, out_dev, out_stride, out_len_dev, true);
 }
 
+// ---- per-slot streaming (mp3mi_batch_encode_slots) ----
+// What every slot holds before a call: the frames of the stream open in it, -1 for none (mp3mi_batch::slots_on)
+static void slot_frames_now(const mp3mi_batch *b, int64_t *f)
+{
+    for (int s = 0; s < b->n_streams; s++) f[s] = b->slots_on ? b->slot_frames_h[s] : (b->frames_done > 0 ? (int64_t) b->frames_done : -1);
+}
+
+// When every slot is open at the same frame, or none is, the per-slot bookkeeping hands over to the whole-batch one: the next
+// call then runs exactly as if there had never been a per-slot call (a batch whose streams all began together)
+static void slots_settle(mp3mi_batch *b)
+{
+    const int64_t f0 = b->slot_frames_h[0];
+    for (int s = 1; s < b->n_streams; s++)
+        if (b->slot_frames_h[s] != f0) return;
+    if (f0 > 0) {
+        b->slots_on = false;
+        b->frames_done = f0;
+    }
+}
+
+// Writes the staging copy of the control block this per-slot call takes (waits for the per-slot call two before, whose kernels
+// read the device copy of the same parity and whose upload read this staging)
+static int ctl_take(mp3mi_batch *b, int *par)
+{
+    const int p = (int) (b->ctl_calls & 1u);
+    if (b->ctl_used[p]) CHK(hipEventSynchronize(b->ev_ctl[p]));
+    *par = p;
+    return MP3MI_OK;
+}
+
+static int slots_impl(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, const uint8_t *ctl_host, const int32_t *n_samples_host,
+                      uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev)
+{
+    if (!b || !pcm_dev || !ctl_host || !out_dev || !out_len_dev || n_frames <= 0 || n_frames > b->max_frames) return MP3MI_ERR_ARG;
+    if (out_stride < (size_t) n_frames * (size_t) b->max_frame_bytes + 1 + MP3MI_CARRY_BYTES) return MP3MI_ERR_ARG;
+    const int S = b->n_streams;
+    const int32_t full = (int32_t) n_frames * 1152;
+    std::vector<int64_t> f((size_t) S);
+    slot_frames_now(b, f.data());
+    // every rule first: a call that breaks one leaves the batch as it was
+    for (int s = 0; s < S; s++) {
+        const int c = ctl_host[s];
+        if (c & ~(MP3MI_SLOT_START | MP3MI_SLOT_END)) return MP3MI_ERR_ARG;
+        const bool open = f[s] >= 0, start = c & MP3MI_SLOT_START, end = c & MP3MI_SLOT_END, part = open || start;
+        if (end && !part) return MP3MI_ERR_ARG;
+        const int32_t n = n_samples_host ? n_samples_host[s] : (part ? full : 0);
+        if (!part ? n != 0 : (!end ? n != full : (n < 0 || n > full))) return MP3MI_ERR_ARG;
+    }
+    ON_DEVICE(b);
+    slot_call sc;
+    if (ctl_take(b, &sc.par) != MP3MI_OK) return MP3MI_ERR_HIP;
+    uint8_t *blk = b->ctl_stage[sc.par];
+    int64_t *fabs = (int64_t *) blk;
+    int32_t *ns = (int32_t *) (blk + 8 * (size_t) S), *list = (int32_t *) (blk + 12 * (size_t) S);
+    uint8_t *ctl = blk + 16 * (size_t) S;
+    sc.n_start = 0;
+    sc.any_continue = false;
+    for (int s = 0; s < S; s++) {
+        const int c = ctl_host[s];
+        const bool open = f[s] >= 0, start = c & MP3MI_SLOT_START, part = open || start;
+        fabs[s] = (start || !open) ? 0 : f[s];
+        ns[s] = n_samples_host ? n_samples_host[s] : (part ? full : 0);
+        ctl[s] = (uint8_t) ((c & MP3MI_SLOT_START ? MP3MI_SLOT_DEV_START : 0) | (c & MP3MI_SLOT_END ? MP3MI_SLOT_DEV_END : 0) |
+                            (part ? MP3MI_SLOT_DEV_ACTIVE : 0));
+        if (start) list[sc.n_start++] = s;
+        else if (open) sc.any_continue = true;
+    }
+    const uint8_t *dev = b->ctl_dev[sc.par];
+    sc.fabs = (const int64_t *) dev;
+    sc.ns = (const int32_t *) (dev + 8 * (size_t) S);
+    sc.list = (const int32_t *) (dev + 12 * (size_t) S);
+    sc.ctl = dev + 16 * (size_t) S;
+    const int rc = encode_impl(b, pcm_dev, NULL, n_frames, out_dev, out_stride, out_len_dev, false, NULL, &sc);
+    if (rc != MP3MI_OK) return rc;
+    b->ctl_calls++;
+    for (int s = 0; s < S; s++) {
+        const int c = ctl_host[s];
+        if (c & MP3MI_SLOT_START) f[s] = 0;
+        if (c & MP3MI_SLOT_END) f[s] = -1;
+        else if (f[s] >= 0) f[s] += n_frames;
+    }
+    b->slot_frames_h.assign(f.begin(), f.end());
+    b->slots_on = true;
+    slots_settle(b);
+    return MP3MI_OK;
+}
+
+extern "C" int mp3mi_batch_encode_slots(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, const uint8_t *ctl_host,
+                                        const int32_t *n_samples_host, uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev)
+{
+    return slots_impl(b, pcm_dev, n_frames, ctl_host, n_samples_host, out_dev, out_stride, out_len_dev);
+}
+
+extern "C" int mp3mi_batch_slot_frames(const mp3mi_batch *b, int64_t *frames_host)
+{
+    if (!b || !frames_host) return MP3MI_ERR_ARG;
+    slot_frames_now(b, frames_host);
+    int n = 0;
+    for (int s = 0; s < b->n_streams; s++) n += frames_host[s] >= 0;
+    return n;
+}
+
 extern "C" int mp3mi_batch_encode_next(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, uint8_t *out_dev,
                                        size_t out_stride, uint32_t *out_len_dev)
 {
+    if (b && b->slots_on) {
+        // per-slot bookkeeping in force: with no stream open every slot starts (the whole-batch start: state cleared for all);
+        // otherwise the open streams go on and the other slots stay closed
+        bool any = false;
+        for (int s = 0; s < b->n_streams && !any; s++) any = b->slot_frames_h[s] >= 0;
+        if (any) {
+            std::vector<uint8_t> ctl((size_t) b->n_streams, 0);
+            return slots_impl(b, pcm_dev, n_frames, ctl.data(), NULL, out_dev, out_stride, out_len_dev);
+        }
+        if (!pcm_dev || !out_dev || !out_len_dev || n_frames <= 0 || n_frames > b->max_frames ||
+            out_stride < (size_t) n_frames * (size_t) b->max_frame_bytes + 1 + MP3MI_CARRY_BYTES)
+            return MP3MI_ERR_ARG; // (before the bookkeeping changes)
+        b->slots_on = false;
+        b->frames_done = 0;
+        b->fresh = false;
+    }
     return encode_impl(b, pcm_dev, NULL, n_frames, out_dev, out_stride, out_len_dev, false);
 }
 
@@ -587,6 +747,40 @@ extern "C" int mp3mi_batch_flush(mp3mi_batch *b, uint8_t *out_dev, size_t out_st
     if (!b || !out_dev || !out_len_dev || out_stride < (size_t) MP3MI_CARRY_BYTES + 1) return MP3MI_ERR_ARG;
     ON_DEVICE(b);
     hold_release(b);
+    if (b->slots_on) { // some slots open, not all at the same frame (slots_settle), or none: end the open ones
+        const int S = b->n_streams;
+        int par = 0, n_open = 0;
+        for (int s = 0; s < S; s++) n_open += b->slot_frames_h[s] >= 0;
+        if (n_open == 0) { // nothing to end; the ended streams' status stays in their slots
+            CHK(hipMemsetAsync(out_len_dev, 0, sizeof(uint32_t) * (size_t) S, b->lstream));
+            return MP3MI_OK;
+        }
+        if (ctl_take(b, &par) != MP3MI_OK) return MP3MI_ERR_HIP;
+        uint8_t *blk = b->ctl_stage[par];
+        memset(blk, 0, b->ctl_bytes);
+        for (int s = 0; s < S; s++) {
+            const bool open = b->slot_frames_h[s] >= 0;
+            ((int64_t *) blk)[s] = open ? b->slot_frames_h[s] : 0;
+            blk[16 * (size_t) S + s] = open ? MP3MI_SLOT_DEV_ACTIVE : 0;
+        }
+        CHK(hipMemcpyAsync(b->ctl_dev[par], blk, b->ctl_bytes, hipMemcpyHostToDevice, b->lstream));
+        mp3mi_geom g = mp3mi_make_geom(S, b->channels, b->rate_idx, 0, 0, 0);
+        g.crc = b->crc;
+        g.fabs_s = (const int64_t *) b->ctl_dev[par];
+        g.slot_ctl = b->ctl_dev[par] + 16 * (size_t) S;
+        mp3mi_launch_stream_tail(g, 1, (int32_t *) b->loop_state, (int) (mp3mi_loop_state_size() / 4), b->bits_per_frame, out_dev, out_stride,
+                                 b->out_base, b->carry, b->carry_len, out_len_dev, b->voided, b->lstream);
+        CHK(hipGetLastError());
+        mp3mi_launch_status_gather(S, (const int32_t *) b->loop_state, (int) (mp3mi_loop_state_size() / 4), b->status_dev, b->lstream);
+        CHK(hipGetLastError());
+        CHK(hipEventRecord(b->ev_ctl[par], b->lstream));
+        b->ctl_used[par] = true;
+        b->ctl_calls++;
+        b->status_kept = true;
+        CHK(hipEventRecord(b->ev_done, b->lstream));
+        b->have_done = true;
+        return reset_impl(b);
+    }
     if (b->fresh) { // nothing was encoded since the reset: no file body (the reference would write one byte; see mp3mi.h)
         CHK(hipMemsetAsync(out_len_dev, 0, sizeof(uint32_t) * (size_t) b->n_streams, b->lstream));
         return MP3MI_OK;
@@ -608,7 +802,7 @@ extern "C" int mp3mi_batch_flush(mp3mi_batch *b, uint8_t *out_dev, size_t out_st
 }
 
 static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_samples_dev, int n_frames, uint8_t *out_dev,
-                       size_t out_stride, uint32_t *out_len_dev, bool whole_file, const host_call *hc)
+                       size_t out_stride, uint32_t *out_len_dev, bool whole_file, const host_call *hc, const slot_call *sc)
 {
     if (!b || !pcm_dev || !out_dev || !out_len_dev || n_frames <= 0 || n_frames > b->max_frames) return MP3MI_ERR_ARG;
     if (out_stride < (size_t) n_frames * (size_t) b->max_frame_bytes + 1 + (whole_file ? 0 : MP3MI_CARRY_BYTES)) return MP3MI_ERR_ARG;
@@ -627,7 +821,7 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
     // wavefronts, serial, nothing beside them -- runs out: back-to-back calls lose no pipeline fill.
     // a whole-file call starts every stream afresh; a streaming call continues (the first one after create / reset /
     // flush / a whole-file call starts afresh too)
-    if (whole_file || (b->frames_done == 0 && !b->fresh)) {
+    if (whole_file || (!sc && b->frames_done == 0 && !b->fresh)) {
         CHK(hipMemsetAsync(b->psy_state, 0, mp3mi_psy_state_size() * (size_t) S * C, b->stream));
         CHK(hipMemsetAsync(b->pcm_hist, 0, sizeof(int16_t) * MP3MI_PCM_HIST * (size_t) C * (size_t) S, b->stream));
         CHK(hipMemsetAsync(b->loop_state, 0, mp3mi_loop_state_size() * (size_t) S, b->lstream));
@@ -635,13 +829,36 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         CHK(hipMemsetAsync(b->carry_len, 0, sizeof(int32_t) * (size_t) S, b->lstream));
         b->frames_done = 0;
     }
-    const long fabs0 = b->frames_done;
+    // (a per-slot call: every slot has its own frame index, in the control block; k_loop counts the frame of a status from the
+    // call's first, and k_stream_tail places it in the stream)
+    const long fabs0 = sc ? 0 : b->frames_done;
+    if (sc) n_samples_dev = sc->ns;
+    const bool kept = b->status_kept;
     b->fresh = false;
     b->status_kept = false;
     if (b->place_cost) CHK(hipMemsetAsync(b->place_cost, 0, sizeof(int) * (size_t) S, b->lstream)); // first chunk: order = identity
     if (hc && b->hio.out_used[hc->slot]) CHK(hipStreamWaitEvent(b->lstream, b->hio.out_free[hc->slot], 0)); // the call two before this one copied out of it
     CHK(hipMemsetAsync(out_dev, 0, out_stride * (size_t) S, b->lstream)); // (behind the formatter of the call before: it may be the same buffer)
-    if (!whole_file && fabs0 > 0) { // the bytes earlier calls formatted but could not deliver lead the rows
+    if (sc) {
+        // the control block goes up on the front stream, ahead of everything of the call that reads it; the START slots' state is
+        // cleared on the stream that owns it: psy state and PCM history before the call's first transform, the loop state, the
+        // file position and the carry length before carry_in and the call's first k_loop
+        CHK(hipMemcpyAsync(b->ctl_dev[sc->par], b->ctl_stage[sc->par], b->ctl_bytes, hipMemcpyHostToDevice, b->stream));
+        CHK(hipEventRecord(b->ev_ctl_up, b->stream));
+        const mp3mi_slot_region none = {NULL, 0};
+        mp3mi_launch_slot_begin(sc->list, sc->n_start, {b->psy_state, mp3mi_psy_state_size() * (size_t) C},
+                                {b->pcm_hist, sizeof(int16_t) * MP3MI_PCM_HIST * (size_t) C}, none, b->stream);
+        CHK(hipGetLastError());
+        CHK(hipStreamWaitEvent(b->lstream, b->ev_ctl_up, 0));
+        if (kept) { // the last flush ended every stream and reset the state: the ended streams' status stays until their slot STARTs
+            mp3mi_launch_status_scatter(S, (int32_t *) b->loop_state, (int) (mp3mi_loop_state_size() / 4), b->status_dev, b->lstream);
+            CHK(hipGetLastError());
+        }
+        mp3mi_launch_slot_begin(sc->list, sc->n_start, {b->loop_state, mp3mi_loop_state_size()}, {b->out_base, sizeof(int64_t)},
+                                {b->carry_len, sizeof(int32_t)}, b->lstream);
+        CHK(hipGetLastError());
+    }
+    if (!whole_file && (sc ? sc->any_continue : fabs0 > 0)) { // the bytes earlier calls formatted but could not deliver lead the rows
         mp3mi_launch_carry_in(S, b->carry, b->carry_len, out_dev, out_stride, b->lstream);
         CHK(hipGetLastError());
     }
@@ -694,6 +911,8 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         g.hdr_mode = b->hdr_mode;
         g.crc = b->crc;
         g.fabs0 = fabs0;
+        g.fabs_s = sc ? sc->fabs + v.s0 : NULL;
+        g.slot_ctl = sc ? sc->ctl + v.s0 : NULL;
         g.hist = b->pcm_hist + v.s0 * MP3MI_PCM_HIST * (size_t) C;
         g.out_base = whole_file ? NULL : b->out_base + v.s0;
         g.whole_file = whole_file ? 1 : 0;
@@ -886,6 +1105,8 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         g.hdr_mode = b->hdr_mode;
         g.crc = b->crc;
         g.fabs0 = fabs0;
+        g.fabs_s = sc ? sc->fabs : NULL;
+        g.slot_ctl = sc ? sc->ctl : NULL;
         g.hist = b->pcm_hist;
         g.out_base = whole_file ? NULL : b->out_base;
         g.whole_file = whole_file ? 1 : 0;
@@ -909,8 +1130,13 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         b->hio.pcm_used[hc->slot] = true;
         b->hio.pending[hc->slot] = true;
     }
+    if (sc) { // (lstream has joined the front stream: every reader of this copy of the control block is ahead of this)
+        CHK(hipEventRecord(b->ev_ctl[sc->par], b->lstream));
+        b->ctl_used[sc->par] = true;
+    }
     b->slot_base = (b->slot_base + nchunks) & 1;
-    b->frames_done = whole_file ? 0 : fabs0 + n_frames; // a whole-file call leaves finished streams behind
+    b->frames_done = (whole_file || sc) ? 0 : fabs0 + n_frames; // a whole-file call leaves finished streams behind
+    if (whole_file) b->slots_on = false;
     CHK(hipEventRecord(ts.ev1, b->lstream));
     ts.pending = true;
     b->call_no++;

@@ -151,7 +151,9 @@ __global__ void __launch_bounds__(64, 3) k_filter(const mp3mi_tables *__restrict
         const double scale = ((sub & 1) && (q & 1)) ? -0x1p-15 : 0x1p-15;
         double *const out = sbs + ((size_t) s * G1 * C + ch) * 576 + sub;
         // granule slots below gi_first lie before the stream: the reference's zero-initialised l3_sb_sample
-        const int gi_first = (2 * geo.fabs0 + (long) geo.g0 - 1 < 0) ? (int) (1 - (long) geo.g0 - 2 * geo.fabs0) : 0;
+        // (per-slot streaming: the stream open in this slot has its own frame index)
+        const long f_first = geo.fabs_s ? (long) geo.fabs_s[s] : geo.fabs0;
+        const int gi_first = (2 * f_first + (long) geo.g0 - 1 < 0) ? (int) (1 - (long) geo.g0 - 2 * f_first) : 0;
         {
             int sgm = sg, gim = gi, qm = q;
             unsigned off = (unsigned) (gi * C * 576 + q * 32);

@@ -131,6 +131,16 @@ MP3MI_DEVFN bool fmt_flush_dies(long n_done, long m_end, int slot)
     return queued >= 1 && written * slot == m_end && ((queued * (long) slot * 8) % 32) == 0;
 }
 
+// Length of the file of a stream that ends after n_done frames with m_end bytes of main data written
+// (src/formatBitstream.c:87-120 + src/common.c:843-868, 968): the flush stops short of the last slot by what the current
+// slot still has free, and close writes the byte under construction as well.  No frames: no file body.
+MP3MI_DEVFN long fmt_file_end(long n_done, long m_end, int slot, int frame_bytes)
+{
+    if (n_done <= 0) return 0;
+    const long rem = ((m_end + slot - 1) / slot) * slot - m_end;
+    return n_done * frame_bytes - rem + 1;
+}
+
 #define FMT_KERNEL_ARGS const mp3mi_tables *__restrict__ T, mp3mi_geom geo, const int16_t *__restrict__ ix_all,                          \
                         const mp3mi_frame_side *__restrict__ side_all, const int32_t *__restrict__ bits_per_frame,                 \
                         const int32_t *__restrict__ bitrate_index, uint8_t *__restrict__ out, size_t out_stride,                   \
@@ -144,7 +154,7 @@ MP3MI_DEVFN void fmt_frame(fmt_lds &L, FMT_KERNEL_ARGS)
     const int C = geo.channels, G = geo.n_gran;
     const int fl = (int) blockIdx.x % geo.nf, s = (int) blockIdx.x / geo.nf;
     const long n_call = (long) geo.f0 + fl;     // frame index within this call
-    const long n_abs = geo.fabs0 + n_call;      // and within the stream: what places the frame in the file
+    const long n_abs = (geo.fabs_s ? (long) geo.fabs_s[s] : geo.fabs0) + n_call; // and within the stream: what places the frame in the file
     // ragged batch: this stream's frame count; frames beyond it were not encoded and emit nothing
     const long n_frames_s = geo.n_samples ? ((long) geo.n_samples[s] + 1151) / 1152 : (long) geo.n_frames;
     if (n_call >= n_frames_s) {
@@ -356,12 +366,9 @@ MP3MI_DEVFN void fmt_frame(fmt_lds &L, FMT_KERNEL_ARGS)
         dst[phys] = (uint8_t) (L.words[k >> 2] >> (24 - 8 * (k & 3)));
     }
     if (geo.whole_file && n_call == n_frames_s - 1 && lane == 0) {
-        // file length (src/formatBitstream.c:87-120 + src/common.c:843-868, 968): the flush stops
-        // short of the last slot by what the current slot still has free, and close writes the
-        // byte under construction as well
+        // file length (fmt_file_end)
         const long mend = (long) n_abs * (long) slot - (long) mdb + nbytes; // once per stream
-        const long rem = ((mend + slot - 1) / slot) * slot - mend;
-        uint32_t len = (uint32_t) (n_frames_s * frame_bytes - rem + 1);
+        uint32_t len = (uint32_t) fmt_file_end(n_frames_s, mend, slot, frame_bytes);
         if (loop_state) {
             int32_t *st = &loop_state[(size_t) s * loop_state_words + (loop_state_words - 1)];
             if (*st == 0 && fmt_flush_dies(n_frames_s, mend, slot)) *st = MP3MI_DEV_STATUS(MP3MI_DEV_ABORT_FLUSH_SLOT, n_frames_s);
@@ -422,6 +429,9 @@ __global__ void __launch_bounds__(64) k_carry_in(const uint8_t *__restrict__ car
 // After the call's frames are formatted (flush = 0): how much of the row is final, what stays in the carry.
 // flush = 1 (III_FlushBitstream + close_bit_stream_w, src/formatBitstream.c:87-120, src/common.c:843-868, 968):
 // the carry goes out up to where the last main data ends, plus the byte under construction.
+// Per-slot calls (geo.slot_ctl, mp3mi_batch_encode_slots): a slot in which no stream is open delivers nothing and keeps its
+// state; a stream that ENDs with the call (flush = 0) has its carry and this call's frames in the row already, so only the
+// file's end is settled there -- where the whole-file call's last frame settles it (fmt_file_end).
 __global__ void __launch_bounds__(64) k_stream_tail(mp3mi_geom geo, int flush, int32_t *__restrict__ loop_state, int loop_state_words,
                                                     const int32_t *__restrict__ bits_per_frame, uint8_t *__restrict__ out, size_t out_stride,
                                                     int64_t *__restrict__ out_base, uint8_t *__restrict__ carry,
@@ -430,21 +440,34 @@ __global__ void __launch_bounds__(64) k_stream_tail(mp3mi_geom geo, int flush, i
 {
     const int s = (int) blockIdx.x, lane = (int) threadIdx.x;
     const int C = geo.channels;
+    const int ctl = geo.slot_ctl ? (int) geo.slot_ctl[s] : MP3MI_SLOT_DEV_ACTIVE;
+    if (!(ctl & MP3MI_SLOT_DEV_ACTIVE)) { // nothing open in the slot
+        if (lane == 0) out_len[s] = 0;
+        return;
+    }
+    int32_t *st = &loop_state[(size_t) s * loop_state_words + (loop_state_words - 1)];
+    const long f_first = geo.fabs_s ? (long) geo.fabs_s[s] : geo.fabs0;
+    if (geo.fabs_s && lane == 0 && *st != 0 && !(*st & MP3MI_DEV_ABORT_REPORTED)) {
+        // k_loop of a per-slot call counts the frame of its status from the call's first (its geo.fabs0 is 0): place it in the stream
+        const long fr = (long) ((*st >> 8) & MP3MI_DEV_STATUS_FRAME_MAX) + f_first;
+        *st = MP3MI_DEV_STATUS(*st & 255, fr);
+    }
+    const bool ends = !flush && (ctl & MP3MI_SLOT_DEV_END);
     const int frame_bytes = bits_per_frame[s] / 8, si_bytes = (32 + (geo.crc ? 16 : 0) + (C == 2 ? 256 : 136)) / 8, slot = frame_bytes - si_bytes;
-    const long n_done = geo.fabs0 + (flush ? 0 : geo.n_frames); // frames of the stream encoded so far
+    // frames of the stream encoded so far
+    const long n_done = f_first + (flush ? 0 : (ends ? ((long) geo.n_samples[s] + 1151) / 1152 : (long) geo.n_frames));
     const long resv_bytes = loop_state[(size_t) s * loop_state_words] / 8; // ResvSize / 8 = the next frame's main_data_begin
     const long m_end = n_done * slot - resv_bytes;                 // main data written so far
     const long base = out_base[s];
     uint8_t *row = out + (size_t) s * out_stride;
     uint8_t *cr = carry + (size_t) s * MP3MI_CARRY_BYTES;
-    if (!flush) {
+    if (!flush && !ends) {
         const long fin = fmt_final_upto(m_end, slot, frame_bytes, si_bytes), end = n_done * frame_bytes;
         const int keep = (int) (end - fin); // <= 511 bytes of open slots plus the headers in between
         for (int i = lane; i < keep && i < MP3MI_CARRY_BYTES; i += 64) cr[i] = row[fin - base + i];
         if (lane == 0) {
             // (a stream the reference died on delivers nothing more; mp3mi_batch_stream_status says why.  The sync after
             // the call in which it happened reports it -- once: MP3MI_DEV_ABORT_REPORTED marks the word)
-            int32_t *st = &loop_state[(size_t) s * loop_state_words + (loop_state_words - 1)];
             if (*st != 0 && !(*st & MP3MI_DEV_ABORT_REPORTED)) {
                 *st |= MP3MI_DEV_ABORT_REPORTED;
                 if (voided) atomicAdd(voided, 1u);
@@ -454,15 +477,11 @@ __global__ void __launch_bounds__(64) k_stream_tail(mp3mi_geom geo, int flush, i
             out_base[s] = fin;
         }
     } else {
-        long total = 0;
-        if (n_done > 0) {
-            const long rem = ((m_end + slot - 1) / slot) * slot - m_end;
-            total = n_done * frame_bytes - rem + 1;
-        }
+        const long total = fmt_file_end(n_done, m_end, slot, frame_bytes);
         const int n = (int) (total - base), have = carry_len[s];
-        for (int i = lane; i < n; i += 64) row[i] = i < have ? cr[i] : (uint8_t) 0;
+        if (flush)
+            for (int i = lane; i < n; i += 64) row[i] = i < have ? cr[i] : (uint8_t) 0;
         if (lane == 0) {
-            int32_t *st = &loop_state[(size_t) s * loop_state_words + (loop_state_words - 1)];
             if (*st == 0 && fmt_flush_dies(n_done, m_end, slot)) *st = MP3MI_DEV_STATUS(MP3MI_DEV_ABORT_FLUSH_SLOT, n_done);
             if (*st != 0 && !(*st & MP3MI_DEV_ABORT_REPORTED)) { // (an earlier call of the stream may have reported it already)
                 *st |= MP3MI_DEV_ABORT_REPORTED;
@@ -484,6 +503,43 @@ __global__ void __launch_bounds__(256) k_status_gather(int n_streams, const int3
 void mp3mi_launch_status_gather(int n_streams, const int32_t *loop_state, int loop_state_words, int32_t *status, hipStream_t st)
 {
     hipLaunchKernelGGL(k_status_gather, dim3((unsigned) ((n_streams + 255) / 256)), dim3(256), 0, st, n_streams, loop_state, loop_state_words, status);
+}
+
+__global__ void __launch_bounds__(256) k_status_scatter(int n_streams, int32_t *__restrict__ loop_state, int loop_state_words, const int32_t *__restrict__ status)
+{
+    const int s = (int) (blockIdx.x * 256 + threadIdx.x);
+    if (s < n_streams && status[s] != 0) loop_state[(size_t) s * loop_state_words + (loop_state_words - 1)] = status[s] | MP3MI_DEV_ABORT_REPORTED;
+}
+
+void mp3mi_launch_status_scatter(int n_streams, int32_t *loop_state, int loop_state_words, const int32_t *status, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_status_scatter, dim3((unsigned) ((n_streams + 255) / 256)), dim3(256), 0, st, n_streams, loop_state, loop_state_words, status);
+}
+
+// ---- per-slot streaming (mp3mi_batch_encode_slots) ----
+// Fresh state for the slots a call STARTs: what reset_impl gives every stream, for the listed slots only -- one workgroup per
+// listed slot zeroes that slot's record of each region with plain word stores.  batch.cpp launches it twice, once per HIP stream,
+// each time with the regions that stream owns (the psy state and the PCM history on the front stream; the loop state, the file
+// position and the carry length on the loop stream).
+__global__ void __launch_bounds__(256) k_slot_begin(const int32_t *__restrict__ list, mp3mi_slot_region r0, mp3mi_slot_region r1,
+                                                    mp3mi_slot_region r2)
+{
+    const size_t s = (size_t) list[blockIdx.x];
+    const mp3mi_slot_region r[3] = {r0, r1, r2};
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        if (!r[k].base) continue;
+        const size_t words = r[k].bytes / 4;
+        uint32_t *p = (uint32_t *) ((char *) r[k].base + s * r[k].bytes);
+        for (size_t i = threadIdx.x; i < words; i += 256) p[i] = 0u;
+    }
+}
+
+void mp3mi_launch_slot_begin(const int32_t *list, int n_list, mp3mi_slot_region r0, mp3mi_slot_region r1, mp3mi_slot_region r2,
+                             hipStream_t st)
+{
+    if (n_list <= 0) return;
+    hipLaunchKernelGGL(k_slot_begin, dim3((unsigned) n_list), dim3(256), 0, st, list, r0, r1, r2);
 }
 
 // the last MP3MI_PCM_HIST samples of the call (a frame has 1152 > MP3MI_PCM_HIST) are the next call's history

@@ -46,7 +46,15 @@ struct mp3mi_geom {
                            bit 2: k_psy takes dm_log / dm_exp only (MP3MI_PSY_EXACT=1, tests);
                            bit 3: k_loop's quantiser takes the exact table search only (MP3MI_QUANT_EXACT=1, tests);
                            bit 4: k_cw takes the correctly rounded sines and cosines for every record (MP3MI_CW_EXACT=1, tests) */
+    /* per-slot streaming (mp3mi_batch_encode_slots): streams of one batch begin and end in different calls */
+    const int64_t *fabs_s;   /* device, [n_streams]: index of the call's first frame in the stream open in each slot, or NULL: fabs0 for all */
+    const uint8_t *slot_ctl; /* device, [n_streams]: MP3MI_SLOT_* bits of the call, or NULL: every stream continues */
 };
+/* slot_ctl bits: the slot begins a stream with the call, ends it with the call, takes part in the call at all (a stream is open
+   in it or begins); k_stream_tail leaves a slot without MP3MI_SLOT_DEV_ACTIVE alone */
+#define MP3MI_SLOT_DEV_START 1
+#define MP3MI_SLOT_DEV_END 2
+#define MP3MI_SLOT_DEV_ACTIVE 4
 
 static inline mp3mi_geom mp3mi_make_geom(int n_streams, int channels, int rate_idx, int n_frames, int f0, int nf)
 {
@@ -60,6 +68,7 @@ static inline mp3mi_geom mp3mi_make_geom(int n_streams, int channels, int rate_i
     g.test_flags = 0;
     g.pcm_pitch = 0;
     g.n_samples = NULL;
+    g.fabs_s = NULL; g.slot_ctl = NULL;
 #if defined(MP3MI_ULP_CENSUS)
     g.census_cb_stride = 0;
 #endif
@@ -127,8 +136,15 @@ void mp3mi_launch_carry_in(int n_streams, const uint8_t *carry, const int32_t *c
 void mp3mi_launch_stream_tail(const mp3mi_geom &g, int flush, int32_t *loop_state, int loop_state_words, const int32_t *bits_per_frame,
                               uint8_t *out, size_t out_stride, int64_t *out_base, uint8_t *carry, int32_t *carry_len, uint32_t *out_len,
                               unsigned *voided, hipStream_t st);
+/* k_slot_begin: fresh state for the n_list slots of `list` (a call's MP3MI_SLOT_START slots): every region's record of each listed
+   slot is zeroed -- bytes per slot a multiple of 4; regions with a NULL base are skipped */
+struct mp3mi_slot_region { void *base; size_t bytes; };
+void mp3mi_launch_slot_begin(const int32_t *list, int n_list, mp3mi_slot_region r0, mp3mi_slot_region r1, mp3mi_slot_region r2,
+                             hipStream_t st);
 /* status[s] = the status word of stream s (a gather out of the strided state records) */
 void mp3mi_launch_status_gather(int n_streams, const int32_t *loop_state, int loop_state_words, int32_t *status, hipStream_t st);
+/* the reverse, for the streams a flush ended: their status words go back into the cleared state records, marked as reported */
+void mp3mi_launch_status_scatter(int n_streams, int32_t *loop_state, int loop_state_words, const int32_t *status, hipStream_t st);
 void mp3mi_launch_hist_save(const mp3mi_geom &g, const int16_t *pcm, int16_t *hist, hipStream_t st);
 /* loop_state / voided as for mp3mi_launch_stream_tail (a whole-file call ends the streams in k_format); NULL: no status */
 void mp3mi_launch_format(const mp3mi_tables *T, const mp3mi_geom &g, const int16_t *ix,
