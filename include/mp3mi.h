@@ -239,6 +239,32 @@ int mp3mi_batch_total_timing(mp3mi_batch *b, double *loop_kernel_ms, double *all
  * works, but the runtime stages it and the call blocks while it does.  bench.py --host-io measures this path. */
 int mp3mi_batch_encode_host_async(mp3mi_batch *b, const int16_t *pcm_host, int n_frames, uint8_t *out_host, size_t out_stride,
                                   uint32_t *out_len_host);
+/* Continuous batching on HOST buffers that hold a row per LIVE slot: mp3mi_batch_encode_slots with every array indexed by
+ * ROW instead of by slot, the PCM taken from and the bytes delivered to host memory, overlapped with the kernels like
+ * mp3mi_batch_encode_host_async (two calls in flight, the third blocks on the first; page-locked buffers overlap, pageable
+ * ones work and block).  Only the n_rows rows cross PCIe: a slot batch is sized for the peak, and closed slots cost no transfer.
+ *   row_slot_host[n_rows]   the slot of each row: strictly increasing, each in 0 .. n_streams-1.  NULL: n_rows == n_streams
+ *                           and row r is slot r.
+ *   ctl_host[r], n_samples_host[r] (may be NULL)   as for mp3mi_batch_encode_slots, for the slot of row r.
+ *   pcm_host [n_rows][n_frames*1152][channels]; out_host [n_rows][out_stride], out_stride >= mp3mi_batch_out_stride(b,
+ *   n_frames); out_len_host [n_rows]: per row the bytes of its stream's file that became final with the call (the rest of the
+ *   row is zero when a row map is given).
+ * A slot that no row names must be closed and stays closed.  An open slot without a row, a row whose slot is neither open nor
+ * starting, a slot index out of range or out of order, n_rows outside 1 .. n_streams, and every error
+ * mp3mi_batch_encode_slots refuses return MP3MI_ERR_ARG before anything is enqueued, and the batch is unchanged.  The three
+ * control arrays are copied before the call returns; pcm_host, out_host and out_len_host must stay valid until the call's
+ * results have been waited for (mp3mi_batch_host_wait, mp3mi_batch_sync).  Slots opened or closed here are the slots of
+ * mp3mi_batch_encode_slots, slot_frames, stream_status, encode_next, flush and reset: device and host calls may alternate.
+ * mp3mi_batch_host_io_stats counts these calls: h2d_bytes grows by n_rows * n_frames*1152 * channels * 2 per call.
+ *
+ * mp3mi_batch_host_wait(b, k) waits until the host-buffer call (this one or mp3mi_batch_encode_host_async) issued k calls
+ * ago -- 0: the latest, 1: the one before -- has delivered out_host / out_len_host, and for nothing later: a server issues
+ * tick t+1 and then collects tick t.  Returns MP3MI_OK, MP3MI_ERR_ARG (k not 0 or 1, or no such call) or MP3MI_ERR_HIP;
+ * reference aborts are reported by mp3mi_batch_sync and mp3mi_batch_stream_status as ever. */
+int mp3mi_batch_encode_slots_host_async(mp3mi_batch *b, const int16_t *pcm_host, int n_frames, int n_rows,
+                                        const int32_t *row_slot_host, const uint8_t *ctl_host, const int32_t *n_samples_host,
+                                        uint8_t *out_host, size_t out_stride, uint32_t *out_len_host);
+int mp3mi_batch_host_wait(mp3mi_batch *b, int calls_back);
 /* Bytes moved and time spent inside the copies (HIP events on the two copy streams) over all host-buffer calls since the
  * batch was created; waits for the calls issued so far. */
 typedef struct mp3mi_host_io_stats {

@@ -93,6 +93,9 @@ def lib():
         L.mp3mi_batch_encode_slots.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         L.mp3mi_batch_slot_frames.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        L.mp3mi_batch_encode_slots_host_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        L.mp3mi_batch_host_wait.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.mp3mi_batch_set_mode.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.mp3mi_batch_set_error_protection.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.mp3mi_batch_set_header.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]
@@ -214,6 +217,38 @@ class Batch:
         ns = None if n_samples is None else np.ascontiguousarray(n_samples, dtype=np.int32).reshape(S)
         self._check(self.L.mp3mi_batch_encode_slots(self.h, pcm.data_ptr(), n_frames, ctl.ctypes.data, None if ns is None else ns.ctypes.data,
                                                     out.data_ptr(), out.shape[1], out_len.data_ptr()), "mp3mi_batch_encode_slots")
+
+    def encode_slots_host(self, pcm, n_frames, out, out_len, rows=None, start=None, end=None, n_samples=None):
+        """Continuous batching on host buffers that hold a row per LIVE slot (mp3mi_batch_encode_slots_host_async): rows is the
+        strictly increasing sequence of the rows' slots (None: a row per slot), and start / end / n_samples are as for
+        encode_slots but indexed by ROW.  pcm int16 [n_rows, n_frames*1152*C], out uint8 [n_rows, stride], out_len int32 or
+        uint32 [n_rows]: CPU tensors (pinned ones overlap with the kernels) or numpy arrays, which must stay alive until the
+        call's results have been waited for (host_wait, sync).  Only the rows cross PCIe."""
+        import numpy as np
+
+        def ptr(a):
+            if isinstance(a, np.ndarray):
+                assert a.flags.c_contiguous
+                return a.ctypes.data
+            assert not a.is_cuda and a.is_contiguous()
+            return a.data_ptr()
+        R = self.n_streams if rows is None else len(rows)
+        assert pcm.shape[0] == R and out.shape[0] == R and out_len.shape[0] == R and pcm.dtype.itemsize == 2 and out_len.dtype.itemsize == 4
+        rows_a = None if rows is None else np.ascontiguousarray(rows, dtype=np.int32).reshape(R)
+        ctl = np.zeros(R, np.uint8)
+        if start is not None:
+            ctl |= np.asarray(start, dtype=bool).reshape(R).astype(np.uint8) * 1  # MP3MI_SLOT_START
+        if end is not None:
+            ctl |= np.asarray(end, dtype=bool).reshape(R).astype(np.uint8) * 2  # MP3MI_SLOT_END
+        ns = None if n_samples is None else np.ascontiguousarray(n_samples, dtype=np.int32).reshape(R)
+        self._check(self.L.mp3mi_batch_encode_slots_host_async(self.h, ptr(pcm), n_frames, R, None if rows_a is None else rows_a.ctypes.data,
+                                                               ctl.ctypes.data, None if ns is None else ns.ctypes.data, ptr(out), out.shape[1],
+                                                               ptr(out_len)), "mp3mi_batch_encode_slots_host_async")
+
+    def host_wait(self, calls_back=0):
+        """waits until the host-buffer call issued calls_back calls ago (0: the latest, 1: the one before) has delivered its
+        out / out_len, and for nothing later (mp3mi_batch_host_wait)"""
+        self._check(self.L.mp3mi_batch_host_wait(self.h, calls_back), "mp3mi_batch_host_wait")
 
     def slot_frames(self):
         """numpy int64 [n_streams]: frames encoded so far by the stream open in each slot, -1 where none is (no device wait)"""

@@ -105,7 +105,7 @@ struct mp3mi_batch {
     // pinned staging and on the device, twice (by the parity of the per-slot call: ctl_calls & 1); ev_ctl[p] is recorded behind the
     // last reader of copy p, and the host waits for it before it writes staging p again (the per-slot call two before)
     uint8_t *ctl_stage[2], *ctl_dev[2];
-    size_t ctl_bytes;
+    size_t ctl_bytes, ctl_rows_off; // (behind the four arrays, for host-buffer calls: row_slot int32[n_rows] at ctl_rows_off)
     hipEvent_t ev_ctl[2], ev_ctl_up;
     bool ctl_used[2];
     unsigned ctl_calls;
@@ -123,6 +123,15 @@ struct mp3mi_batch {
         bool pcm_used[2], out_used[2];
         std::vector<hipEvent_t> ev_fmt[2];   // per chunk: the chunk's formatter is done
         std::vector<hipEvent_t> t_up[2], t_dn[2]; // per chunk two events around the copy (the second is what consumers wait for)
+        // per-slot calls on host buffers with a row map (mp3mi_batch_encode_slots_host_async): the caller's rows are DENSE, one
+        // per live slot; they cross PCIe as they are, into and out of dense device buffers, and k_rows_in / k_rows_out
+        // (k_format.hip) move them to and from the rows per slot above.  Created with the first such call of a slot.
+        int16_t *pcm_rows[2];     // [n_rows][max_frames * 1152][C]
+        uint8_t *out_rows[2];     // [n_rows][the caller's out_stride]
+        size_t out_rows_cap[2];   // bytes
+        uint32_t *len_rows[2];    // [n_rows]
+        std::vector<hipEvent_t> ev_in[2]; // per chunk: the chunk's columns are in the slot rows (k_rows_in, on the upload stream)
+        unsigned hold_of[2];      // the ticket of the call hold the slot's call left in force (0: none)
         int n_chunks[2];
         double bytes_up[2], bytes_dn[2];
         bool pending[2];
@@ -385,7 +394,8 @@ static int batch_build(mp3mi_batch *b, int n_streams, int rate_hz, int channels,
     b->sb_dbg = NULL;
     b->slots_on = false;
     b->slot_frames_h.assign((size_t) n_streams, -1);
-    b->ctl_bytes = ((size_t) n_streams * 17 + 255) & ~(size_t) 255;
+    b->ctl_rows_off = ((size_t) n_streams * 17 + 3) & ~(size_t) 3;
+    b->ctl_bytes = (b->ctl_rows_off + (size_t) n_streams * 4 + 255) & ~(size_t) 255;
     for (int i = 0; i < 2; i++) {
         CHK(hipHostMalloc((void **) &b->ctl_stage[i], b->ctl_bytes, 0));
         CHK(hipMalloc((void **) &b->ctl_dev[i], b->ctl_bytes));
@@ -484,9 +494,12 @@ extern "C" void mp3mi_batch_destroy(mp3mi_batch *b)
             if (b->hio.pcm[i]) hipFree(b->hio.pcm[i]);
             if (b->hio.out[i]) hipFree(b->hio.out[i]);
             if (b->hio.len[i]) hipFree(b->hio.len[i]);
+            if (b->hio.pcm_rows[i]) hipFree(b->hio.pcm_rows[i]);
+            if (b->hio.out_rows[i]) hipFree(b->hio.out_rows[i]);
+            if (b->hio.len_rows[i]) hipFree(b->hio.len_rows[i]);
             if (b->hio.pcm_free[i]) hipEventDestroy(b->hio.pcm_free[i]);
             if (b->hio.out_free[i]) hipEventDestroy(b->hio.out_free[i]);
-            for (std::vector<hipEvent_t> *v : {&b->hio.ev_fmt[i], &b->hio.t_up[i], &b->hio.t_dn[i]})
+            for (std::vector<hipEvent_t> *v : {&b->hio.ev_fmt[i], &b->hio.t_up[i], &b->hio.t_dn[i], &b->hio.ev_in[i]})
                 for (hipEvent_t e : *v) hipEventDestroy(e);
         }
         if (b->hio.h2d) hipStreamDestroy(b->hio.h2d);
@@ -547,6 +560,10 @@ struct host_call { // a call on host buffers (mp3mi_batch_encode_host_async): wh
     size_t out_stride;
     uint32_t *out_len;
     int slot;
+    // a per-slot call with a row map: the caller's buffers hold n_rows dense rows, row r belongs to slot rows_host[r]
+    // (rows_host NULL: a row per stream, no map); rows_dev is the map's copy in the call's control block (slots_impl)
+    int n_rows;
+    const int32_t *rows_host, *rows_dev;
 };
 struct slot_call { // a per-slot call (mp3mi_batch_encode_slots): its control block on the device (mp3mi_batch::ctl_dev)
     const int64_t *fabs;  // [S] index of the call's first frame in the stream of each slot
@@ -648,8 +665,24 @@ static int ctl_take(mp3mi_batch *b, int *par)
     return MP3MI_OK;
 }
 
+// The rules of a per-slot call, slot by slot (f: slot_frames_now)
+static bool slots_rules_ok(const mp3mi_batch *b, const int64_t *f, int n_frames, const uint8_t *ctl_host, const int32_t *n_samples_host)
+{
+    const int32_t full = (int32_t) n_frames * 1152;
+    for (int s = 0; s < b->n_streams; s++) {
+        const int c = ctl_host[s];
+        if (c & ~(MP3MI_SLOT_START | MP3MI_SLOT_END)) return false;
+        const bool open = f[s] >= 0, start = c & MP3MI_SLOT_START, end = c & MP3MI_SLOT_END, part = open || start;
+        if (end && !part) return false;
+        const int32_t n = n_samples_host ? n_samples_host[s] : (part ? full : 0);
+        if (!part ? n != 0 : (!end ? n != full : (n < 0 || n > full))) return false;
+    }
+    return true;
+}
+
+// ctl_host / n_samples_host are per SLOT; hc: the call's buffers are the host-buffer copies of hc->slot, and the caller's are hc's
 static int slots_impl(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, const uint8_t *ctl_host, const int32_t *n_samples_host,
-                      uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev)
+                      uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev, host_call *hc = NULL)
 {
     if (!b || !pcm_dev || !ctl_host || !out_dev || !out_len_dev || n_frames <= 0 || n_frames > b->max_frames) return MP3MI_ERR_ARG;
     if (out_stride < (size_t) n_frames * (size_t) b->max_frame_bytes + 1 + MP3MI_CARRY_BYTES) return MP3MI_ERR_ARG;
@@ -658,18 +691,15 @@ static int slots_impl(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, cons
     std::vector<int64_t> f((size_t) S);
     slot_frames_now(b, f.data());
     // every rule first: a call that breaks one leaves the batch as it was
-    for (int s = 0; s < S; s++) {
-        const int c = ctl_host[s];
-        if (c & ~(MP3MI_SLOT_START | MP3MI_SLOT_END)) return MP3MI_ERR_ARG;
-        const bool open = f[s] >= 0, start = c & MP3MI_SLOT_START, end = c & MP3MI_SLOT_END, part = open || start;
-        if (end && !part) return MP3MI_ERR_ARG;
-        const int32_t n = n_samples_host ? n_samples_host[s] : (part ? full : 0);
-        if (!part ? n != 0 : (!end ? n != full : (n < 0 || n > full))) return MP3MI_ERR_ARG;
-    }
+    if (!slots_rules_ok(b, f.data(), n_frames, ctl_host, n_samples_host)) return MP3MI_ERR_ARG;
     ON_DEVICE(b);
     slot_call sc;
     if (ctl_take(b, &sc.par) != MP3MI_OK) return MP3MI_ERR_HIP;
     uint8_t *blk = b->ctl_stage[sc.par];
+    if (hc && hc->rows_host) {
+        memcpy(blk + b->ctl_rows_off, hc->rows_host, sizeof(int32_t) * (size_t) hc->n_rows);
+        hc->rows_dev = (const int32_t *) (b->ctl_dev[sc.par] + b->ctl_rows_off);
+    }
     int64_t *fabs = (int64_t *) blk;
     int32_t *ns = (int32_t *) (blk + 8 * (size_t) S), *list = (int32_t *) (blk + 12 * (size_t) S);
     uint8_t *ctl = blk + 16 * (size_t) S;
@@ -690,7 +720,7 @@ static int slots_impl(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, cons
     sc.ns = (const int32_t *) (dev + 8 * (size_t) S);
     sc.list = (const int32_t *) (dev + 12 * (size_t) S);
     sc.ctl = dev + 16 * (size_t) S;
-    const int rc = encode_impl(b, pcm_dev, NULL, n_frames, out_dev, out_stride, out_len_dev, false, NULL, &sc);
+    const int rc = encode_impl(b, pcm_dev, NULL, n_frames, out_dev, out_stride, out_len_dev, false, hc, &sc);
     if (rc != MP3MI_OK) return rc;
     b->ctl_calls++;
     for (int s = 0; s < S; s++) {
@@ -931,24 +961,39 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         // the chunk's frames; the layout on the device is the caller's).  The chunk's first kernel waits for its copy, so chunk
         // c + 1 crosses PCIe while chunk c is encoded -- and, with calls issued back to back, the next call's first chunk
         // while this call's last one is.
+        // A per-slot call with a row map: the caller's rows are dense, one per live slot.  They cross as they are, into the
+        // dense device buffer, and behind each chunk's copy k_rows_in spreads the chunk's columns into the slot rows the
+        // kernels read -- on the upload stream, so a chunk's rows are in place while the chunk before is encoded.  (The map is
+        // in the control block, which the front stream uploads: ev_ctl_up.)
         mp3mi_batch::host_io &H = b->hio;
         const int sl = hc->slot;
+        const bool mapped = hc->rows_dev != NULL;
+        const size_t R = mapped ? (size_t) hc->n_rows : (size_t) S;
         if (H.pcm_used[sl]) CHK(hipStreamWaitEvent(H.h2d, H.pcm_free[sl], 0)); // (the kernels of the call two before this one)
         while ((int) H.t_up[sl].size() < 2 * nchunks) {
             hipEvent_t e;
             for (std::vector<hipEvent_t> *v : {&H.t_up[sl], &H.t_dn[sl]}) { CHK(hipEventCreate(&e)); v->push_back(e); }
-            if (H.t_up[sl].size() % 2 == 0) { CHK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); H.ev_fmt[sl].push_back(e); }
+            if (H.t_up[sl].size() % 2 == 0) {
+                for (std::vector<hipEvent_t> *v : {&H.ev_fmt[sl], &H.ev_in[sl]}) { CHK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); v->push_back(e); }
+            }
         }
         H.n_chunks[sl] = nchunks;
         H.bytes_up[sl] = H.bytes_dn[sl] = 0.0;
+        if (mapped) CHK(hipStreamWaitEvent(H.h2d, b->ev_ctl_up, 0));
         for (int c = 0; c < nchunks; c++) {
             const int f0 = c * cfr, nf = (n_frames - f0 < cfr) ? n_frames - f0 : cfr;
             const size_t off = (size_t) f0 * 1152 * (size_t) C, width = (size_t) nf * 1152 * (size_t) C * sizeof(int16_t);
+            int16_t *dst = mapped ? H.pcm_rows[sl] : H.pcm[sl];
             CHK(hipEventRecord(H.t_up[sl][2 * c], H.h2d));
-            CHK(hipMemcpy2DAsync(H.pcm[sl] + off, pcm_pitch * sizeof(int16_t), hc->pcm + off, pcm_pitch * sizeof(int16_t), width, (size_t) S,
+            CHK(hipMemcpy2DAsync(dst + off, pcm_pitch * sizeof(int16_t), hc->pcm + off, pcm_pitch * sizeof(int16_t), width, R,
                                  hipMemcpyHostToDevice, H.h2d));
             CHK(hipEventRecord(H.t_up[sl][2 * c + 1], H.h2d));
-            H.bytes_up[sl] += (double) width * S;
+            H.bytes_up[sl] += (double) width * (double) R;
+            if (mapped) {
+                mp3mi_launch_rows_in(hc->rows_dev, hc->n_rows, H.pcm_rows[sl], H.pcm[sl], pcm_pitch * sizeof(int16_t), off * sizeof(int16_t), width, H.h2d);
+                CHK(hipGetLastError());
+                CHK(hipEventRecord(H.ev_in[sl][c], H.h2d));
+            }
         }
     }
     const size_t psy_state_bytes = mp3mi_psy_state_size() * (size_t) C, loop_state_bytes = mp3mi_loop_state_size();
@@ -956,7 +1001,8 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
     auto stage_x = [&](int k, int which) -> int {
         const item_view v = view(k);
         const size_t r = v.rec0;
-        if (hc && (which & 1) && k % P == 0) CHK(hipStreamWaitEvent(b->stream, b->hio.t_up[hc->slot][2 * (k / P) + 1], 0)); // the chunk's PCM is up
+        if (hc && (which & 1) && k % P == 0) // the chunk's PCM is up (and in its slots' rows)
+            CHK(hipStreamWaitEvent(b->stream, hc->rows_dev ? b->hio.ev_in[hc->slot][k / P] : b->hio.t_up[hc->slot][2 * (k / P) + 1], 0));
         mp3mi_launch_fft(b->T, v.g, pcm_dev + v.s0 * pcm_pitch, b->energy_l + r * MP3MI_HBLK_P, b->energy_s + r * 3 * MP3MI_HBLK_S,
                          b->fft_bins + r * MP3MI_FFT_BINS, b->cw_mid + r * 50, b->hist6 + r * 12, b->stream, which);
         CHK(hipGetLastError());
@@ -980,7 +1026,10 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
     bool joined = false;
     {
         const item_view v0 = view(0);
-        if (b->held && !y_after(v0)) {
+        // (A per-slot call on host buffers does not join: its first transforms wait for the tick's PCM to cross PCIe, and a
+        // k_loop held for that long -- a tick is one chunk, so the held launch is the whole tick before -- leaves the chip idle
+        // during the upload: 29.7 ms per 4096 x 32 tick against 16.4 resident.  Let go at once, that k_loop runs beside the upload.)
+        if (b->held && !y_after(v0) && !(hc && sc)) {
             if (stage_x(0, 1) != MP3MI_OK) return MP3MI_ERR_HIP;
             mp3mi_launch_hold_release(b->hold_flag_d, b->hold_seq, b->stream);
             CHK(hipGetLastError());
@@ -991,6 +1040,40 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
             if (stage_x(0, 3) != MP3MI_OK) return MP3MI_ERR_HIP;
         }
     }
+    // The call's file bytes, behind its last formatter -- a streaming call's behind its k_stream_tail, which settles the lengths
+    // -- as ONE copy: rows of the caller's stride when that is the device
+    // buffer's (mp3mi_batch_out_stride(b, max_frames): a plain copy, which the DMA engines take), a 2-D copy
+    // otherwise.  (A window of columns per chunk -- the bytes that became final with it -- was measured first: the
+    // runtime runs such rectangles as copy KERNELS, 11 ms each beside the encoder's own, and the step lost 56 ms;
+    // profiles/r04_experiments.txt.  With calls issued back to back this copy runs beside the next call's kernels.)
+    // With a row map k_rows_out gathers the listed slots' bytes and lengths into dense rows of the caller's stride first, so
+    // that the copy is plain whatever the stride and moves the live rows only.
+    auto download = [&]() -> int {
+        mp3mi_batch::host_io &H = b->hio;
+        const int sl = hc->slot;
+        const bool mapped = hc->rows_dev != NULL;
+        const size_t R = mapped ? (size_t) hc->n_rows : (size_t) S;
+        const size_t row = mapped ? hc->out_stride : (hc->out_stride < out_stride ? hc->out_stride : out_stride);
+        if (mapped) {
+            mp3mi_launch_rows_out(hc->rows_dev, hc->n_rows, out_dev, out_stride, out_len_dev, H.out_rows[sl], hc->out_stride, H.len_rows[sl], b->lstream);
+            CHK(hipGetLastError());
+        }
+        CHK(hipEventRecord(H.ev_fmt[sl][0], b->lstream));
+        CHK(hipStreamWaitEvent(H.d2h, H.ev_fmt[sl][0], 0));
+        CHK(hipEventRecord(H.t_dn[sl][0], H.d2h));
+        if (mapped)
+            CHK(hipMemcpyAsync(hc->out, H.out_rows[sl], hc->out_stride * R, hipMemcpyDeviceToHost, H.d2h));
+        else if (hc->out_stride == out_stride)
+            CHK(hipMemcpyAsync(hc->out, out_dev, out_stride * (size_t) S, hipMemcpyDeviceToHost, H.d2h));
+        else
+            CHK(hipMemcpy2DAsync(hc->out, hc->out_stride, out_dev, out_stride, row, (size_t) S, hipMemcpyDeviceToHost, H.d2h));
+        CHK(hipMemcpyAsync(hc->out_len, mapped ? H.len_rows[sl] : out_len_dev, sizeof(uint32_t) * R, hipMemcpyDeviceToHost, H.d2h));
+        CHK(hipEventRecord(H.t_dn[sl][1], H.d2h));
+        H.bytes_dn[sl] += (double) row * (double) R;
+        CHK(hipEventRecord(H.out_free[sl], H.d2h));
+        H.out_used[sl] = true;
+        return MP3MI_OK;
+    };
     for (int k = 0; k < n_items; k++) {
         const item_view v = view(k);
         const mp3mi_geom &g = v.g;
@@ -1042,7 +1125,7 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         }
         CHK(hipMemsetAsync(b->gate_count + 1, 0, sizeof(unsigned), b->lstream));
         CHK(hipStreamWaitEvent(b->lstream, b->ev_front[v.ev], 0));
-        if (b->hold_calls && k == n_items - 1) {
+        if (b->hold_calls && k == n_items - 1 && !(hc && sc)) { // (a per-slot call on host buffers is not held: the next one would not join, above)
             // the call's LAST k_loop: held until the next call's first transforms are through (its first item then runs beside
             // this launch), the host lets go (hold_release), or the bound has passed: 20 ms, more for chunks so long that what the
             // front stream still holds of this item plus the next call's transforms take longer (0.4 ms per frame of a chunk)
@@ -1070,28 +1153,7 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
                             out_dev + v.s0 * out_stride, out_stride, out_len_dev + v.s0, (int32_t *) ((char *) b->loop_state + v.s0 * loop_state_bytes),
                             (int) (loop_state_bytes / 4), b->voided, b->lstream);
         CHK(hipGetLastError());
-        if (hc && k == n_items - 1) {
-            // The call's file bytes, behind its last formatter, as ONE copy: rows of the caller's stride when that is the device
-            // buffer's (mp3mi_batch_out_stride(b, max_frames): a plain copy, which the DMA engines take), a 2-D copy
-            // otherwise.  (A window of columns per chunk -- the bytes that became final with it -- was measured first: the
-            // runtime runs such rectangles as copy KERNELS, 11 ms each beside the encoder's own, and the step lost 56 ms;
-            // profiles/r04_experiments.txt.  With calls issued back to back this copy runs beside the next call's kernels.)
-            mp3mi_batch::host_io &H = b->hio;
-            const int sl = hc->slot;
-            const size_t row = hc->out_stride < out_stride ? hc->out_stride : out_stride;
-            CHK(hipEventRecord(H.ev_fmt[sl][0], b->lstream));
-            CHK(hipStreamWaitEvent(H.d2h, H.ev_fmt[sl][0], 0));
-            CHK(hipEventRecord(H.t_dn[sl][0], H.d2h));
-            if (hc->out_stride == out_stride)
-                CHK(hipMemcpyAsync(hc->out, out_dev, out_stride * (size_t) S, hipMemcpyDeviceToHost, H.d2h));
-            else
-                CHK(hipMemcpy2DAsync(hc->out, hc->out_stride, out_dev, out_stride, row, (size_t) S, hipMemcpyDeviceToHost, H.d2h));
-            CHK(hipMemcpyAsync(hc->out_len, out_len_dev, sizeof(uint32_t) * (size_t) S, hipMemcpyDeviceToHost, H.d2h));
-            CHK(hipEventRecord(H.t_dn[sl][1], H.d2h));
-            H.bytes_dn[sl] += (double) row * S;
-            CHK(hipEventRecord(H.out_free[sl], H.d2h));
-            H.out_used[sl] = true;
-        }
+        if (hc && whole_file && k == n_items - 1 && download() != MP3MI_OK) return MP3MI_ERR_HIP;
         b->last_nf = g.nf;
         b->last_slot = v.slot;
     }
@@ -1121,6 +1183,7 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
             mp3mi_launch_stream_tail(g, 0, (int32_t *) b->loop_state, (int) (mp3mi_loop_state_size() / 4), b->bits_per_frame, out_dev,
                                      out_stride, b->out_base, b->carry, b->carry_len, out_len_dev, b->voided, b->lstream);
             CHK(hipGetLastError());
+            if (hc && download() != MP3MI_OK) return MP3MI_ERR_HIP;
         }
         CHK(hipEventRecord(b->ev_hist, b->stream));
         CHK(hipStreamWaitEvent(b->lstream, b->ev_hist, 0)); // ev_done below then covers both streams
@@ -1129,6 +1192,7 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         CHK(hipEventRecord(b->hio.pcm_free[hc->slot], b->lstream));
         b->hio.pcm_used[hc->slot] = true;
         b->hio.pending[hc->slot] = true;
+        b->hio.hold_of[hc->slot] = b->held ? b->hold_seq : 0u;
     }
     if (sc) { // (lstream has joined the front stream: every reader of this copy of the control block is ahead of this)
         CHK(hipEventRecord(b->ev_ctl[sc->par], b->lstream));
@@ -1323,6 +1387,89 @@ extern "C" int mp3mi_batch_encode_host_async(mp3mi_batch *b, const int16_t *pcm_
     const int rc = encode_impl(b, H.pcm[sl], NULL, n_frames, H.out[sl], H.out_stride, H.len[sl], true, &hc);
     if (rc == MP3MI_OK) H.call_no++; // (a call that failed took no slot)
     return rc;
+}
+
+// The dense device buffers of a call with a row map (mp3mi_batch::host_io::pcm_rows): PCM and lengths for as many rows as there
+// are slots; the output rows have the caller's stride, so that buffer grows with the largest call so far (behind the slot's
+// last download -- the host has waited for it: host_io_harvest).
+static int host_rows_init(mp3mi_batch *b, int sl, size_t out_stride)
+{
+    mp3mi_batch::host_io &H = b->hio;
+    const size_t S = (size_t) b->n_streams;
+    if (!H.pcm_rows[sl]) CHK(hipMalloc((void **) &H.pcm_rows[sl], S * (size_t) b->max_frames * 1152 * (size_t) b->channels * sizeof(int16_t)));
+    if (!H.len_rows[sl]) CHK(hipMalloc((void **) &H.len_rows[sl], S * sizeof(uint32_t)));
+    if (H.out_rows_cap[sl] < S * out_stride) {
+        if (H.out_rows[sl]) {
+            if (H.out_used[sl]) CHK(hipEventSynchronize(H.out_free[sl]));
+            CHK(hipFree(H.out_rows[sl]));
+            H.out_rows[sl] = NULL;
+            H.out_rows_cap[sl] = 0;
+        }
+        CHK(hipMalloc((void **) &H.out_rows[sl], S * out_stride));
+        H.out_rows_cap[sl] = S * out_stride;
+    }
+    return MP3MI_OK;
+}
+
+// mp3mi_batch_encode_slots with host buffers that hold a row per LIVE slot: the arrays by row become arrays by slot (a slot no
+// row names must be closed and stays so), the per-slot call's rules are checked on those, and the call runs as the per-slot
+// call on the host-buffer copies of the batch, with the row map between the dense rows and the rows per slot (encode_impl).
+extern "C" int mp3mi_batch_encode_slots_host_async(mp3mi_batch *b, const int16_t *pcm_host, int n_frames, int n_rows, const int32_t *row_slot_host,
+                                                   const uint8_t *ctl_host, const int32_t *n_samples_host, uint8_t *out_host, size_t out_stride,
+                                                   uint32_t *out_len_host)
+{
+    if (!b || !pcm_host || !ctl_host || !out_host || !out_len_host || n_frames <= 0 || n_frames > b->max_frames) return MP3MI_ERR_ARG;
+    const int S = b->n_streams;
+    if (n_rows < 1 || n_rows > S || (!row_slot_host && n_rows != S)) return MP3MI_ERR_ARG;
+    if (out_stride < mp3mi_batch_out_stride(b, n_frames)) return MP3MI_ERR_ARG;
+    std::vector<int64_t> f((size_t) S);
+    slot_frames_now(b, f.data());
+    std::vector<uint8_t> ctl_s;
+    std::vector<int32_t> ns_s;
+    const uint8_t *ctl = ctl_host;
+    const int32_t *ns = n_samples_host;
+    if (row_slot_host) {
+        ctl_s.assign((size_t) S, 0);
+        if (n_samples_host) ns_s.assign((size_t) S, 0);
+        std::vector<char> named((size_t) S, 0);
+        for (int r = 0; r < n_rows; r++) {
+            const int32_t s = row_slot_host[r];
+            if (s < 0 || s >= S || (r > 0 && s <= row_slot_host[r - 1])) return MP3MI_ERR_ARG;
+            if (f[s] < 0 && !(ctl_host[r] & MP3MI_SLOT_START)) return MP3MI_ERR_ARG; // a row carries a stream: open or starting
+            named[s] = 1;
+            ctl_s[s] = ctl_host[r];
+            if (n_samples_host) ns_s[s] = n_samples_host[r];
+        }
+        for (int s = 0; s < S; s++)
+            if (f[s] >= 0 && !named[s]) return MP3MI_ERR_ARG; // an open stream goes on (or ends) in every call
+        ctl = ctl_s.data();
+        ns = n_samples_host ? ns_s.data() : NULL;
+    }
+    if (!slots_rules_ok(b, f.data(), n_frames, ctl, ns)) return MP3MI_ERR_ARG;
+    ON_DEVICE(b);
+    mp3mi_batch::host_io &H = b->hio;
+    const int sl = (int) (H.call_no & 1);
+    if (host_io_init(b, sl) != MP3MI_OK) return MP3MI_ERR_HIP;
+    if (host_io_harvest(b, sl) != MP3MI_OK) return MP3MI_ERR_HIP; // (waits for the call two before this one: at most two in flight)
+    if (row_slot_host && host_rows_init(b, sl, out_stride) != MP3MI_OK) return MP3MI_ERR_HIP;
+    host_call hc = {pcm_host, out_host, out_stride, out_len_host, sl, n_rows, row_slot_host, NULL};
+    const int rc = slots_impl(b, H.pcm[sl], n_frames, ctl, ns, H.out[sl], H.out_stride, H.len[sl], &hc);
+    if (rc == MP3MI_OK) H.call_no++; // (a call that failed took no slot)
+    return rc;
+}
+
+// Waits for the results of ONE host-buffer call: the latest (0) or the one before (1).  Only the call hold that very call left
+// in force is let go -- a later call's stays, so a server collects tick t while tick t + 1 keeps its place in the pipeline.
+extern "C" int mp3mi_batch_host_wait(mp3mi_batch *b, int calls_back)
+{
+    if (!b || calls_back < 0 || calls_back > 1) return MP3MI_ERR_ARG;
+    mp3mi_batch::host_io &H = b->hio;
+    if (!H.ready || H.call_no <= (unsigned) calls_back) return MP3MI_ERR_ARG;
+    ON_DEVICE(b);
+    const int sl = (int) ((H.call_no - 1u - (unsigned) calls_back) & 1u);
+    if (b->held && H.hold_of[sl] == b->hold_seq) hold_release(b);
+    CHK(hipEventSynchronize(H.t_dn[sl][1]));
+    return MP3MI_OK;
 }
 
 extern "C" int mp3mi_batch_host_io_stats(mp3mi_batch *b, mp3mi_host_io_stats *st)

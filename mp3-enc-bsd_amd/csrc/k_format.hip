@@ -542,6 +542,82 @@ void mp3mi_launch_slot_begin(const int32_t *list, int n_list, mp3mi_slot_region 
     hipLaunchKernelGGL(k_slot_begin, dim3((unsigned) n_list), dim3(256), 0, st, list, r0, r1, r2);
 }
 
+// ---- per-slot streaming on host buffers (mp3mi_batch_encode_slots_host_async) ----
+// The caller's buffers hold one ROW per live slot, dense; the encoder's kernels read and write one row per SLOT.  Two bandwidth
+// kernels sit between the copies and the encoder: both move 16 bytes per lane and access (one wavefront-instruction = 1 KiB,
+// contiguous), the row of a workgroup -- and with it the slot, one load of the map -- is uniform, and no LDS is involved:
+// nothing is reused, so registers are the whole staging.
+//
+// k_rows_in: the columns [col0, col0 + width) -- a chunk's frames -- of the dense rows into the slot rows of the device PCM
+// copy.  Bytes throughout; pitch, col0 and width are multiples of 16 (a frame of one channel is 2304 bytes), both bases come
+// from hipMalloc.  gridDim.y workgroups share a row; four accesses are in flight per lane.
+__global__ void __launch_bounds__(256) k_rows_in(const int32_t *__restrict__ row_slot, const uint8_t *__restrict__ dense,
+                                                 uint8_t *__restrict__ pcm, size_t pitch, size_t col0, size_t width)
+{
+    const size_t r = blockIdx.x, s = (size_t) row_slot[r];
+    const uint4 *src = (const uint4 *) (dense + r * pitch + col0);
+    uint4 *dst = (uint4 *) (pcm + s * pitch + col0);
+    const size_t n = width / 16, step = (size_t) 256 * gridDim.y;
+    size_t i = (size_t) blockIdx.y * 256 + threadIdx.x;
+    for (; i + 3 * step < n; i += 4 * step) {
+        const uint4 a = src[i], b = src[i + step], c = src[i + 2 * step], d = src[i + 3 * step];
+        dst[i] = a; dst[i + step] = b; dst[i + 2 * step] = c; dst[i + 3 * step] = d;
+    }
+    for (; i < n; i += step) dst[i] = src[i];
+}
+
+void mp3mi_launch_rows_in(const int32_t *row_slot, int n_rows, const int16_t *dense, int16_t *pcm, size_t pitch_bytes, size_t col0_bytes,
+                          size_t width_bytes, hipStream_t st)
+{
+    if (n_rows <= 0 || width_bytes == 0) return;
+    const size_t per_wg = (size_t) 256 * 16 * 4; // four accesses per lane
+    size_t ny = (width_bytes + per_wg - 1) / per_wg;
+    if (ny > 8) ny = 8;
+    hipLaunchKernelGGL(k_rows_in, dim3((unsigned) n_rows, (unsigned) ny), dim3(256), 0, st, row_slot, (const uint8_t *) dense, (uint8_t *) pcm,
+                       pitch_bytes, col0_bytes, width_bytes);
+}
+
+// k_rows_out: behind the call's k_stream_tail, the out_len bytes of every listed slot's row, and the length, into dense rows of
+// the caller's stride (the rest of a dense row is zeroed: the download is one plain copy of whole rows).  The slot rows' stride
+// is a multiple of 256; the dense stride is the caller's: 16 bytes per lane when it is a multiple of 16, bytes otherwise.
+__global__ void __launch_bounds__(256) k_rows_out(const int32_t *__restrict__ row_slot, const uint8_t *__restrict__ out, size_t out_stride,
+                                                  const uint32_t *__restrict__ out_len, uint8_t *__restrict__ dense, size_t dense_stride,
+                                                  uint32_t *__restrict__ dense_len)
+{
+    const size_t r = blockIdx.x, s = (size_t) row_slot[r];
+    const size_t lim = out_stride < dense_stride ? out_stride : dense_stride;
+    size_t len = out_len[s];
+    if (len > lim) len = lim; // (a row never holds more: out_len <= out_stride, and the caller's stride is checked on the host)
+    const uint8_t *src = out + s * out_stride;
+    uint8_t *dst = dense + r * dense_stride;
+    if (threadIdx.x == 0) dense_len[r] = (uint32_t) len;
+    if (dense_stride % 16 == 0) {
+        const size_t n = dense_stride / 16, n_src = (len + 15) / 16; // (16 n_src <= out_stride: a multiple of 256)
+        for (size_t i = threadIdx.x; i < n; i += 256) {
+            uint4 v;
+            v.x = v.y = v.z = v.w = 0u;
+            if (i < n_src) {
+                v = ((const uint4 *) src)[i];
+                const size_t keep = len - 16 * i; // bytes of this vector that belong to the file (>= 16: all)
+                if (keep < 16) { // the file's last vector: word j keeps its first keep - 4 j bytes
+                    auto mask = [&](int j) { const long k = (long) keep - 4 * j; return k >= 4 ? 0xFFFFFFFFu : (k <= 0 ? 0u : 0xFFFFFFFFu >> (8 * (4 - k))); };
+                    v.x &= mask(0); v.y &= mask(1); v.z &= mask(2); v.w &= mask(3);
+                }
+            }
+            ((uint4 *) dst)[i] = v;
+        }
+    } else {
+        for (size_t i = threadIdx.x; i < dense_stride; i += 256) dst[i] = i < len ? src[i] : (uint8_t) 0;
+    }
+}
+
+void mp3mi_launch_rows_out(const int32_t *row_slot, int n_rows, const uint8_t *out, size_t out_stride, const uint32_t *out_len, uint8_t *dense,
+                           size_t dense_stride, uint32_t *dense_len, hipStream_t st)
+{
+    if (n_rows <= 0) return;
+    hipLaunchKernelGGL(k_rows_out, dim3((unsigned) n_rows), dim3(256), 0, st, row_slot, out, out_stride, out_len, dense, dense_stride, dense_len);
+}
+
 // the last MP3MI_PCM_HIST samples of the call (a frame has 1152 > MP3MI_PCM_HIST) are the next call's history
 __global__ void __launch_bounds__(256) k_hist_save(mp3mi_geom geo, const int16_t *__restrict__ pcm, int16_t *__restrict__ hist)
 {

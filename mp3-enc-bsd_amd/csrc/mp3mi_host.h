@@ -141,6 +141,13 @@ void mp3mi_launch_stream_tail(const mp3mi_geom &g, int flush, int32_t *loop_stat
 struct mp3mi_slot_region { void *base; size_t bytes; };
 void mp3mi_launch_slot_begin(const int32_t *list, int n_list, mp3mi_slot_region r0, mp3mi_slot_region r1, mp3mi_slot_region r2,
                              hipStream_t st);
+/* per-slot streaming on host buffers: dense rows (one per live slot, row_slot[r] = its slot) to and from the rows per slot.
+   k_rows_in: bytes [col0, col0 + width) of every dense PCM row into the same columns of its slot's row (all multiples of 16);
+   k_rows_out: out_len[slot] bytes of every listed slot's output row and the length into dense rows of dense_stride, rest zeroed */
+void mp3mi_launch_rows_in(const int32_t *row_slot, int n_rows, const int16_t *dense, int16_t *pcm, size_t pitch_bytes, size_t col0_bytes,
+                          size_t width_bytes, hipStream_t st);
+void mp3mi_launch_rows_out(const int32_t *row_slot, int n_rows, const uint8_t *out, size_t out_stride, const uint32_t *out_len, uint8_t *dense,
+                           size_t dense_stride, uint32_t *dense_len, hipStream_t st);
 /* status[s] = the status word of stream s (a gather out of the strided state records) */
 void mp3mi_launch_status_gather(int n_streams, const int32_t *loop_state, int loop_state_words, int32_t *status, hipStream_t st);
 /* the reverse, for the streams a flush ended: their status words go back into the cleared state records, marked as reported */

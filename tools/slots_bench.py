@@ -8,7 +8,17 @@
                                                    many closed slots START
 Prints one JSON line: ms per call of each case and the library's source hash.
 
-usage: slots_bench.py [--calls 20] [--frames 32] [--streams 4096] [--reps 3]"""
+--host [--occupancy F]: the per-slot cases on PAGE-LOCKED HOST buffers (mp3mi_batch_encode_slots_host_async; ticks issued back
+to back, tick t collected with mp3mi_batch_host_wait(1) after tick t + 1 has been issued), with a fraction F of the slots live
+(the others stay closed; with F < 1, or with --map, the rows go through a row map, so only the live rows cross PCIe):
+  (d) resident_slots      encode_slots on resident PCM with the same live slots                    the floor
+  (e) sync_copy           what a caller had before the host call: hipMemcpy of full [n_streams] rows up, encode_slots,
+                          sync, hipMemcpy down, tick by tick                                       the baseline to beat
+  (f) host_continue       the host call, every live slot continuing
+  (g) host_churn          the host call; in every tick 1/32 of the live slots END and as many closed ones START, so the row
+                          set changes from tick to tick
+
+usage: slots_bench.py [--calls 20] [--frames 32] [--streams 4096] [--reps 3] [--host [--occupancy 1.0] [--map]]"""
 import argparse
 import importlib
 import json
@@ -27,7 +37,12 @@ def main():
     ap.add_argument("--frames", type=int, default=32)
     ap.add_argument("--streams", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=3, help="runs of every case; the fastest counts")
+    ap.add_argument("--host", action="store_true", help="the per-slot cases on page-locked host buffers")
+    ap.add_argument("--occupancy", type=float, default=1.0, help="--host: fraction of the slots that are live")
+    ap.add_argument("--map", action="store_true", help="--host: a row map at occupancy 1.0 too (k_rows_in / k_rows_out run)")
     a = ap.parse_args()
+    if a.host:
+        return host_main(a)
     import torch
     mp3 = importlib.import_module("mp3-enc-bsd_amd")
     S, nf, rate, ch, kbps = a.streams, a.frames, 44100, 2, 128
@@ -85,6 +100,105 @@ def main():
                       "kbps": kbps, "ms_per_call": res,
                       "continue_vs_next": round(res["slots_continue"] / res["encode_next"], 4),
                       "churn_vs_continue": round(res["slots_churn"] / res["slots_continue"], 4),
+                      "source_hash": mp3.lib().mp3mi_source_hash().decode()}))
+
+
+def host_main(a):
+    import torch
+    mp3 = importlib.import_module("mp3-enc-bsd_amd")
+    S, nf, rate, ch, kbps = a.streams, a.frames, 44100, 2, 128
+    full = nf * 1152
+    dev = torch.device("cuda:0")
+    pcm = torch.empty((S, full * ch), dtype=torch.int16, device=dev)
+    torch.cuda.synchronize()
+    mp3.synth_pcm_device(pcm, full, ch, rate)
+    b = mp3.Batch(S, rate, ch, kbps, nf)
+    stride = b.out_stride(nf)
+    out = torch.zeros((S, stride), dtype=torch.uint8, device=dev)
+    out_len = torch.zeros(S, dtype=torch.int32, device=dev)
+    rng = np.random.default_rng(1)
+    R = max(1, min(S, int(round(a.occupancy * S))))
+    live = np.sort(rng.choice(S, R, replace=False))
+    mapped = a.map or R < S
+    is_live = np.zeros(S, bool)
+    is_live[live] = True
+    # page-locked: the PCM of all slots (the baseline moves all of it; the host call reads the first rows of it as its dense
+    # rows -- every row holds a stream's worth of synthetic PCM, which row is immaterial to the time), two sets of outputs
+    pcm_h = torch.empty((S, full * ch), dtype=torch.int16).pin_memory()
+    pcm_h.copy_(pcm)
+    out_h = [torch.zeros((S, stride), dtype=torch.uint8).pin_memory() for _ in range(2)]
+    len_h = [torch.zeros(S, dtype=torch.int32).pin_memory() for _ in range(2)]
+    torch.cuda.synchronize()
+
+    def resident():
+        b.encode_slots(pcm, nf, out, out_len, start=is_live)
+        for _ in range(a.calls - 1):
+            b.encode_slots(pcm, nf, out, out_len)
+
+    def sync_copy():
+        for k in range(a.calls):
+            pcm.copy_(pcm_h)  # full rows, blocking
+            torch.cuda.synchronize()
+            b.encode_slots(pcm, nf, out, out_len, start=is_live if k == 0 else None)
+            b.sync()
+            out_h[0].copy_(out)
+            len_h[0].copy_(out_len)
+            torch.cuda.synchronize()
+
+    def host_tick(k, rows, **kw):
+        n = len(rows)
+        b.encode_slots_host(pcm_h[:n], nf, out_h[k & 1][:n], len_h[k & 1][:n], rows=rows if mapped else None, **kw)
+        if k >= 1:
+            b.host_wait(1)  # collect tick k - 1 behind tick k's issue
+
+    def host_continue():
+        host_tick(0, live, start=np.ones(R, bool))
+        for k in range(1, a.calls):
+            host_tick(k, live)
+        b.host_wait(0)
+
+    def host_churn():
+        open_ = is_live.copy()
+        host_tick(0, live, start=np.ones(R, bool))
+        closed_last = np.zeros(S, bool)
+        for k in range(1, a.calls):
+            start = closed_last
+            end = np.zeros(S, bool)
+            end[rng.choice(np.flatnonzero(open_), max(1, R // 32), replace=False)] = True
+            rows = np.flatnonzero(open_ | start)
+            ns = np.full(S, full, np.int32)
+            ns[end] = rng.integers(0, full + 1, int(end.sum()))
+            host_tick(k, rows, start=start[rows], end=end[rows], n_samples=ns[rows])
+            open_ = (open_ | start) & ~end
+            closed_last = end
+        b.host_wait(0)
+
+    if not mapped:
+        # without a row map a closed slot still has a row, and a row must carry a stream: churn cannot leave slots closed
+        cases = (("resident_slots", resident), ("sync_copy", sync_copy), ("host_continue", host_continue))
+    else:
+        cases = (("resident_slots", resident), ("sync_copy", sync_copy), ("host_continue", host_continue), ("host_churn", host_churn))
+    res = {}
+    for name, fn in cases:
+        best = None
+        for r in range(a.reps + 1):  # the first run warms up
+            b.reset()
+            b.sync()
+            t0 = time.perf_counter()
+            fn()
+            b.flush(out, out_len)
+            b.sync()
+            ms = (time.perf_counter() - t0) * 1e3 / a.calls
+            if r > 0:
+                best = ms if best is None else min(best, ms)
+        res[name] = round(best, 3)
+    st = b.host_io_stats()
+    b.close()
+    print(json.dumps({"tool": "slots_bench --host", "streams": S, "live_slots": R, "row_map": bool(mapped), "frames_per_call": nf, "calls": a.calls,
+                      "rate": rate, "channels": ch, "kbps": kbps, "ms_per_call": res,
+                      "host_vs_resident": round(res["host_continue"] / res["resident_slots"], 4),
+                      "host_vs_sync_copy": round(res["host_continue"] / res["sync_copy"], 4),
+                      "h2d_GBps": round(st["h2d_bytes"] / max(st["h2d_ms"], 1e-9) / 1e6, 2), "d2h_GBps": round(st["d2h_bytes"] / max(st["d2h_ms"], 1e-9) / 1e6, 2),
                       "source_hash": mp3.lib().mp3mi_source_hash().decode()}))
 
 
