@@ -352,6 +352,21 @@ enum {
 };
 int mp3mi_debug_quantize_count(int rate_hz, int n_gran, const double *xr, const int32_t *gran, int16_t *ix, double *xr_out,
                                int32_t *fields);
+/* Self-test hook: k_format (csrc/k_format.hip), as a whole-file batch call launches it, on n_streams chains of GIVEN frames of one
+ * format: rate_hz, channels, kbps, the header's mode field (0 stereo, 1 joint, 2 dual, 3 mono) and hdr_flags (mode_ext << 4 |
+ * copyright << 3 | original << 2 | emphasis), crc (error protection).  Chain s has n_frames_s[s] <= n_frames frames; ix holds
+ * the signed quantised values [n_streams][2 * n_frames][channels][576], side the mp3mi_frame_side records (csrc/mp3mi_dev.h)
+ * [n_streams][n_frames].  Out: the files' bytes in rows of out_stride >= n_frames * frame bytes + 1, their lengths and per
+ * stream 0 or MP3MI_STREAM_* | frames << 8 (a chain the reference dies on in its flush: length 0).
+ * MP3MI_ERR_ARG, and nothing is launched, for a chain outside the formatter's domain ("III_format_bitstream"):
+ * main_data_begin is the reservoir's (0 for frame 0, then + slot bytes - the frame's bytes, 0..511, never negative), a frame's
+ * part2_3_length sum + resvDrain is a multiple of 8, part2_3_length <= 4095 covers part2_length (the scalefactor bits as
+ * scalefac_compress, scfsi and the granule give them) + the code bits, each region's table exists and takes the region's
+ * maximum (0 only for zeros), block type 2 has (big_values, count1) = (288, 0) or (0, 0), types 1 and 3 region counts 7 / 13,
+ * 2 big_values + 4 count1 <= 576, count1 lines are 0 / +-1 and the lines behind them 0, scalefactors fit their slen. */
+int mp3mi_debug_format_frames(int rate_hz, int channels, int kbps, int hdr_mode, int hdr_flags, int crc, int n_streams, int n_frames,
+                              const int32_t *n_frames_s, const int16_t *ix, const void *side, uint8_t *out, size_t out_stride,
+                              uint32_t *out_len, int32_t *status);
 /* diagnostics: of the (granule, channel) records of the last call's LAST chunk, how many needed the second tier of
  * the unpredictability (k_part's check); *n_records receives their number.  Call after
  * mp3mi_batch_sync. */

@@ -1,0 +1,202 @@
+// The self-test hook mp3mi_debug_format_frames (include/mp3mi.h): chains of given frames -- quantised values, side information,
+// scalefactors -- through k_format as the batch launches it for a whole file.  Host code only: k_format.hip is untouched, the
+// kernel is the one the encoder runs.
+//
+// What k_format takes on trust from k_loop is checked here first (a chain that breaks one of the rules is refused, nothing is
+// launched): the rules are those under which the reference's III_format_bitstream (src/l3bitstream.c:67-162) runs through all
+// of its asserts and its bit counts stay inside the frame image (fmt_lds.words) and the output row.
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include "mp3mi_host.h"
+#include "mp3mi.h"
+
+static const int FD_BITRATES[15] = {0, 32, 40, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256, 320}; // src/common.c:124
+static const int FD_SLEN1[16] = {0, 0, 0, 0, 3, 1, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4};                      // src/l3bitstream.c:171-172
+static const int FD_SLEN2[16] = {0, 1, 2, 3, 0, 1, 2, 3, 1, 2, 3, 1, 2, 3, 2, 3};
+static const int FD_IMAGE_BITS = 640 * 32; // fmt_lds.words (k_format.hip)
+
+static inline int fd_abs(int v) { return v < 0 ? -v : v; }
+
+// table t may code the pair (x, y) of magnitudes: 0 for an all-zero region only; no escape below table 16
+static bool fd_table_takes(const mp3mi_tables *T, int t, int x, int y)
+{
+    const int m = x > y ? x : y;
+    if (t == 0) return m == 0;
+    if (t < 0 || t > 31 || T->ht_xlen[t] == 0) return false; // (4 and 14 do not exist)
+    if (t < 16) return m < (int) T->ht_xlen[t];
+    return m - 15 <= (int) T->ht_linmax[t];
+}
+
+// bits of the pair in table t (src/huffcode.h:16-139)
+static int fd_pair_bits(const mp3mi_tables *T, int t, int x, int y)
+{
+    if (t == 0) return 0;
+    const int lin = T->ht_linbits[t], ylen = T->ht_ylen[t];
+    int bits = (x != 0) + (y != 0);
+    if (t > 15) {
+        if (x > 14) { x = 15; bits += lin; }
+        if (y > 14) { y = 15; bits += lin; }
+    }
+    return bits + T->ht_len[T->ht_off[t] + x * ylen + y];
+}
+
+// one (granule, channel): 1 where it keeps every rule, scalefactor + code bits <= part2_3_length among them
+static int fd_check_granule(const mp3mi_tables *T, const mp3mi_gr_side *g, const int32_t scfsi[4], int gr, const int16_t *ix)
+{
+    if (g->part2_3_length < 0 || g->part2_3_length > 4095 || g->big_values < 0 || g->count1 < 0 ||
+        2 * g->big_values + 4 * g->count1 > 576 || g->global_gain < 0 || g->global_gain > 255 || g->scalefac_compress < 0 ||
+        g->scalefac_compress > 15 || (g->window_switching_flag & ~1) || (g->preflag & ~1) || (g->count1table_select & ~1))
+        return 0;
+    if (g->window_switching_flag ? (g->block_type < 1 || g->block_type > 3) : g->block_type != 0) return 0;
+    const bool shortb = g->window_switching_flag && g->block_type == 2;
+    const int slen1 = FD_SLEN1[g->scalefac_compress], slen2 = FD_SLEN2[g->scalefac_compress];
+    int part2 = 0;
+    if (shortb) {
+        for (int i = 0; i < 36; i++)
+            if (g->scalefac[i] < 0 || g->scalefac[i] >= (1 << (i < 18 ? slen1 : slen2))) return 0;
+        part2 = 18 * (slen1 + slen2);
+    } else {
+        for (int i = 0; i < 21; i++)
+            if (g->scalefac[i] < 0 || g->scalefac[i] >= (1 << (i < 11 ? slen1 : slen2))) return 0;
+        static const int n_band[4] = {6, 5, 5, 5};
+        for (int b = 0; b < 4; b++)
+            if (gr == 0 || scfsi[b] == 0) part2 += n_band[b] * (b < 2 ? slen1 : slen2);
+    }
+    if (g->part2_length != part2) return 0;
+    int bits = part2;
+    const int bigvalues = 2 * g->big_values;
+    if (shortb) { // src/loop.c:1493-1497 leaves (288, 0), or nothing at all
+        if (!((g->big_values == 288 || g->big_values == 0) && g->count1 == 0)) return 0;
+        if (g->big_values)
+            for (int sfb = 0; sfb < 13; sfb++) {
+                const int start = T->sfb_s[sfb], end = T->sfb_s[sfb + 1], t = start < 12 ? g->table_select[0] : g->table_select[1];
+                for (int w = 0; w < 3; w++)
+                    for (int line = start; line < end; line += 2) {
+                        const int x = fd_abs(ix[line * 3 + w]), y = fd_abs(ix[(line + 1) * 3 + w]);
+                        if (!fd_table_takes(T, t, x, y)) return 0;
+                        bits += fd_pair_bits(T, t, x, y);
+                    }
+            }
+    } else {
+        if (g->window_switching_flag ? (g->region0_count != 7 || g->region1_count != 13)
+                                     : (g->region0_count < 0 || g->region0_count > 15 || g->region1_count < 0 || g->region1_count > 7 ||
+                                        g->region0_count + g->region1_count + 2 > 22))
+            return 0;
+        const int r1s = T->sfb_l[g->region0_count + 1], r2s = T->sfb_l[g->region0_count + g->region1_count + 2];
+        for (int i = 0; i < bigvalues; i += 2) {
+            const int t = i < r1s ? g->table_select[0] : (i < r2s ? g->table_select[1] : g->table_select[2]);
+            const int x = fd_abs(ix[i]), y = fd_abs(ix[i + 1]);
+            if (!fd_table_takes(T, t, x, y)) return 0;
+            bits += fd_pair_bits(T, t, x, y);
+        }
+    }
+    const int c1end = bigvalues + 4 * g->count1, toff = T->ht_off[32 + g->count1table_select];
+    for (int i = bigvalues; i < c1end; i += 4) {
+        int p = 0;
+        for (int k = 0; k < 4; k++) {
+            const int q = fd_abs(ix[i + k]);
+            if (q > 1) return 0;
+            p |= q << k;
+            bits += q;
+        }
+        bits += T->ht_len[toff + p];
+    }
+    for (int i = c1end; i < 576; i++)
+        if (ix[i] != 0) return 0;
+    return bits <= g->part2_3_length; // the rest is stuffing
+}
+
+extern "C" int mp3mi_debug_format_frames(int rate_hz, int channels, int kbps, int hdr_mode, int hdr_flags, int crc, int n_streams,
+                                         int n_frames, const int32_t *n_frames_s, const int16_t *ix, const void *side_v,
+                                         uint8_t *out, size_t out_stride, uint32_t *out_len, int32_t *status)
+{
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return MP3MI_ERR_NO_DEVICE;
+    const mp3mi_frame_side *side = (const mp3mi_frame_side *) side_v;
+    const int ri = rate_hz == 44100 ? 0 : (rate_hz == 48000 ? 1 : (rate_hz == 32000 ? 2 : -1));
+    int bi = 1;
+    while (bi < 15 && FD_BITRATES[bi] != kbps) bi++;
+    if (ri < 0 || bi == 15 || (channels != 1 && channels != 2) || hdr_mode < 0 || hdr_mode > 3 || (channels == 1) != (hdr_mode == 3) ||
+        (hdr_flags & ~63) || (crc & ~1) || n_streams <= 0 || n_frames < 0 || !n_frames_s || !out_len || !status ||
+        (n_frames > 0 && (!ix || !side || !out)))
+        return MP3MI_ERR_ARG;
+    static const double s_freq[3] = {44.1, 48, 32}; // src/common.c:113, src/musicin.c:562-566
+    const int frame_bytes = (int) (((double) 1152 / s_freq[ri]) * ((double) kbps / 8.0));
+    const int si_bytes = 4 + 2 * crc + (channels == 2 ? 32 : 17), slot = frame_bytes - si_bytes;
+    if (slot <= 0 || out_stride < (size_t) n_frames * frame_bytes + 1) return MP3MI_ERR_ARG;
+    mp3mi_tables *Th = (mp3mi_tables *) malloc(sizeof(mp3mi_tables));
+    if (!Th) return MP3MI_ERR_NOMEM;
+    const int trc = mp3mi_build_tables(Th, ri);
+    if (trc != 0) {
+        free(Th);
+        return trc == -8 ? MP3MI_ERR_TABLES : MP3MI_ERR_ARG;
+    }
+    const int C = channels;
+    bool legal = true;
+    for (int s = 0; legal && s < n_streams; s++) {
+        if (n_frames_s[s] < 0 || n_frames_s[s] > n_frames) { legal = false; break; }
+        long mdb = 0; // the reservoir starts empty
+        for (int f = 0; legal && f < n_frames_s[s]; f++) {
+            const mp3mi_frame_side *sd = &side[(size_t) s * n_frames + f];
+            long bits = sd->resvDrain;
+            legal = sd->resvDrain >= 0 && sd->main_data_begin == mdb && mdb <= 511;
+            for (int gr = 0; legal && gr < 2; gr++)
+                for (int ch = 0; legal && ch < C; ch++) {
+                    for (int b = 0; b < 4; b++) legal = legal && !(sd->scfsi[ch][b] & ~1);
+                    const int16_t *q = ix + (((size_t) s * 2 * n_frames + (2 * f + gr)) * C + ch) * 576;
+                    legal = legal && fd_check_granule(Th, &sd->gr[gr][ch], sd->scfsi[ch], gr, q);
+                    bits += sd->gr[gr][ch].part2_3_length;
+                }
+            legal = legal && bits % 8 == 0 && bits <= FD_IMAGE_BITS && bits / 8 <= mdb + slot; // (data never passes its own slot's end)
+            mdb += slot - bits / 8;
+        }
+    }
+    if (!legal) {
+        free(Th);
+        return MP3MI_ERR_ARG;
+    }
+    const size_t S = (size_t) n_streams, nf = (size_t) n_frames;
+    mp3mi_tables *dT = NULL;
+    int16_t *dix = NULL;
+    mp3mi_frame_side *dside = NULL;
+    int32_t *dpar = NULL; // bits_per_frame, bitrate_index, n_samples, status: [4][S]
+    uint8_t *dout = NULL;
+    uint32_t *dlen = NULL;
+    int32_t *par = (int32_t *) calloc(4 * S, sizeof(int32_t));
+    int rc = par ? MP3MI_ERR_HIP : MP3MI_ERR_NOMEM;
+    for (size_t s = 0; par && s < S; s++) {
+        par[s] = 8 * frame_bytes;
+        par[S + s] = bi;
+        par[2 * S + s] = n_frames_s[s] * 1152;
+    }
+    if (par && hipMalloc((void **) &dT, sizeof(mp3mi_tables)) == hipSuccess && hipMalloc((void **) &dix, (S * nf * 2 * C * 576 + 1) * 2) == hipSuccess &&
+        hipMalloc((void **) &dside, (S * nf + 1) * sizeof(mp3mi_frame_side)) == hipSuccess && hipMalloc((void **) &dpar, 4 * S * 4) == hipSuccess &&
+        hipMalloc((void **) &dout, S * out_stride) == hipSuccess && hipMalloc((void **) &dlen, S * 4) == hipSuccess &&
+        hipMemcpy(dT, Th, sizeof(mp3mi_tables), hipMemcpyHostToDevice) == hipSuccess &&
+        hipMemcpy(dpar, par, 4 * S * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemset(dout, 0, S * out_stride) == hipSuccess &&
+        hipMemset(dlen, 0, S * 4) == hipSuccess &&
+        (nf == 0 || (hipMemcpy(dix, ix, S * nf * 2 * C * 576 * 2, hipMemcpyHostToDevice) == hipSuccess &&
+                     hipMemcpy(dside, side, S * nf * sizeof(mp3mi_frame_side), hipMemcpyHostToDevice) == hipSuccess))) {
+        // the whole-file geometry of a batch call (batch.cpp); a stream of no frames has no file body
+        mp3mi_geom g = mp3mi_make_geom(n_streams, C, ri, n_frames, 0, n_frames > 0 ? n_frames : 1);
+        g.hdr_mode = hdr_mode;
+        g.hdr_flags = hdr_flags;
+        g.crc = crc;
+        g.n_samples = dpar + 2 * S;
+        mp3mi_launch_format(dT, g, dix, dside, dpar, dpar + S, dout, out_stride, dlen, dpar + 3 * S, 1, (unsigned *) NULL, 0);
+        if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(out_len, dlen, S * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(status, dpar + 3 * S, S * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+            (nf == 0 || hipMemcpy(out, dout, S * out_stride, hipMemcpyDeviceToHost) == hipSuccess))
+            rc = MP3MI_OK;
+    }
+    if (dT) hipFree(dT);
+    if (dix) hipFree(dix);
+    if (dside) hipFree(dside);
+    if (dpar) hipFree(dpar);
+    if (dout) hipFree(dout);
+    if (dlen) hipFree(dlen);
+    free(par);
+    free(Th);
+    return rc;
+}

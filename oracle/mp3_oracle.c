@@ -89,6 +89,7 @@ typedef struct {
 struct mp3o_stream {
     int rate_idx, rate_hz, kbps, bitrate_index, channels, mode;
     int crc, copyright, original, emphasis; /* the driver's -e -c -o -d (src/musicin.c:263-275) */
+    int mode_ext;                           /* header field; the driver leaves 0 for Layer III, a caller of III_format_bitstream need not */
     int ref_abort;                          /* MP3O_ABORT_*: the reference would have died here (see mp3_oracle.h) */
     int bitsPerFrame, mean_bits;
     tables_t *T;
@@ -1467,7 +1468,7 @@ static void queue_side_info(mp3o_stream *s)
     bb_put(&b, 0, 1);                       /* padding: never (src/musicin.c:566-581) */
     bb_put(&b, 0, 1);                       /* extension: uninitialised in the reference, observed 0 */
     bb_put(&b, (unsigned) s->mode, 2);
-    bb_put(&b, 0, 2);                       /* mode_ext */
+    bb_put(&b, (unsigned) s->mode_ext, 2);  /* info->mode_ext, src/l3bitstream.c:331 */
     bb_put(&b, (unsigned) s->copyright, 1);
     bb_put(&b, (unsigned) s->original, 1);
     bb_put(&b, (unsigned) s->emphasis, 2);
@@ -1712,6 +1713,78 @@ int mp3o_quantize_count(int rate_hz, int n_gran, const double *xr_in, const int3
     }
     mp3o_close(s);
     return 0;
+}
+
+/* Test entry (tests/test_format_edges.py): a chain of given frames through format_frame() and mp3o_flush() above, as the frame
+ * loop calls them.  Each frame's main_data_begin is the one the formatter left behind (0 at the start), as with the reference. */
+size_t mp3o_format_frames(int rate_hz, int channels, int kbps, int mode, int mode_ext, int crc, int copyright, int original,
+                          int emphasis, int n_frames, const int32_t *side, const int16_t *ix, uint8_t **out, int32_t *mdb_after,
+                          int *ref_abort)
+{
+    enum { GR_WORDS = 15 + 39, FRAME_WORDS = 10 + 4 * GR_WORDS }; /* mp3mi_gr_side, mp3mi_frame_side (csrc/mp3mi_dev.h) */
+    static double xr[2][2][576];
+    mp3o_stream *s = mp3o_open(rate_hz, kbps, channels);
+    const uint8_t *p;
+    size_t len;
+    int f, gr, ch, i, w;
+    *out = NULL;
+    *ref_abort = 0;
+    if (!s || mode < 0 || mode > 3 || (channels == 1) != (mode == 3)) {
+        mp3o_close(s);
+        return 0;
+    }
+    s->mode = mode; s->mode_ext = mode_ext & 3; s->crc = crc != 0; s->copyright = copyright != 0; s->original = original != 0;
+    s->emphasis = emphasis & 3;
+    for (f = 0; f < n_frames; f++) {
+        const int32_t *fs = side + (size_t) f * FRAME_WORDS;
+        s->side.resvDrain = fs[1];
+        for (ch = 0; ch < 2; ch++)
+            for (i = 0; i < 4; i++) s->side.scfsi[ch][i] = (unsigned) fs[2 + 4 * ch + i];
+        for (gr = 0; gr < 2; gr++)
+            for (ch = 0; ch < channels; ch++) {
+                const int32_t *q = fs + 10 + (2 * gr + ch) * GR_WORDS;
+                const int16_t *v = ix + ((size_t) (2 * f + gr) * channels + ch) * 576;
+                gr_info_t *g = &s->side.gr[gr][ch];
+                memset(g, 0, sizeof(*g));
+                g->part2_3_length = (unsigned) q[0]; g->big_values = (unsigned) q[1]; g->count1 = (unsigned) q[2];
+                g->global_gain = (unsigned) q[3]; g->scalefac_compress = (unsigned) q[4]; g->window_switching_flag = (unsigned) q[5];
+                g->block_type = (unsigned) q[6];
+                g->table_select[0] = (unsigned) q[7]; g->table_select[1] = (unsigned) q[8]; g->table_select[2] = (unsigned) q[9];
+                g->region0_count = (unsigned) q[10]; g->region1_count = (unsigned) q[11]; g->preflag = (unsigned) q[12];
+                g->count1table_select = (unsigned) q[13]; g->part2_length = (unsigned) q[14];
+                gr_deco(g);
+                memset(s->scalefac_l[gr][ch], 0, sizeof(s->scalefac_l[gr][ch]));
+                memset(s->scalefac_s[gr][ch], 0, sizeof(s->scalefac_s[gr][ch]));
+                if (g->window_switching_flag && g->block_type == 2) {
+                    for (i = 0; i < 12; i++)
+                        for (w = 0; w < 3; w++) s->scalefac_s[gr][ch][i][w] = q[15 + 3 * i + w];
+                } else
+                    for (i = 0; i < 21; i++) s->scalefac_l[gr][ch][i] = q[15 + i];
+                for (i = 0; i < 576; i++) { /* magnitudes, and the signs where the formatter takes them from */
+                    s->l3_enc[gr][ch][i] = v[i] < 0 ? -v[i] : v[i];
+                    xr[gr][ch][i] = v[i] < 0 ? -1.0 : 1.0;
+                }
+            }
+        format_frame(s, xr);
+        mdb_after[f] = s->side.main_data_begin;
+    }
+    if (n_frames <= 0) { /* the driver's flush has nothing to flush: no file body */
+        *out = (uint8_t *) malloc(1);
+        mp3o_close(s);
+        return 0;
+    }
+    mp3o_flush(s);
+    if (s->ref_abort) {
+        *ref_abort = s->ref_abort | (n_frames << 8);
+        *out = (uint8_t *) malloc(1);
+        mp3o_close(s);
+        return 0;
+    }
+    p = mp3o_output(s, &len);
+    *out = (uint8_t *) malloc(len ? len : 1);
+    memcpy(*out, p, len);
+    mp3o_close(s);
+    return len;
 }
 
 mp3o_stream *mp3o_open(int rate_hz, int kbps, int channels)
