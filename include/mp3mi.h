@@ -187,6 +187,34 @@ int mp3mi_batch_encode_slots(mp3mi_batch *b, const int16_t *pcm_dev, int n_frame
                              const int32_t *n_samples_host, uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev);
 int mp3mi_batch_slot_frames(const mp3mi_batch *b, int64_t *frames_host);
 
+/* A bitrate per STREAM of a slot batch, chosen at its START: mp3mi_batch_encode_slots / mp3mi_batch_encode_slots_host_async with
+ * one more HOST array, copied before the call returns and indexed like ctl_host (by slot in the device call, by row in the host
+ * call).  kbps_host == NULL: exactly the calls without it, which are wrappers that pass NULL.
+ *   kbps_host[s], slot s STARTs   0: the slot's create-time bitrate (mp3mi_batch_create's kbps[s] / kbps_all).  Otherwise an MPEG-1
+ *                                 Layer III bitrate (32 .. 320, what mp3mi_batch_create accepts for the batch's rate and channel
+ *                                 count) that does not exceed the batch's CEILING: the largest bitrate the batch was created with.
+ *                                 That bitrate sizes the largest frame and with it mp3mi_batch_out_stride, so a server that takes
+ *                                 requests of every bitrate creates its batch with kbps_all = 320 and chooses per START.  The cost:
+ *                                 output rows -- and the host call's download, which moves whole rows -- are sized for the ceiling
+ *                                 whatever the streams' bitrates are.
+ *   kbps_host[s], no START        0, or, where a stream is open in the slot, the bitrate that stream has: a caller may pass one
+ *                                 persistent array call after call.
+ * Anything else returns MP3MI_ERR_ARG before anything is enqueued, and the batch is unchanged, like every other broken rule of a
+ * per-slot call.
+ * The bitrate belongs to the STREAM, not to the slot: it holds from the stream's START until the stream ends -- by END, by
+ * mp3mi_batch_flush, by mp3mi_batch_reset, abandoned by a new START in its slot, or by a whole-file, ragged or host whole-file
+ * call -- and afterwards the slot is back at its create-time bitrate.  Open streams keep their bitrates through every call that
+ * continues them: per-slot calls with ctl 0, mp3mi_batch_encode_next going on with the open slots (also once every slot is open
+ * at the same frame and the whole-batch bookkeeping has taken over), and the flush that ends them.  The calls that start EVERY
+ * stream afresh -- mp3mi_batch_encode, mp3mi_batch_encode_ragged, mp3mi_batch_encode_host_async and an mp3mi_batch_encode_next
+ * that starts every slot -- encode at the create-time bitrates, exactly as on a batch that never saw another one.
+ *   mp3mi_batch_slot_kbps   host-side only, no wait: kbps_host[s] = the bitrate of the stream open in slot s, the slot's
+ *                           create-time bitrate where none is.  Returns the batch's ceiling in kbps, or a negative MP3MI_ERR_*. */
+int mp3mi_batch_encode_slots_kbps(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, const uint8_t *ctl_host,
+                                  const int32_t *n_samples_host, const int32_t *kbps_host,
+                                  uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev);
+int mp3mi_batch_slot_kbps(const mp3mi_batch *b, int32_t *kbps_host);
+
 /* Ragged batch: stream s has n_samples_dev[s] valid samples per channel (0 <= n <= n_frames*1152) in
  * its row of pcm_dev (row pitch n_frames*1152*channels as above).  As the reference's get_audio /
  * read_samples do (/root/reference/src/encode.c:123-269, zero fill :162-166), the last partial frame
@@ -264,6 +292,10 @@ int mp3mi_batch_encode_host_async(mp3mi_batch *b, const int16_t *pcm_host, int n
 int mp3mi_batch_encode_slots_host_async(mp3mi_batch *b, const int16_t *pcm_host, int n_frames, int n_rows,
                                         const int32_t *row_slot_host, const uint8_t *ctl_host, const int32_t *n_samples_host,
                                         uint8_t *out_host, size_t out_stride, uint32_t *out_len_host);
+/* The same with a bitrate per row's stream, kbps_host[n_rows] (mp3mi_batch_encode_slots_kbps above: NULL is the call without it) */
+int mp3mi_batch_encode_slots_kbps_host_async(mp3mi_batch *b, const int16_t *pcm_host, int n_frames, int n_rows,
+                                  const int32_t *row_slot_host, const uint8_t *ctl_host, const int32_t *n_samples_host,
+                                  const int32_t *kbps_host, uint8_t *out_host, size_t out_stride, uint32_t *out_len_host);
 int mp3mi_batch_host_wait(mp3mi_batch *b, int calls_back);
 /* Bytes moved and time spent inside the copies (HIP events on the two copy streams) over all host-buffer calls since the
  * batch was created; waits for the calls issued so far. */

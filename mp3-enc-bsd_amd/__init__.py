@@ -93,8 +93,14 @@ def lib():
         L.mp3mi_batch_encode_slots.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         L.mp3mi_batch_slot_frames.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        L.mp3mi_batch_encode_slots_kbps.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        L.mp3mi_batch_slot_kbps.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.mp3mi_batch_encode_slots_host_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        L.mp3mi_batch_encode_slots_kbps_host_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                               ctypes.c_void_p]
         L.mp3mi_batch_host_wait.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.mp3mi_batch_set_mode.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.mp3mi_batch_set_error_protection.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -200,12 +206,15 @@ class Batch:
     def reset(self):
         self._check(self.L.mp3mi_batch_reset(self.h), "mp3mi_batch_reset")
 
-    def encode_slots(self, pcm, n_frames, out, out_len, start=None, end=None, n_samples=None):
+    def encode_slots(self, pcm, n_frames, out, out_len, start=None, end=None, n_samples=None, kbps=None):
         """Continuous batching (mp3mi_batch_encode_slots): every stream index is a slot in which one stream after another
         begins (start[s] true: with this call's first sample, from fresh state) and ends (end[s] true: this call holds its last
         n_samples[s] samples per channel).  start / end: boolean sequences of n_streams (None: all false); n_samples: an int
         sequence (None: a full call for every open or starting slot, 0 for the others).  Tensors as for encode_next; out /
-        out_len receive per slot the bytes of its file that became final with this call (0 for a closed slot)."""
+        out_len receive per slot the bytes of its file that became final with this call (0 for a closed slot).  kbps: an int
+        sequence, per slot the bitrate of the stream that STARTs there (0: the slot's create-time bitrate; at most the largest
+        bitrate the batch was created with) and 0 or the open stream's own bitrate elsewhere (mp3mi_batch_encode_slots_kbps);
+        None: the call without it."""
         import numpy as np
         assert pcm.is_cuda and out.is_cuda and out_len.is_cuda and pcm.is_contiguous() and out.is_contiguous()
         S = self.n_streams
@@ -215,12 +224,18 @@ class Batch:
         if end is not None:
             ctl |= np.asarray(end, dtype=bool).reshape(S).astype(np.uint8) * 2  # MP3MI_SLOT_END
         ns = None if n_samples is None else np.ascontiguousarray(n_samples, dtype=np.int32).reshape(S)
+        if kbps is not None:
+            kb = np.ascontiguousarray(kbps, dtype=np.int32).reshape(S)
+            self._check(self.L.mp3mi_batch_encode_slots_kbps(self.h, pcm.data_ptr(), n_frames, ctl.ctypes.data, None if ns is None else ns.ctypes.data,
+                                                             kb.ctypes.data, out.data_ptr(), out.shape[1], out_len.data_ptr()),
+                        "mp3mi_batch_encode_slots_kbps")
+            return
         self._check(self.L.mp3mi_batch_encode_slots(self.h, pcm.data_ptr(), n_frames, ctl.ctypes.data, None if ns is None else ns.ctypes.data,
                                                     out.data_ptr(), out.shape[1], out_len.data_ptr()), "mp3mi_batch_encode_slots")
 
-    def encode_slots_host(self, pcm, n_frames, out, out_len, rows=None, start=None, end=None, n_samples=None):
+    def encode_slots_host(self, pcm, n_frames, out, out_len, rows=None, start=None, end=None, n_samples=None, kbps=None):
         """Continuous batching on host buffers that hold a row per LIVE slot (mp3mi_batch_encode_slots_host_async): rows is the
-        strictly increasing sequence of the rows' slots (None: a row per slot), and start / end / n_samples are as for
+        strictly increasing sequence of the rows' slots (None: a row per slot), and start / end / n_samples / kbps are as for
         encode_slots but indexed by ROW.  pcm int16 [n_rows, n_frames*1152*C], out uint8 [n_rows, stride], out_len int32 or
         uint32 [n_rows]: CPU tensors (pinned ones overlap with the kernels) or numpy arrays, which must stay alive until the
         call's results have been waited for (host_wait, sync).  Only the rows cross PCIe."""
@@ -241,6 +256,12 @@ class Batch:
         if end is not None:
             ctl |= np.asarray(end, dtype=bool).reshape(R).astype(np.uint8) * 2  # MP3MI_SLOT_END
         ns = None if n_samples is None else np.ascontiguousarray(n_samples, dtype=np.int32).reshape(R)
+        if kbps is not None:
+            kb = np.ascontiguousarray(kbps, dtype=np.int32).reshape(R)
+            self._check(self.L.mp3mi_batch_encode_slots_kbps_host_async(self.h, ptr(pcm), n_frames, R, None if rows_a is None else rows_a.ctypes.data,
+                                                                        ctl.ctypes.data, None if ns is None else ns.ctypes.data, kb.ctypes.data,
+                                                                        ptr(out), out.shape[1], ptr(out_len)), "mp3mi_batch_encode_slots_kbps_host_async")
+            return
         self._check(self.L.mp3mi_batch_encode_slots_host_async(self.h, ptr(pcm), n_frames, R, None if rows_a is None else rows_a.ctypes.data,
                                                                ctl.ctypes.data, None if ns is None else ns.ctypes.data, ptr(out), out.shape[1],
                                                                ptr(out_len)), "mp3mi_batch_encode_slots_host_async")
@@ -258,6 +279,16 @@ class Batch:
         if rc < 0:
             raise Mp3miError("mp3mi_batch_slot_frames failed with %d" % rc)
         return f
+
+    def slot_kbps(self):
+        """(numpy int32 [n_streams]: the bitrate of the stream open in each slot, the slot's create-time bitrate where none is;
+        the batch's ceiling in kbps -- the largest bitrate a START may choose) (no device wait)"""
+        import numpy as np
+        k = np.zeros(self.n_streams, np.int32)
+        rc = self.L.mp3mi_batch_slot_kbps(self.h, k.ctypes.data)
+        if rc < 0:
+            raise Mp3miError("mp3mi_batch_slot_kbps failed with %d" % rc)
+        return k, rc
 
     def set_mode(self, mode):
         """0 stereo, 2 dual channel, 3 mono (the reference's -m s|d|m); joint stereo is refused as in the reference"""

@@ -40,8 +40,8 @@ size_t mp3mi_loop_state_size(void);
 struct mp3mi_batch {
     int device;              // the HIP device everything of this batch lives on (current at create time)
     int n_streams, rate_idx, rate_hz, channels, max_frames, chunk_frames;
-    std::vector<int> bits_per_frame_h, bitrate_index_h;
-    int max_frame_bytes;
+    std::vector<int> bits_per_frame_h, bitrate_index_h, kbps_h; // as created, per stream index
+    int max_frame_bytes, ceil_kbps; // of the largest bitrate the batch was created with: what the output rows are sized for
     hipStream_t stream;      // front stream: feed-forward kernels (and the initial memsets)
     hipStream_t lstream;     // loop stream: k_loop + k_format
     // A batch of more streams than k_loop holds resident is cut into PARTS (contiguous stream ranges); a part's frames of
@@ -77,7 +77,16 @@ struct mp3mi_batch {
     int crc;                 // error protection (-e): zero CRC word after the header, as the reference writes it
     int last_slot;
     mp3mi_tables *T;
-    int32_t *bits_per_frame, *bitrate_index;
+    // The LIVE bitrate arrays, [S] each, which k_loop, k_format and k_stream_tail read per stream (one allocation, rate_live: bits
+    // per frame | bitrate index), and the create-time values beside them (rate_create, same layout).  A per-slot call may START a
+    // stream at another bitrate (mp3mi_batch_encode_slots_kbps): k_slot_rate writes the live arrays, rates_restore copies the
+    // create-time ones back.  Both run on the LOOP stream only, and the host never writes the live arrays after create: every
+    // reader runs on the loop stream, so a write is in order behind the readers of the call before (a held k_loop among them) and
+    // ahead of the readers of the call that issued it.
+    int32_t *rate_live, *rate_create;
+    int32_t *bits_per_frame, *bitrate_index; // rate_live, rate_live + S
+    std::vector<int32_t> slot_kbps_h;  // the bitrate of the stream open in each slot; of a closed slot: kbps_h
+    bool rate_dirty;                   // the live arrays may differ from the create-time ones
     float *energy_l, *energy_s, *hist6, *fft_bins;
     double *cw_mid, *xr[2], *sbs, *sb_dbg, *part_eb;
     mp3mi_cw_fixlist *cw_fix; // the (granule, channel) records whose unpredictability needs its second tier (k_part)
@@ -101,11 +110,13 @@ struct mp3mi_batch {
     // every call runs the whole-batch path above; a per-slot call sets slots_on, and the slots are as slot_frames_h says.
     bool slots_on;
     std::vector<int64_t> slot_frames_h; // frames encoded by the stream open in each slot, -1: no stream open there
-    // the control block of a per-slot call -- fabs_s int64[S] | n_samples int32[S] | START list int32[S] | ctl uint8[S] -- in
+    // the control block of a per-slot call -- fabs_s int64[S] | n_samples int32[S] | START list int32[S] | ctl uint8[S] | (row map) |
+    // at ctl_rate_off, by position in the START list: bits per frame int32[S] | bitrate index int32[S] (k_slot_rate) -- in
     // pinned staging and on the device, twice (by the parity of the per-slot call: ctl_calls & 1); ev_ctl[p] is recorded behind the
     // last reader of copy p, and the host waits for it before it writes staging p again (the per-slot call two before)
     uint8_t *ctl_stage[2], *ctl_dev[2];
-    size_t ctl_bytes, ctl_rows_off; // (behind the four arrays, for host-buffer calls: row_slot int32[n_rows] at ctl_rows_off)
+    size_t ctl_bytes, ctl_rows_off, ctl_rate_off; // (behind the four arrays, for host-buffer calls: row_slot int32[n_rows] at ctl_rows_off)
+    size_t ctl_base_bytes;   // the block without the bitrates: all that goes up while no call writes the live bitrate arrays
     hipEvent_t ev_ctl[2], ev_ctl_up;
     bool ctl_used[2];
     unsigned ctl_calls;
@@ -173,6 +184,24 @@ struct device_scope {
     if (!dev_scope_.ok) { fprintf(stderr, "mp3mi: cannot select device %d\n", (b)->device); return MP3MI_ERR_HIP; }
 
 static const int BITRATES[15] = {0, 32, 40, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256, 320}; // src/common.c:124
+
+// What a bitrate means for a stream of sampling-frequency code ri: its index in the header and the frame's size, slots per frame
+// never padded (src/musicin.c:562-581).  False for anything but an MPEG-1 Layer III bitrate (src/common.c:118-125, 460-481) --
+// the check of mp3mi_batch_create_ex and of a per-slot call's kbps_host alike.
+static bool rate_of_kbps(int ri, int k, int *bitrate_index, int *bits_per_frame)
+{
+    static const double s_freq[3] = {44.1, 48, 32}; // src/common.c:113
+    int bi;
+    for (bi = 1; bi < 15; bi++)
+        if (BITRATES[bi] == k) break;
+    if (bi == 15 || ri < 0 || ri > 2) return false;
+    const int whole_SpF = (int) (((double) 1152 / s_freq[ri]) * ((double) k / 8.0));
+    *bitrate_index = bi;
+    *bits_per_frame = 8 * whole_SpF;
+    return true;
+}
+
+static int rate_idx_of(int rate_hz) { return rate_hz == 44100 ? 0 : rate_hz == 48000 ? 1 : rate_hz == 32000 ? 2 : -1; }
 
 static int have_device(void)
 {
@@ -247,31 +276,26 @@ extern "C" void mp3mi_batch_options_from_env(mp3mi_batch_options *o)
 static int batch_build(mp3mi_batch *b, int n_streams, int rate_hz, int channels, const int *kbps, int kbps_all, int max_frames,
                        const mp3mi_batch_options &opt)
 {
-    static const double s_freq[3] = {44.1, 48, 32}; // src/common.c:113
-    int ri;
-    if (rate_hz == 44100) ri = 0;
-    else if (rate_hz == 48000) ri = 1;
-    else if (rate_hz == 32000) ri = 2;
-    else return MP3MI_ERR_ARG; // the reference's L3psycho_anal exits on anything else (src/l3psy.c:170-176)
+    const int ri = rate_idx_of(rate_hz);
+    if (ri < 0) return MP3MI_ERR_ARG; // the reference's L3psycho_anal exits on anything else (src/l3psy.c:170-176)
     if (n_streams <= 0 || max_frames <= 0 || (channels != 1 && channels != 2)) return MP3MI_ERR_ARG;
     CHK(hipGetDevice(&b->device));
     b->n_streams = n_streams; b->rate_idx = ri; b->rate_hz = rate_hz; b->channels = channels;
     b->max_frames = max_frames; b->debug = 0; b->last_nf = 0;
     b->bits_per_frame_h.resize(n_streams);
     b->bitrate_index_h.resize(n_streams);
+    b->kbps_h.resize(n_streams);
     b->max_frame_bytes = 0;
+    b->ceil_kbps = 0;
     for (int s = 0; s < n_streams; s++) {
         const int k = kbps ? kbps[s] : kbps_all;
-        int bi;
-        for (bi = 1; bi < 15; bi++)
-            if (BITRATES[bi] == k) break;
-        if (bi == 15) return MP3MI_ERR_ARG;
-        // slots per frame, never padded (src/musicin.c:562-581)
-        const int whole_SpF = (int) (((double) 1152 / s_freq[ri]) * ((double) k / 8.0));
-        b->bitrate_index_h[s] = bi;
-        b->bits_per_frame_h[s] = 8 * whole_SpF;
-        if (whole_SpF > b->max_frame_bytes) b->max_frame_bytes = whole_SpF;
+        if (!rate_of_kbps(ri, k, &b->bitrate_index_h[s], &b->bits_per_frame_h[s])) return MP3MI_ERR_ARG;
+        b->kbps_h[s] = k;
+        if (k > b->ceil_kbps) b->ceil_kbps = k;
+        if (b->bits_per_frame_h[s] / 8 > b->max_frame_bytes) b->max_frame_bytes = b->bits_per_frame_h[s] / 8;
     }
+    b->slot_kbps_h.assign(b->kbps_h.begin(), b->kbps_h.end());
+    b->rate_dirty = false;
     // chunk size from a scratch budget (bytes per frame and stream of the per-chunk buffers)
     const size_t per_gc = MP3MI_HBLK_P * 4 + MP3MI_PART_P * 12 + 3 * MP3MI_HBLK_S * 4 + MP3MI_FFT_BINS * 4 + 50 * 8 + 12 * 4 +
                           2 * (sizeof(mp3mi_psy_out) + sizeof(mp3mi_loop_prep) + 576 * 8) + 576 * 8 + 576 * 2;
@@ -348,10 +372,14 @@ static int batch_build(mp3mi_batch *b, int n_streams, int rate_hz, int channels,
     }
     CHK(hipMalloc((void **) &b->T, sizeof(mp3mi_tables)));
     CHK(hipMemcpy(b->T, Th, sizeof(mp3mi_tables), hipMemcpyHostToDevice));
-    CHK(hipMalloc((void **) &b->bits_per_frame, sizeof(int32_t) * n_streams));
-    CHK(hipMalloc((void **) &b->bitrate_index, sizeof(int32_t) * n_streams));
-    CHK(hipMemcpy(b->bits_per_frame, b->bits_per_frame_h.data(), sizeof(int32_t) * n_streams, hipMemcpyHostToDevice));
-    CHK(hipMemcpy(b->bitrate_index, b->bitrate_index_h.data(), sizeof(int32_t) * n_streams, hipMemcpyHostToDevice));
+    CHK(hipMalloc((void **) &b->rate_live, 2 * sizeof(int32_t) * n_streams));
+    CHK(hipMalloc((void **) &b->rate_create, 2 * sizeof(int32_t) * n_streams));
+    b->bits_per_frame = b->rate_live;
+    b->bitrate_index = b->rate_live + n_streams;
+    for (int32_t *dst : {b->rate_live, b->rate_create}) {
+        CHK(hipMemcpy(dst, b->bits_per_frame_h.data(), sizeof(int32_t) * n_streams, hipMemcpyHostToDevice));
+        CHK(hipMemcpy(dst + n_streams, b->bitrate_index_h.data(), sizeof(int32_t) * n_streams, hipMemcpyHostToDevice));
+    }
     CHK(hipMalloc((void **) &b->energy_l, ngc * MP3MI_HBLK_P * sizeof(float)));
     CHK(hipMalloc((void **) &b->part_eb, ngc * MP3MI_PART_P * sizeof(double)));
 #if defined(MP3MI_ULP_CENSUS) // (diagnostic build: two shadow copies behind the sums, mp3mi_geom::census_cb_stride)
@@ -395,7 +423,9 @@ static int batch_build(mp3mi_batch *b, int n_streams, int rate_hz, int channels,
     b->slots_on = false;
     b->slot_frames_h.assign((size_t) n_streams, -1);
     b->ctl_rows_off = ((size_t) n_streams * 17 + 3) & ~(size_t) 3;
-    b->ctl_bytes = (b->ctl_rows_off + (size_t) n_streams * 4 + 255) & ~(size_t) 255;
+    b->ctl_rate_off = b->ctl_rows_off + (size_t) n_streams * 4;
+    b->ctl_base_bytes = (b->ctl_rate_off + 255) & ~(size_t) 255;
+    b->ctl_bytes = (b->ctl_rate_off + (size_t) n_streams * 8 + 255) & ~(size_t) 255;
     for (int i = 0; i < 2; i++) {
         CHK(hipHostMalloc((void **) &b->ctl_stage[i], b->ctl_bytes, 0));
         CHK(hipMalloc((void **) &b->ctl_dev[i], b->ctl_bytes));
@@ -444,11 +474,8 @@ extern "C" int mp3mi_batch_create_ex(mp3mi_batch **out, int n_streams, int rate_
     if (rate_hz != 44100 && rate_hz != 48000 && rate_hz != 32000) return MP3MI_ERR_ARG; // src/l3psy.c:170-176 exits on anything else
     if (n_streams <= 0 || max_frames <= 0 || (channels != 1 && channels != 2)) return MP3MI_ERR_ARG;
     for (int s = 0; s < n_streams; s++) {
-        const int k = kbps ? kbps[s] : kbps_all;
-        int bi;
-        for (bi = 1; bi < 15; bi++)
-            if (BITRATES[bi] == k) break;
-        if (bi == 15) return MP3MI_ERR_ARG;
+        int bi, bits;
+        if (!rate_of_kbps(rate_idx_of(rate_hz), kbps ? kbps[s] : kbps_all, &bi, &bits)) return MP3MI_ERR_ARG;
         if (!kbps) break;
     }
     if (!have_device()) {
@@ -472,7 +499,7 @@ extern "C" void mp3mi_batch_destroy(mp3mi_batch *b)
     hold_release(b);
     if (b->stream) hipStreamSynchronize(b->stream);
     if (b->lstream) hipStreamSynchronize(b->lstream);
-    void *bufs[] = {b->T, b->bits_per_frame, b->bitrate_index, b->energy_l, b->energy_s, b->hist6, b->fft_bins, b->cw_mid, b->cw_fix,
+    void *bufs[] = {b->T, b->rate_live, b->rate_create, b->energy_l, b->energy_s, b->hist6, b->fft_bins, b->cw_mid, b->cw_fix,
                     b->part_eb, b->part_cb, b->xr[0], b->xr[1], b->psy[0], b->psy[1], b->prep[0], b->prep[1], b->prep_fix, b->sbs, b->ix, b->side,
                     b->psy_state, b->loop_state, b->pcm_hist, b->out_base, b->carry, b->carry_len, b->gate_count, b->place_order, b->place_cost, b->place_zero, b->sb_dbg, b->voided, b->status_dev,
                     b->ctl_dev[0], b->ctl_dev[1]};
@@ -571,6 +598,8 @@ struct slot_call { // a per-slot call (mp3mi_batch_encode_slots): its control bl
     const int32_t *list;  // [n_start] the slots that START
     const uint8_t *ctl;   // [S] MP3MI_SLOT_DEV_* bits
     int n_start;
+    const int32_t *rate_bits; // [n_start] bits per frame, then at [S] the bitrate index, of the streams that START, by position in
+                              // `list`; NULL: the live bitrate arrays hold the create-time values and stay as they are
     bool any_continue;    // a stream that earlier calls began goes on in the call: its carried bytes lead its row
     int par;              // which copy of the control block
 };
@@ -596,11 +625,26 @@ static int harvest_timing(mp3mi_batch *b, int k)
     return MP3MI_OK;
 }
 
+// Every stream is over, or starts afresh: back to the create-time bitrates where a per-slot call has written others
+// (mp3mi_batch::rate_dirty).  On the LOOP stream, like every write of the live arrays: in order behind the last reader of the
+// streams that end -- the k_loop, k_format and k_stream_tail of the call before, which may still run there, held even -- and
+// ahead of every reader of the streams that begin.  (Not on the front stream, where the rest of a reset goes: the copy would
+// have to wait for ev_done, and ev_done to be recorded behind the last reader on every path that leads here.)
+static int rates_restore(mp3mi_batch *b)
+{
+    if (!b->rate_dirty) return MP3MI_OK;
+    CHK(hipMemcpyAsync(b->rate_live, b->rate_create, 2 * sizeof(int32_t) * (size_t) b->n_streams, hipMemcpyDeviceToDevice, b->lstream));
+    b->slot_kbps_h.assign(b->kbps_h.begin(), b->kbps_h.end());
+    b->rate_dirty = false;
+    return MP3MI_OK;
+}
+
 // Fresh encoder state for every stream: what the reference's function statics and the caller's buffers hold when
 // its main() starts (all zero).  Enqueued on the front stream behind whatever is still running.
 static int reset_impl(mp3mi_batch *b)
 {
     const int S = b->n_streams, C = b->channels;
+    if (rates_restore(b) != MP3MI_OK) return MP3MI_ERR_HIP;
     if (b->have_done) CHK(hipStreamWaitEvent(b->stream, b->ev_done, 0)); // the previous call's kernels may still be running on the loop stream
     CHK(hipMemsetAsync(b->psy_state, 0, mp3mi_psy_state_size() * (size_t) S * C, b->stream));
     CHK(hipMemsetAsync(b->loop_state, 0, mp3mi_loop_state_size() * (size_t) S, b->stream));
@@ -666,7 +710,8 @@ static int ctl_take(mp3mi_batch *b, int *par)
 }
 
 // The rules of a per-slot call, slot by slot (f: slot_frames_now)
-static bool slots_rules_ok(const mp3mi_batch *b, const int64_t *f, int n_frames, const uint8_t *ctl_host, const int32_t *n_samples_host)
+static bool slots_rules_ok(const mp3mi_batch *b, const int64_t *f, int n_frames, const uint8_t *ctl_host, const int32_t *n_samples_host,
+                           const int32_t *kbps_host)
 {
     const int32_t full = (int32_t) n_frames * 1152;
     for (int s = 0; s < b->n_streams; s++) {
@@ -676,13 +721,19 @@ static bool slots_rules_ok(const mp3mi_batch *b, const int64_t *f, int n_frames,
         if (end && !part) return false;
         const int32_t n = n_samples_host ? n_samples_host[s] : (part ? full : 0);
         if (!part ? n != 0 : (!end ? n != full : (n < 0 || n > full))) return false;
+        // the bitrate: a STARTing stream's own (0: the slot's create-time one), a Layer III bitrate that fits the rows; else 0, or
+        // what the open stream has
+        const int32_t k = kbps_host ? kbps_host[s] : 0;
+        int bi, bits;
+        if (start ? (k != 0 && (k > b->ceil_kbps || !rate_of_kbps(b->rate_idx, k, &bi, &bits))) : (k != 0 && !(open && k == b->slot_kbps_h[s])))
+            return false;
     }
     return true;
 }
 
 // ctl_host / n_samples_host are per SLOT; hc: the call's buffers are the host-buffer copies of hc->slot, and the caller's are hc's
 static int slots_impl(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, const uint8_t *ctl_host, const int32_t *n_samples_host,
-                      uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev, host_call *hc = NULL)
+                      const int32_t *kbps_host, uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev, host_call *hc = NULL)
 {
     if (!b || !pcm_dev || !ctl_host || !out_dev || !out_len_dev || n_frames <= 0 || n_frames > b->max_frames) return MP3MI_ERR_ARG;
     if (out_stride < (size_t) n_frames * (size_t) b->max_frame_bytes + 1 + MP3MI_CARRY_BYTES) return MP3MI_ERR_ARG;
@@ -691,7 +742,7 @@ static int slots_impl(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, cons
     std::vector<int64_t> f((size_t) S);
     slot_frames_now(b, f.data());
     // every rule first: a call that breaks one leaves the batch as it was
-    if (!slots_rules_ok(b, f.data(), n_frames, ctl_host, n_samples_host)) return MP3MI_ERR_ARG;
+    if (!slots_rules_ok(b, f.data(), n_frames, ctl_host, n_samples_host, kbps_host)) return MP3MI_ERR_ARG;
     ON_DEVICE(b);
     slot_call sc;
     if (ctl_take(b, &sc.par) != MP3MI_OK) return MP3MI_ERR_HIP;
@@ -703,6 +754,9 @@ static int slots_impl(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, cons
     int64_t *fabs = (int64_t *) blk;
     int32_t *ns = (int32_t *) (blk + 8 * (size_t) S), *list = (int32_t *) (blk + 12 * (size_t) S);
     uint8_t *ctl = blk + 16 * (size_t) S;
+    int32_t *rate_bits = (int32_t *) (blk + b->ctl_rate_off), *rate_index = rate_bits + S; // by position in the START list
+    std::vector<int32_t> kb(b->slot_kbps_h);
+    bool other_rate = false; // a stream STARTs at another bitrate than its slot was created with
     sc.n_start = 0;
     sc.any_continue = false;
     for (int s = 0; s < S; s++) {
@@ -712,9 +766,22 @@ static int slots_impl(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, cons
         ns[s] = n_samples_host ? n_samples_host[s] : (part ? full : 0);
         ctl[s] = (uint8_t) ((c & MP3MI_SLOT_START ? MP3MI_SLOT_DEV_START : 0) | (c & MP3MI_SLOT_END ? MP3MI_SLOT_DEV_END : 0) |
                             (part ? MP3MI_SLOT_DEV_ACTIVE : 0));
-        if (start) list[sc.n_start++] = s;
-        else if (open) sc.any_continue = true;
+        if (start) {
+            kb[s] = (kbps_host && kbps_host[s]) ? kbps_host[s] : b->kbps_h[s];
+            int bi = 0, bits = 0;
+            (void) rate_of_kbps(b->rate_idx, kb[s], &bi, &bits); // (checked: slots_rules_ok, create)
+            rate_bits[sc.n_start] = bits;
+            rate_index[sc.n_start] = bi;
+            other_rate |= kb[s] != b->kbps_h[s];
+            list[sc.n_start++] = s;
+        } else if (open)
+            sc.any_continue = true;
+        if (c & MP3MI_SLOT_END) kb[s] = b->kbps_h[s]; // the stream takes its bitrate with it
     }
+    // the START slots' bitrates go into the live arrays (encode_impl) once any slot of the batch may hold another than its
+    // create-time one -- a START with kbps 0, or without kbps_host, then brings its slot back; a batch that never saw another
+    // bitrate launches what it always launched
+    sc.rate_bits = (b->rate_dirty || other_rate) ? (const int32_t *) (b->ctl_dev[sc.par] + b->ctl_rate_off) : NULL;
     const uint8_t *dev = b->ctl_dev[sc.par];
     sc.fabs = (const int64_t *) dev;
     sc.ns = (const int32_t *) (dev + 8 * (size_t) S);
@@ -723,6 +790,8 @@ static int slots_impl(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, cons
     const int rc = encode_impl(b, pcm_dev, NULL, n_frames, out_dev, out_stride, out_len_dev, false, hc, &sc);
     if (rc != MP3MI_OK) return rc;
     b->ctl_calls++;
+    b->slot_kbps_h.swap(kb);
+    b->rate_dirty |= other_rate;
     for (int s = 0; s < S; s++) {
         const int c = ctl_host[s];
         if (c & MP3MI_SLOT_START) f[s] = 0;
@@ -735,10 +804,24 @@ static int slots_impl(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, cons
     return MP3MI_OK;
 }
 
+extern "C" int mp3mi_batch_encode_slots_kbps(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, const uint8_t *ctl_host,
+                                             const int32_t *n_samples_host, const int32_t *kbps_host, uint8_t *out_dev, size_t out_stride,
+                                             uint32_t *out_len_dev)
+{
+    return slots_impl(b, pcm_dev, n_frames, ctl_host, n_samples_host, kbps_host, out_dev, out_stride, out_len_dev);
+}
+
 extern "C" int mp3mi_batch_encode_slots(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, const uint8_t *ctl_host,
                                         const int32_t *n_samples_host, uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev)
 {
-    return slots_impl(b, pcm_dev, n_frames, ctl_host, n_samples_host, out_dev, out_stride, out_len_dev);
+    return mp3mi_batch_encode_slots_kbps(b, pcm_dev, n_frames, ctl_host, n_samples_host, NULL, out_dev, out_stride, out_len_dev);
+}
+
+extern "C" int mp3mi_batch_slot_kbps(const mp3mi_batch *b, int32_t *kbps_host)
+{
+    if (!b || !kbps_host) return MP3MI_ERR_ARG;
+    memcpy(kbps_host, b->slot_kbps_h.data(), sizeof(int32_t) * (size_t) b->n_streams);
+    return b->ceil_kbps;
 }
 
 extern "C" int mp3mi_batch_slot_frames(const mp3mi_batch *b, int64_t *frames_host)
@@ -760,7 +843,7 @@ extern "C" int mp3mi_batch_encode_next(mp3mi_batch *b, const int16_t *pcm_dev, i
         for (int s = 0; s < b->n_streams && !any; s++) any = b->slot_frames_h[s] >= 0;
         if (any) {
             std::vector<uint8_t> ctl((size_t) b->n_streams, 0);
-            return slots_impl(b, pcm_dev, n_frames, ctl.data(), NULL, out_dev, out_stride, out_len_dev);
+            return slots_impl(b, pcm_dev, n_frames, ctl.data(), NULL, NULL, out_dev, out_stride, out_len_dev);
         }
         if (!pcm_dev || !out_dev || !out_len_dev || n_frames <= 0 || n_frames > b->max_frames ||
             out_stride < (size_t) n_frames * (size_t) b->max_frame_bytes + 1 + MP3MI_CARRY_BYTES)
@@ -787,13 +870,13 @@ extern "C" int mp3mi_batch_flush(mp3mi_batch *b, uint8_t *out_dev, size_t out_st
         }
         if (ctl_take(b, &par) != MP3MI_OK) return MP3MI_ERR_HIP;
         uint8_t *blk = b->ctl_stage[par];
-        memset(blk, 0, b->ctl_bytes);
+        memset(blk, 0, b->ctl_base_bytes); // (k_stream_tail reads fabs_s and ctl only)
         for (int s = 0; s < S; s++) {
             const bool open = b->slot_frames_h[s] >= 0;
             ((int64_t *) blk)[s] = open ? b->slot_frames_h[s] : 0;
             blk[16 * (size_t) S + s] = open ? MP3MI_SLOT_DEV_ACTIVE : 0;
         }
-        CHK(hipMemcpyAsync(b->ctl_dev[par], blk, b->ctl_bytes, hipMemcpyHostToDevice, b->lstream));
+        CHK(hipMemcpyAsync(b->ctl_dev[par], blk, b->ctl_base_bytes, hipMemcpyHostToDevice, b->lstream));
         mp3mi_geom g = mp3mi_make_geom(S, b->channels, b->rate_idx, 0, 0, 0);
         g.crc = b->crc;
         g.fabs_s = (const int64_t *) b->ctl_dev[par];
@@ -857,6 +940,10 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         CHK(hipMemsetAsync(b->loop_state, 0, mp3mi_loop_state_size() * (size_t) S, b->lstream));
         CHK(hipMemsetAsync(b->out_base, 0, sizeof(int64_t) * (size_t) S, b->lstream));
         CHK(hipMemsetAsync(b->carry_len, 0, sizeof(int32_t) * (size_t) S, b->lstream));
+        // streams that per-slot calls began at bitrates of their own end here.  (The host mirror is reset with the copy's enqueue, not
+        // with the call's success: a HIP error further down leaves a call half enqueued, like any MP3MI_ERR_HIP of this function,
+        // and no entry point recovers a batch from that, so the mirror is not rolled back.)
+        if (rates_restore(b) != MP3MI_OK) return MP3MI_ERR_HIP;
         b->frames_done = 0;
     }
     // (a per-slot call: every slot has its own frame index, in the control block; k_loop counts the frame of a status from the
@@ -873,7 +960,9 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         // the control block goes up on the front stream, ahead of everything of the call that reads it; the START slots' state is
         // cleared on the stream that owns it: psy state and PCM history before the call's first transform, the loop state, the
         // file position and the carry length before carry_in and the call's first k_loop
-        CHK(hipMemcpyAsync(b->ctl_dev[sc->par], b->ctl_stage[sc->par], b->ctl_bytes, hipMemcpyHostToDevice, b->stream));
+        // (the bitrates behind it travel only where k_slot_rate will read them: otherwise the copy is the size it always had)
+        CHK(hipMemcpyAsync(b->ctl_dev[sc->par], b->ctl_stage[sc->par], sc->rate_bits ? b->ctl_bytes : b->ctl_base_bytes, hipMemcpyHostToDevice,
+                           b->stream));
         CHK(hipEventRecord(b->ev_ctl_up, b->stream));
         const mp3mi_slot_region none = {NULL, 0};
         mp3mi_launch_slot_begin(sc->list, sc->n_start, {b->psy_state, mp3mi_psy_state_size() * (size_t) C},
@@ -887,6 +976,10 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         mp3mi_launch_slot_begin(sc->list, sc->n_start, {b->loop_state, mp3mi_loop_state_size()}, {b->out_base, sizeof(int64_t)},
                                 {b->carry_len, sizeof(int32_t)}, b->lstream);
         CHK(hipGetLastError());
+        if (sc->rate_bits) { // ... and their bitrates: here, behind the readers of the call before and ahead of this call's first
+            mp3mi_launch_slot_rate(sc->list, sc->n_start, sc->rate_bits, sc->rate_bits + S, b->bits_per_frame, b->bitrate_index, b->lstream);
+            CHK(hipGetLastError());
+        }
     }
     if (!whole_file && (sc ? sc->any_continue : fabs0 > 0)) { // the bytes earlier calls formatted but could not deliver lead the rows
         mp3mi_launch_carry_in(S, b->carry, b->carry_len, out_dev, out_stride, b->lstream);
@@ -1414,9 +1507,9 @@ static int host_rows_init(mp3mi_batch *b, int sl, size_t out_stride)
 // mp3mi_batch_encode_slots with host buffers that hold a row per LIVE slot: the arrays by row become arrays by slot (a slot no
 // row names must be closed and stays so), the per-slot call's rules are checked on those, and the call runs as the per-slot
 // call on the host-buffer copies of the batch, with the row map between the dense rows and the rows per slot (encode_impl).
-extern "C" int mp3mi_batch_encode_slots_host_async(mp3mi_batch *b, const int16_t *pcm_host, int n_frames, int n_rows, const int32_t *row_slot_host,
-                                                   const uint8_t *ctl_host, const int32_t *n_samples_host, uint8_t *out_host, size_t out_stride,
-                                                   uint32_t *out_len_host)
+extern "C" int mp3mi_batch_encode_slots_kbps_host_async(mp3mi_batch *b, const int16_t *pcm_host, int n_frames, int n_rows, const int32_t *row_slot_host,
+                                                        const uint8_t *ctl_host, const int32_t *n_samples_host, const int32_t *kbps_host,
+                                                        uint8_t *out_host, size_t out_stride, uint32_t *out_len_host)
 {
     if (!b || !pcm_host || !ctl_host || !out_host || !out_len_host || n_frames <= 0 || n_frames > b->max_frames) return MP3MI_ERR_ARG;
     const int S = b->n_streams;
@@ -1425,12 +1518,13 @@ extern "C" int mp3mi_batch_encode_slots_host_async(mp3mi_batch *b, const int16_t
     std::vector<int64_t> f((size_t) S);
     slot_frames_now(b, f.data());
     std::vector<uint8_t> ctl_s;
-    std::vector<int32_t> ns_s;
+    std::vector<int32_t> ns_s, kbps_s;
     const uint8_t *ctl = ctl_host;
-    const int32_t *ns = n_samples_host;
+    const int32_t *ns = n_samples_host, *kbps = kbps_host;
     if (row_slot_host) {
         ctl_s.assign((size_t) S, 0);
         if (n_samples_host) ns_s.assign((size_t) S, 0);
+        if (kbps_host) kbps_s.assign((size_t) S, 0);
         std::vector<char> named((size_t) S, 0);
         for (int r = 0; r < n_rows; r++) {
             const int32_t s = row_slot_host[r];
@@ -1439,13 +1533,15 @@ extern "C" int mp3mi_batch_encode_slots_host_async(mp3mi_batch *b, const int16_t
             named[s] = 1;
             ctl_s[s] = ctl_host[r];
             if (n_samples_host) ns_s[s] = n_samples_host[r];
+            if (kbps_host) kbps_s[s] = kbps_host[r];
         }
         for (int s = 0; s < S; s++)
             if (f[s] >= 0 && !named[s]) return MP3MI_ERR_ARG; // an open stream goes on (or ends) in every call
         ctl = ctl_s.data();
         ns = n_samples_host ? ns_s.data() : NULL;
+        kbps = kbps_host ? kbps_s.data() : NULL;
     }
-    if (!slots_rules_ok(b, f.data(), n_frames, ctl, ns)) return MP3MI_ERR_ARG;
+    if (!slots_rules_ok(b, f.data(), n_frames, ctl, ns, kbps)) return MP3MI_ERR_ARG;
     ON_DEVICE(b);
     mp3mi_batch::host_io &H = b->hio;
     const int sl = (int) (H.call_no & 1);
@@ -1453,9 +1549,17 @@ extern "C" int mp3mi_batch_encode_slots_host_async(mp3mi_batch *b, const int16_t
     if (host_io_harvest(b, sl) != MP3MI_OK) return MP3MI_ERR_HIP; // (waits for the call two before this one: at most two in flight)
     if (row_slot_host && host_rows_init(b, sl, out_stride) != MP3MI_OK) return MP3MI_ERR_HIP;
     host_call hc = {pcm_host, out_host, out_stride, out_len_host, sl, n_rows, row_slot_host, NULL};
-    const int rc = slots_impl(b, H.pcm[sl], n_frames, ctl, ns, H.out[sl], H.out_stride, H.len[sl], &hc);
+    const int rc = slots_impl(b, H.pcm[sl], n_frames, ctl, ns, kbps, H.out[sl], H.out_stride, H.len[sl], &hc);
     if (rc == MP3MI_OK) H.call_no++; // (a call that failed took no slot)
     return rc;
+}
+
+extern "C" int mp3mi_batch_encode_slots_host_async(mp3mi_batch *b, const int16_t *pcm_host, int n_frames, int n_rows, const int32_t *row_slot_host,
+                                                   const uint8_t *ctl_host, const int32_t *n_samples_host, uint8_t *out_host, size_t out_stride,
+                                                   uint32_t *out_len_host)
+{
+    return mp3mi_batch_encode_slots_kbps_host_async(b, pcm_host, n_frames, n_rows, row_slot_host, ctl_host, n_samples_host, NULL, out_host,
+                                                    out_stride, out_len_host);
 }
 
 // Waits for the results of ONE host-buffer call: the latest (0) or the one before (1).  Only the call hold that very call left

@@ -542,6 +542,27 @@ void mp3mi_launch_slot_begin(const int32_t *list, int n_list, mp3mi_slot_region 
     hipLaunchKernelGGL(k_slot_begin, dim3((unsigned) n_list), dim3(256), 0, st, list, r0, r1, r2);
 }
 
+// The bitrate of the streams a call STARTs (mp3mi_batch_encode_slots_kbps): lane i puts the frame size in bits and the header's
+// bitrate index of the i-th listed slot -- computed on the host, in the call's control block -- into the live arrays that k_loop,
+// k_format and k_stream_tail read per stream.  On the loop stream only, where every reader runs (batch.cpp).
+__global__ void __launch_bounds__(64) k_slot_rate(const int32_t *__restrict__ list, int n_list, const int32_t *__restrict__ bits,
+                                                  const int32_t *__restrict__ index, int32_t *__restrict__ bits_per_frame,
+                                                  int32_t *__restrict__ bitrate_index)
+{
+    const int i = (int) (blockIdx.x * 64 + threadIdx.x);
+    if (i >= n_list) return;
+    const int s = list[i];
+    bits_per_frame[s] = bits[i];
+    bitrate_index[s] = index[i];
+}
+
+void mp3mi_launch_slot_rate(const int32_t *list, int n_list, const int32_t *bits, const int32_t *index, int32_t *bits_per_frame,
+                            int32_t *bitrate_index, hipStream_t st)
+{
+    if (n_list <= 0) return;
+    hipLaunchKernelGGL(k_slot_rate, dim3((unsigned) ((n_list + 63) / 64)), dim3(64), 0, st, list, n_list, bits, index, bits_per_frame, bitrate_index);
+}
+
 // ---- per-slot streaming on host buffers (mp3mi_batch_encode_slots_host_async) ----
 // The caller's buffers hold one ROW per live slot, dense; the encoder's kernels read and write one row per SLOT.  Two bandwidth
 // kernels sit between the copies and the encoder: both move 16 bytes per lane and access (one wavefront-instruction = 1 KiB,

@@ -141,6 +141,10 @@ void mp3mi_launch_stream_tail(const mp3mi_geom &g, int flush, int32_t *loop_stat
 struct mp3mi_slot_region { void *base; size_t bytes; };
 void mp3mi_launch_slot_begin(const int32_t *list, int n_list, mp3mi_slot_region r0, mp3mi_slot_region r1, mp3mi_slot_region r2,
                              hipStream_t st);
+/* k_slot_rate: bits_per_frame[list[i]] = bits[i], bitrate_index[list[i]] = index[i] for the n_list listed slots (the bitrates of the
+   streams a call STARTs; list values are slots of the two live arrays, checked on the host) */
+void mp3mi_launch_slot_rate(const int32_t *list, int n_list, const int32_t *bits, const int32_t *index, int32_t *bits_per_frame,
+                            int32_t *bitrate_index, hipStream_t st);
 /* per-slot streaming on host buffers: dense rows (one per live slot, row_slot[r] = its slot) to and from the rows per slot.
    k_rows_in: bytes [col0, col0 + width) of every dense PCM row into the same columns of its slot's row (all multiples of 16);
    k_rows_out: out_len[slot] bytes of every listed slot's output row and the length into dense rows of dense_stride, rest zeroed */

@@ -8,6 +8,9 @@
                                                    many closed slots START
 Prints one JSON line: ms per call of each case and the library's source hash.
 
+--mixed-kbps: the batch is created at 320 kbps and every START of (b) and (c) draws its stream's bitrate from 64 / 128 / 192 / 320
+(mp3mi_batch_encode_slots_kbps; seeded); (a) runs at the create-time 320.  The line also carries the mean bitrate of (b)'s streams.
+
 --host [--occupancy F]: the per-slot cases on PAGE-LOCKED HOST buffers (mp3mi_batch_encode_slots_host_async; ticks issued back
 to back, tick t collected with mp3mi_batch_host_wait(1) after tick t + 1 has been issued), with a fraction F of the slots live
 (the others stay closed; with F < 1, or with --map, the rows go through a row map, so only the live rows cross PCIe):
@@ -18,7 +21,7 @@ to back, tick t collected with mp3mi_batch_host_wait(1) after tick t + 1 has bee
   (g) host_churn          the host call; in every tick 1/32 of the live slots END and as many closed ones START, so the row
                           set changes from tick to tick
 
-usage: slots_bench.py [--calls 20] [--frames 32] [--streams 4096] [--reps 3] [--host [--occupancy 1.0] [--map]]"""
+usage: slots_bench.py [--calls 20] [--frames 32] [--streams 4096] [--reps 3] [--mixed-kbps] [--host [--occupancy 1.0] [--map]]"""
 import argparse
 import importlib
 import json
@@ -37,15 +40,18 @@ def main():
     ap.add_argument("--frames", type=int, default=32)
     ap.add_argument("--streams", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=3, help="runs of every case; the fastest counts")
+    ap.add_argument("--mixed-kbps", action="store_true", help="a batch created at 320 kbps; every START draws 64 / 128 / 192 / 320")
     ap.add_argument("--host", action="store_true", help="the per-slot cases on page-locked host buffers")
     ap.add_argument("--occupancy", type=float, default=1.0, help="--host: fraction of the slots that are live")
     ap.add_argument("--map", action="store_true", help="--host: a row map at occupancy 1.0 too (k_rows_in / k_rows_out run)")
     a = ap.parse_args()
     if a.host:
+        if a.mixed_kbps:
+            ap.error("--mixed-kbps times the resident cases (without --host)")
         return host_main(a)
     import torch
     mp3 = importlib.import_module("mp3-enc-bsd_amd")
-    S, nf, rate, ch, kbps = a.streams, a.frames, 44100, 2, 128
+    S, nf, rate, ch, kbps = a.streams, a.frames, 44100, 2, 320 if a.mixed_kbps else 128
     full = nf * 1152
     dev = torch.device("cuda:0")
     pcm = torch.empty((S, full * ch), dtype=torch.int16, device=dev)
@@ -57,18 +63,26 @@ def main():
     torch.cuda.synchronize()
     rng = np.random.default_rng(1)
     every = np.ones(S, bool)
+    rates = np.array([64, 128, 192, 320], np.int32)
+    drawn = []  # the bitrates of run_continue's streams
+
+    def draw(start):
+        """kbps of a call: a drawn bitrate for every START (None without --mixed-kbps: the call without the array)"""
+        return np.where(start, rates[rng.integers(0, 4, S)], 0).astype(np.int32) if a.mixed_kbps else None
 
     def run_next():
         for _ in range(a.calls):
             b.encode_next(pcm, nf, out, out_len)
 
     def run_continue():
-        b.encode_slots(pcm, nf, out, out_len, start=every)
+        kb = draw(every)
+        drawn[:] = [] if kb is None else [kb]
+        b.encode_slots(pcm, nf, out, out_len, start=every, kbps=kb)
         for _ in range(a.calls - 1):
             b.encode_slots(pcm, nf, out, out_len)
 
     def run_churn():
-        b.encode_slots(pcm, nf, out, out_len, start=every)
+        b.encode_slots(pcm, nf, out, out_len, start=every, kbps=draw(every))
         closed = np.zeros(S, bool)
         for _ in range(a.calls - 1):
             start = closed.copy()
@@ -77,7 +91,7 @@ def main():
             end[rng.choice(cand, S // 32, replace=False)] = True
             ns = np.full(S, full, np.int32)
             ns[end] = rng.integers(0, full + 1, int(end.sum()))
-            b.encode_slots(pcm, nf, out, out_len, start=start, end=end, n_samples=ns)
+            b.encode_slots(pcm, nf, out, out_len, start=start, end=end, n_samples=ns, kbps=draw(start))
             closed = end
 
     cases = (("encode_next", run_next), ("slots_continue", run_continue), ("slots_churn", run_churn))
@@ -97,7 +111,8 @@ def main():
         res[name] = round(best, 3)
     b.close()
     print(json.dumps({"tool": "slots_bench", "streams": S, "frames_per_call": nf, "calls": a.calls, "rate": rate, "channels": ch,
-                      "kbps": kbps, "ms_per_call": res,
+                      "kbps": kbps, "mixed_kbps": bool(a.mixed_kbps), "mean_kbps_continue": round(float(drawn[0].mean()), 1) if drawn else kbps,
+                      "ms_per_call": res,
                       "continue_vs_next": round(res["slots_continue"] / res["encode_next"], 4),
                       "churn_vs_continue": round(res["slots_churn"] / res["slots_continue"], 4),
                       "source_hash": mp3.lib().mp3mi_source_hash().decode()}))
