@@ -325,8 +325,8 @@ int mp3mi_encode_host_ex(int n_streams, int rate_hz, int channels, const int *kb
  * compare them with oracle/stage_dump.h).  what: 0 = psychoacoustic records (mp3mi_psy_out),
  * 1 = xr (f64[576] per granule-channel), 2 = quantised values (int16[576]), 3 = side info
  * (mp3mi_frame_side per frame), 4 = raw subband samples (f64[576], enabled by
- * mp3mi_batch_debug_enable), 5 = the loop's stateless head (csrc/mp3mi_dev.h: mp3mi_loop_prep, 472 bytes per
- * granule-channel); the psychoacoustic transforms' outputs (src/subs.c:38-123): 6 = long energies (f32, rows of 544
+ * mp3mi_batch_debug_enable), 5 = the loop's stateless head (csrc/mp3mi_dev.h: the first 472 bytes of mp3mi_loop_prep
+ * per granule-channel); the psychoacoustic transforms' outputs (src/subs.c:38-123): 6 = long energies (f32, rows of 544
  * per granule-channel: lines 0..512, the rest padding), 7 = short energies (f32[3][129]), 8 = raw lines (f32[312]:
  * (re, im) of short lines 2..51 of the three windows, then re[6], im[6] of long lines 0..5).  Returns the number of
  * bytes written, or a negative error. */
@@ -384,6 +384,10 @@ enum {
 };
 int mp3mi_debug_quantize_count(int rate_hz, int n_gran, const double *xr, const int32_t *gran, int16_t *ix, double *xr_out,
                                int32_t *fields);
+/* Self-test hook: the peak lines of n_gran granules of 576 xr each, as k_mdct's tail records them for k_loop's region maxima
+ * (csrc/mp3mi_dev.h, peak cells): peak[32 i + c] = a line of cell c of granule i with the largest |xr|; cell_first[33]: the cells'
+ * first lines and, last, 576.  MP3MI_ERR_NO_DEVICE without a GPU. */
+int mp3mi_debug_peak_lines(int rate_hz, int n_gran, const double *xr, uint16_t *peak, int32_t *cell_first);
 /* Self-test hook: k_format (csrc/k_format.hip), as a whole-file batch call launches it, on n_streams chains of GIVEN frames of one
  * format: rate_hz, channels, kbps, the header's mode field (0 stereo, 1 joint, 2 dual, 3 mono) and hdr_flags (mode_ext << 4 |
  * copyright << 3 | original << 2 | emphasis), crc (error protection).  Chain s has n_frames_s[s] <= n_frames frames; ix holds

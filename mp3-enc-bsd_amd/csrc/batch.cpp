@@ -18,6 +18,7 @@
 //
 // Mirrors the Layer III case of the reference's frame loop (src/musicin.c:708-788) for every
 // stream at once.  No CPU fallback: every entry point returns an error when HIP cannot run.
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -224,6 +225,7 @@ extern "C" const char *mp3mi_version(void)
 #endif
 }
 
+static_assert(offsetof(mp3mi_loop_prep, peak) == MP3MI_LOOP_PREP_HEAD, "mp3mi_batch_debug_fetch hands out the head of a prep record");
 static_assert((int) MP3MI_STREAM_ABORT_GLOBAL_GAIN == MP3MI_DEV_ABORT_GLOBAL_GAIN && (int) MP3MI_STREAM_ABORT_HUFF_BITS == MP3MI_DEV_ABORT_HUFF_BITS &&
                   (int) MP3MI_STREAM_ABORT_FLUSH_SLOT == MP3MI_DEV_ABORT_FLUSH_SLOT,
               "status codes of mp3mi.h and mp3mi_dev.h");
@@ -1405,7 +1407,7 @@ extern "C" long mp3mi_batch_debug_fetch(mp3mi_batch *b, int what, void *host_dst
     case 2: src = b->ix; n = ngc * 576 * sizeof(int16_t); break;
     case 3: src = b->side; n = (size_t) b->n_streams * (size_t) b->last_nf * sizeof(mp3mi_frame_side); break;
     case 4: src = b->sb_dbg; n = ngc * 576 * sizeof(double); break;
-    case 5: src = b->prep[b->last_slot]; n = ngc * sizeof(mp3mi_loop_prep); break;
+    case 5: src = b->prep[b->last_slot]; n = ngc * MP3MI_LOOP_PREP_HEAD; break;
     // the transforms' outputs as k_fft hands them to k_cw / k_part / k_psy (the direct FFT seam: oracle/fft_seam.h)
     case 6: src = b->energy_l; n = ngc * MP3MI_HBLK_P * sizeof(float); break;
     case 7: src = b->energy_s; n = ngc * 3 * MP3MI_HBLK_S * sizeof(float); break;
@@ -1416,6 +1418,14 @@ extern "C" long mp3mi_batch_debug_fetch(mp3mi_batch *b, int what, void *host_dst
     ON_DEVICE(b);
     hold_release(b);
     if (hipStreamSynchronize(b->stream) != hipSuccess || hipStreamSynchronize(b->lstream) != hipSuccess) return MP3MI_ERR_HIP;
+    if (what == 5) { // the records' heads, side by side (what follows the head is k_loop's alone: mp3mi_dev.h)
+        char *tmp = (char *) malloc(ngc * sizeof(mp3mi_loop_prep));
+        if (!tmp) return MP3MI_ERR_NOMEM;
+        const bool ok = hipMemcpy(tmp, src, ngc * sizeof(mp3mi_loop_prep), hipMemcpyDeviceToHost) == hipSuccess;
+        for (size_t i = 0; ok && i < ngc; i++) memcpy((char *) host_dst + i * MP3MI_LOOP_PREP_HEAD, tmp + i * sizeof(mp3mi_loop_prep), MP3MI_LOOP_PREP_HEAD);
+        free(tmp);
+        return ok ? (long) n : MP3MI_ERR_HIP;
+    }
     if (hipMemcpy(host_dst, src, n, hipMemcpyDeviceToHost) != hipSuccess) return MP3MI_ERR_HIP;
     return (long) n;
 }

@@ -471,6 +471,19 @@ __device__ __attribute__((noinline)) void mdct_prep_tail(const mp3mi_tables *T, 
     if (band == 0 && wr && ((am >> (32 * h)) & 0xffffffffull) != 0) fix->list[atomicAdd(&fix->count, 1u)] = rec;
 }
 
+// The peak lines of a long / start / stop granule (mp3mi_dev.h, peak cells): what lets k_loop take a region's largest quantised value
+// from one line per cell, pass after pass.  Lane & 31 = cell, its first line and lines from the caller (mp3mi_peak_cell, once a
+// kernel); WP: the longest cell.  A walk of its own behind the head's, not a compare beside its energy chains: there it took the
+// head's function past the registers k_mdct can have beside k_loop -- and a walk over cells of at most 32 lines is four steps where
+// the chains (a band each) take up to thirteen.  Not part of what k_prep recomputes for a listed record: nothing here is a matter of rounding.
+__device__ __attribute__((noinline)) void mdct_peak_tail(MDCT_LDS_PTR(const double) X, bool wr, int first, int lines, int WP, mp3mi_loop_prep *out)
+{
+    const int cell = wave_lane() & 31, h = wave_lane() >> 5;
+    MDCT_LDS_PTR(const double) Z = X + (MDCT_ZERO - 576 * h);
+    const int at = mp3mi_cell_peak(X + first, Z, lines, WP);
+    if (wr) out->peak[cell] = (uint16_t) (first + at);
+}
+
 // Diagnostic build only (-DMP3MI_MDCT_PROFILE, tools/mdct_profile.py): a wavefront's cycles per phase, summed over all of them
 #if defined(MP3MI_MDCT_PROFILE) && !defined(MP3MI_EMU)
 __device__ unsigned long long g_mdct_prof[8];
@@ -521,8 +534,10 @@ __global__ void __launch_bounds__(64, 3) k_mdct(const mp3mi_tables *__restrict__
     for (int k = 0; k < 18; k++) prev[64 * k] = blk[32 * k]; // the run's first "previous granule"
     if (lane < 8) L.zero[lane] = 0.0;
     // the longest band-energy chains, long and short (lane & 31 = scalefactor band)
-    int WL = 0, WS = 0;
+    int WL = 0, WS = 0, WP = 0, pc_first = 576, pc_lines = 0; // (pc_*: this lane's peak cell)
     if (prep) {
+        mp3mi_peak_cell(T->sfb_l, band, &pc_first, &pc_lines);
+        WP = wave_max_i32(pc_lines);
         WL = wave_max_i32(band < 21 ? T->sfb_l[band + 1] - T->sfb_l[band] : 0);
         WS = wave_max_i32(band < 12 ? T->sfb_s[band + 1] - T->sfb_s[band] : 0);
     }
@@ -581,9 +596,11 @@ __global__ void __launch_bounds__(64, 3) k_mdct(const mp3mi_tables *__restrict__
         MDCT_PROF(3);
         // ---- the loop's stateless head for these two granules (see above); BEFORE the spectrum's stores: a function
         //      begins by waiting for every memory operation in flight ----
-        if (prep)
+        if (prep) {
             mdct_prep_tail(T, (MDCT_LDS_PTR(const double)) &L.x[h][0], h == 0 || two, bt, bt0 != 2 || bt1 != 2, bt0 == 2 || bt1 == 2, WL, WS, (geo.test_flags & 32) != 0,
                            &psy[rec0 + (size_t) kk * C], &prep[rec0 + (size_t) kk * C], fix, (unsigned) (rec0 + (size_t) kk * C));
+            if (bt0 != 2 || bt1 != 2) mdct_peak_tail((MDCT_LDS_PTR(const double)) &L.x[h][0], (h == 0 || two) && bt != 2, pc_first, pc_lines, WP, &prep[rec0 + (size_t) kk * C]);
+        }
         MDCT_PROF(4);
         // element lane + 64 j of the two [band][18] blocks: j < 9 the lower track's, then the upper one's
         double *out_lo = xr_out + (rec_lo + (size_t) kk * C) * 576, *out_hi = xr_out + (rec_hi + (size_t) kk * C) * 576;
@@ -627,6 +644,9 @@ __global__ void __launch_bounds__(64) k_prep_tail(const mp3mi_tables *__restrict
     const size_t rec = h ? r1 : r0;
     mdct_prep_tail(T, (MDCT_LDS_PTR(const double)) &L.x[h][0], h == 0 || two, h ? bt1 : bt0, bt0 != 2 || bt1 != 2, bt0 == 2 || bt1 == 2, WL, WS, false,
                    &psy[rec], &prep[rec], fix, (unsigned) rec);
+    int pc_first, pc_lines;
+    mp3mi_peak_cell(T->sfb_l, band, &pc_first, &pc_lines);
+    mdct_peak_tail((MDCT_LDS_PTR(const double)) &L.x[h][0], (h == 0 || two) && (h ? bt1 : bt0) != 2, pc_first, pc_lines, wave_max_i32(pc_lines), &prep[rec]);
 }
 
 void mp3mi_launch_prep_tail(const mp3mi_tables *T, const mp3mi_geom &g, const double *xr, const mp3mi_psy_out *psy, mp3mi_loop_prep *prep,

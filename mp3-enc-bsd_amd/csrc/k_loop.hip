@@ -24,7 +24,7 @@
 // read with v_readlane; per-line Huffman code lengths sit in LDS; the quantiser boundary table
 // and i^(4/3) are read through L1/L2.
 //
-// HBM per (granule, channel): 4608 B xr in, 472 B psy record and 472 B prep record in, 1152 B ix out,
+// HBM per (granule, channel): 4608 B xr in, 472 B psy record and 536 B prep record in, 1152 B ix out,
 // ~54 words of side information out.
 #include "mp3mi_host.h"
 #include "dmath.h"
@@ -45,8 +45,8 @@ struct loop_gr { // wave-uniform working copy of gr_info (src/l3side.h:60-87)
     int sfb_lmax, sfb_smax, address1, address2, address3, q;
 };
 
-// 7.6 KB per wavefront plus one 1.9 KB copy of the code-length tables per workgroup of LOOP_W = 4 wavefronts: the 16
-// wavefronts per CU that 4096 streams on 256 CUs need take 129 KB of its 160 KB of LDS, and at 80 VGPRs 320 of a SIMD's
+// 7.7 KB per wavefront plus one 1.9 KB copy of the code-length tables per workgroup of LOOP_W = 4 wavefronts: the 16
+// wavefronts per CU that 4096 streams on 256 CUs need take 131 KB of its 160 KB of LDS (k_filter's three workgroups of 8.7 KB fit beside them), and at 80 VGPRs 320 of a SIMD's
 // 512 registers -- the feed-forward kernels of the next chunk find room beside them (batch.cpp).
 struct loop_lds {
     double xr[576 + 2] __attribute__((aligned(16))); // the granule's spectrum (amplified in place; [576] = [577] = 0: the pair a finished noise job
@@ -61,6 +61,9 @@ struct loop_lds {
     int band_sf[36];      // scalefactors of the iteration in progress
     int band_sfsave[36];  // and of the last iteration whose result stands (src/loop.c:505-519)
     mp3mi_loop_state st;
+    // long / start / stop blocks, lane < 32: the peak line of cell `lane` -- the line of the cell whose quantised value is the cell's largest
+    // in every pass (mp3mi_dev.h, peak cells; loop_count_bits); lanes 32..63: 1024 | lane & 1 (loop_stream sets them once)
+    uint16_t peak[64];
     // of the frame's side information only what a later granule or the end of the frame reads back; the records
     // themselves go straight to memory
     int p23[2][2];      // part2_3_length (ResvFrameEnd adds the stuffing bits, src/reservoir.c:190-224)
@@ -619,35 +622,57 @@ MP3MI_DEVFN int loop_count_bits(const mp3mi_tables *T, const loop_regs &R, loop_
     // (the addresses may come out of LDS: make their uniformity explicit, they bound the loops below)
     const int a1 = __builtin_amdgcn_readfirstlane(g.address1), a2 = __builtin_amdgcn_readfirstlane(g.address2);
     const int e2 = __builtin_amdgcn_readfirstlane(2 * g.big_values);
-    // Region 0 = lines [0, a1), 1 = [a1, a2), 2 = [a2, e2).  Each region is walked on its own, 64
-    // consecutive lines (32 pairs: one word each) per step straight out of L.ix, so a line is visited once,
-    // by the region it belongs to, with that region's wave-uniform descriptor; lines from slot nslot on are
-    // zero.  (Written out per region: arrays indexed by the region would live in scratch memory.)
-    const int nzend = 64 * nslot;
-    auto region_max = [&](int lo, int hi) {        hi = hi < nzend ? hi : nzend; // both even
-        mp3mi_u16x2 m = {0, 0}; // the maxima of the x and of the y of this lane's pairs: one packed instruction a step
-        const unsigned *p = ixw + (lo >> 1) + lane;
-        const int span = hi > lo ? hi - lo : 0, nfull = span >> 7, rest = (span & 127) >> 1; // whole steps of 64 pairs (nothing to mask), and a last one
-        if (nfull > 0) {
-            m = LOOP_PK_MAX_U16(m, __builtin_bit_cast(mp3mi_u16x2, p[0]));
-            if (nfull > 1) {
-                m = LOOP_PK_MAX_U16(m, __builtin_bit_cast(mp3mi_u16x2, p[64]));
-                if (nfull > 2) {
-                    m = LOOP_PK_MAX_U16(m, __builtin_bit_cast(mp3mi_u16x2, p[128]));
-                    if (nfull > 3) m = LOOP_PK_MAX_U16(m, __builtin_bit_cast(mp3mi_u16x2, p[192]));
+    // Region 0 = lines [0, a1), 1 = [a1, a2), 2 = [a2, e2).
+    int red[4]; // the count1 region's two bit sums and the three region maxima: four reductions in lock-step
+    red[0] = c1part;
+    // The maxima.  subdivide has just set the addresses (big_values > 0) to band edges with a1 <= a2 <= e2 -- or to [0, sfb_l[8]) and
+    // [sfb_l[8], e2) for a start / stop block --: every region is then a run of whole peak cells, but for the cell that e2 cuts, and a
+    // cell's largest value is the one at its peak line, in every pass (mp3mi_dev.h): ONE read per lane, and the peak line itself says
+    // which region the cell is of (a1 and a2 are cell edges).  The cut cell: if it starts below n_big it holds a value above 1, so does
+    // its peak line, which therefore lies below n_big <= e2 -- inside the region.  If it starts at n_big or later, it starts AT n_big
+    // and e2 = n_big + 2 (both even, e2 - n_big is 0 or 2): its part of the region is the one pair in front of e2, values 0 / 1, while
+    // its peak may lie past e2 (it then counts for no region) and read 1 where the pair holds zeros.  So the two lines of the pair in
+    // front of e2 are read as well, by lanes 32 and up -- which have no cell --, as cells of one line: always right, since they ARE in
+    // the region the test puts them in.
+    // Anything else -- stale addresses (big_values == 0), an address past e2 (a band edge above a small big_values) -- walks the regions.
+    if (e2 > 0 && a1 <= a2 && a2 <= e2) {
+        const int w = (int) L.peak[lane];
+        const int p = w < 1024 ? w : e2 - 1026 + w; // (lanes 32..63 hold 1024 | lane & 1: lines e2 - 2, e2 - 1)
+        const int v = (int) ((const uint16_t *) L.ix)[p];
+        red[1] = p < a1 ? v : 0;
+        red[2] = (p >= a1 && p < a2) ? v : 0;
+        red[3] = (p >= a2 && p < e2) ? v : 0;
+    } else {
+        // Each region is walked on its own, 64 pairs (one word each) per step straight out of L.ix; lines from slot nslot on are
+        // zero, so the maxima may skip them.  (Written out per region: arrays indexed by the region would live in scratch memory.)
+        const int nzend = 64 * nslot;
+        auto region_max = [&](int lo, int hi) {
+            hi = hi < nzend ? hi : nzend; // both even
+            mp3mi_u16x2 m = {0, 0}; // the maxima of the x and of the y of this lane's pairs: one packed instruction a step
+            const unsigned *p = ixw + (lo >> 1) + lane;
+            const int span = hi > lo ? hi - lo : 0, nfull = span >> 7, rest = (span & 127) >> 1; // whole steps of 64 pairs (nothing to mask), and a last one
+            if (nfull > 0) {
+                m = LOOP_PK_MAX_U16(m, __builtin_bit_cast(mp3mi_u16x2, p[0]));
+                if (nfull > 1) {
+                    m = LOOP_PK_MAX_U16(m, __builtin_bit_cast(mp3mi_u16x2, p[64]));
+                    if (nfull > 2) {
+                        m = LOOP_PK_MAX_U16(m, __builtin_bit_cast(mp3mi_u16x2, p[128]));
+                        if (nfull > 3) m = LOOP_PK_MAX_U16(m, __builtin_bit_cast(mp3mi_u16x2, p[192]));
+                    }
                 }
             }
-        }
-        if (rest) {
-            // read unconditionally (L.ix is padded: pairs past the end exist) and mask: a conditional load costs
-            // three scalar instructions and two branches per step
-            const unsigned xy = lane < rest ? p[64 * nfull] : 0u;
-            m = LOOP_PK_MAX_U16(m, __builtin_bit_cast(mp3mi_u16x2, xy));
-        }
-        return (int) (m.x > m.y ? m.x : m.y); // this lane's part
-    };
-    // the three region maxima and the count1 region's two bit sums: four reductions in lock-step
-    int red[4] = {c1part, region_max(0, a1), region_max(a1, a2), region_max(a2, e2)};
+            if (rest) {
+                // read unconditionally (L.ix is padded: pairs past the end exist) and mask: a conditional load costs
+                // three scalar instructions and two branches per step
+                const unsigned xy = lane < rest ? p[64 * nfull] : 0u;
+                m = LOOP_PK_MAX_U16(m, __builtin_bit_cast(mp3mi_u16x2, xy));
+            }
+            return (int) (m.x > m.y ? m.x : m.y); // this lane's part
+        };
+        red[1] = region_max(0, a1);
+        red[2] = region_max(a1, a2);
+        red[3] = region_max(a2, e2);
+    }
     wave_reduce_i32<1, 3>(red);
     CBPROF(2); // region maxima + reduction
     {
@@ -993,6 +1018,7 @@ MP3MI_DEVFN void loop_stream(const mp3mi_tables *__restrict__ T, loop_kargs_p ka
     for (int i = lane; i < (int) (sizeof(mp3mi_loop_state) / 4); i += 64) ((int *) &L.st)[i] = ((const int *) &LOOP_ARG(state)[s])[i];
     L.ix[576 + lane] = 0; L.ix[640 + lane] = 0; // (the padding: pairs that do not exist)
     if (lane < 2) L.xr[576 + lane] = 0.0;
+    if (lane >= MP3MI_PEAK_CELLS) L.peak[lane] = (uint16_t) (1024 | (lane & 1)); // (loop_count_bits: the lanes without a peak cell)
     wave_sync();
     int ref_abort = __builtin_amdgcn_readfirstlane(L.st.ref_abort); // (sticky: the first event of the stream stands)
 
@@ -1062,6 +1088,7 @@ MP3MI_DEVFN void loop_stream(const mp3mi_tables *__restrict__ T, loop_kargs_p ka
                     L.st.sc_en[gr][ch][lane] = pp->sc_en[lane];
                     L.st.sc_xm[gr][ch][lane] = pp->sc_xm[lane];
                 }
+                if (!shortb && lane < MP3MI_PEAK_CELLS) L.peak[lane] = pp->peak[lane]; // (read from the first pass on: barriers enough in between)
                 const int nonzero = pp->nonzero;
                 int scfsi_m = 0; // this granule's scfsi bits (wave-uniform): what the search asks for between passes
                 wave_sync();
@@ -1644,7 +1671,9 @@ __global__ void __launch_bounds__(64) k_debug_quantize_count(const mp3mi_tables 
 {
     __shared__ loop_lds L;
     __shared__ uint16_t GL[928];
+    __shared__ double zeros[8];
     for (int i = (int) threadIdx.x; i < 928; i += 64) GL[i] = T->glut[i];
+    if (threadIdx.x < 8) zeros[threadIdx.x] = 0.0;
     __syncthreads();
     const size_t gi = blockIdx.x;
     const int lane = wave_lane();
@@ -1679,6 +1708,13 @@ __global__ void __launch_bounds__(64) k_debug_quantize_count(const mp3mi_tables 
         }
     }
     wave_sync();
+    if (!shortb) { // the peak lines of xr_in, by the walk that takes them in the pipeline (k_mdct's tail: mp3mi_cell_peak over mp3mi_peak_cell)
+        int first, lines;
+        mp3mi_peak_cell(T->sfb_l, lane & (MP3MI_PEAK_CELLS - 1), &first, &lines);
+        const int at = mp3mi_cell_peak((const double *) &L.xr[first], (const double *) zeros, lines, wave_max_i32(lines));
+        L.peak[lane] = lane < MP3MI_PEAK_CELLS ? (uint16_t) (first + at) : (uint16_t) (1024 | (lane & 1)); // (as loop_stream fills it)
+        wave_sync();
+    }
     const unsigned long long bandpack = T->lane_bands[shortb][lane];
     if (in.pre && !shortb) { // preemphasis with every one of sfb 17..20 violating (loop_stream)
 #pragma unroll
@@ -1815,6 +1851,60 @@ extern "C" int mp3mi_debug_quantize_count(int rate_hz, int n_gran, const double 
     if (dg) hipFree(dg);
     if (dix) hipFree(dix);
     if (df) hipFree(df);
+    free(Th);
+    return rc;
+}
+
+// ---- self-test hook: the peak lines k_mdct's tail would record for given granules, and the cells they are the peaks of ----
+__global__ void __launch_bounds__(64) k_debug_peak_lines(const mp3mi_tables *__restrict__ T, const double *__restrict__ xr_in, uint16_t *__restrict__ peak_out)
+{
+    __shared__ double xr[576 + 8]; // (eight zeros behind the spectrum: what a lane past its cell's end reads)
+    const int lane = wave_lane();
+    for (int i = lane; i < 576 + 8; i += 64) xr[i] = i < 576 ? xr_in[(size_t) blockIdx.x * 576 + i] : 0.0;
+    __syncthreads();
+    int first, lines;
+    mp3mi_peak_cell(T->sfb_l, lane & (MP3MI_PEAK_CELLS - 1), &first, &lines);
+    const int at = mp3mi_cell_peak((const double *) &xr[first], (const double *) &xr[576], lines, wave_max_i32(lines));
+    if (lane < MP3MI_PEAK_CELLS) peak_out[(size_t) blockIdx.x * MP3MI_PEAK_CELLS + lane] = (uint16_t) (first + at);
+}
+
+extern "C" int mp3mi_debug_peak_lines(int rate_hz, int n_gran, const double *xr, uint16_t *peak, int32_t *cell_first)
+{
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return MP3MI_ERR_NO_DEVICE;
+    const int ri = rate_hz == 44100 ? 0 : (rate_hz == 48000 ? 1 : (rate_hz == 32000 ? 2 : -1));
+    if (ri < 0 || n_gran < 0 || !cell_first || (n_gran > 0 && (!xr || !peak))) return MP3MI_ERR_ARG;
+    mp3mi_tables *Th = (mp3mi_tables *) malloc(sizeof(mp3mi_tables));
+    if (!Th) return MP3MI_ERR_NOMEM;
+    const int trc = mp3mi_build_tables(Th, ri);
+    if (trc != 0) {
+        free(Th);
+        return trc == -8 ? MP3MI_ERR_TABLES : MP3MI_ERR_ARG;
+    }
+    for (int c = 0; c <= MP3MI_PEAK_CELLS; c++) { // (the cells as the kernels cut them; entry MP3MI_PEAK_CELLS closes the last cell)
+        int first = 576, lines = 0, cells = 0;
+        for (int b = 0; b < 22; b++) {
+            const int nb = (Th->sfb_l[b + 1] - Th->sfb_l[b] + MP3MI_PEAK_CELL_LINES - 1) / MP3MI_PEAK_CELL_LINES;
+            if (c >= cells && c < cells + nb) first = Th->sfb_l[b] + (c - cells) * MP3MI_PEAK_CELL_LINES;
+            cells += nb;
+        }
+        cell_first[c] = first;
+    }
+    const size_t n = (size_t) n_gran;
+    mp3mi_tables *dT = NULL;
+    double *dxr = NULL;
+    uint16_t *dpk = NULL;
+    int rc = n ? MP3MI_ERR_HIP : MP3MI_OK;
+    if (n && hipMalloc((void **) &dT, sizeof(mp3mi_tables)) == hipSuccess && hipMalloc((void **) &dxr, n * 576 * 8) == hipSuccess &&
+        hipMalloc((void **) &dpk, n * MP3MI_PEAK_CELLS * 2) == hipSuccess &&
+        hipMemcpy(dT, Th, sizeof(mp3mi_tables), hipMemcpyHostToDevice) == hipSuccess &&
+        hipMemcpy(dxr, xr, n * 576 * 8, hipMemcpyHostToDevice) == hipSuccess) {
+        hipLaunchKernelGGL(k_debug_peak_lines, dim3((unsigned) n), dim3(64), 0, 0, dT, dxr, dpk);
+        if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(peak, dpk, n * MP3MI_PEAK_CELLS * 2, hipMemcpyDeviceToHost) == hipSuccess) rc = MP3MI_OK;
+    }
+    if (dT) hipFree(dT);
+    if (dxr) hipFree(dxr);
+    if (dpk) hipFree(dpk);
     free(Th);
     return rc;
 }

@@ -185,13 +185,74 @@ typedef struct {
 /* Stateless per-(granule, channel) inputs of the iteration loop, computed for all granules in
  * parallel (k_mdct's tail; k_prep for the records it lists) so that the serial kernel starts from them: allowed
  * distortion (calc_xmin, src/loop.c:1085), the integer log-energies calc_scfsi stores (src/loop.c:631-667)
- * and the start value of the quantiser step (quantanf_init, src/loop.c:369).  One 472-byte record per (granule,
- * channel), record-major: k_mdct's lanes write a record's fields side by side and k_loop's wavefront reads them so. */
+ * and the start value of the quantiser step (quantanf_init, src/loop.c:369).  One 536-byte record per (granule,
+ * channel), record-major: k_mdct's lanes write a record's fields side by side and k_loop's wavefront reads them so.
+ * The first MP3MI_LOOP_PREP_HEAD bytes are what the reference computes too (and what mp3mi_batch_debug_fetch hands out);
+ * peak[] is this project's own: see mp3mi_peak_cell below. */
+#define MP3MI_PEAK_CELLS 32
 typedef struct {
     double xmin[36];                 /* long: [sfb], sfb < 21; short: [sfb*3 + window], sfb < 12 */
     int32_t sc_en[21], sc_xm[21];    /* written for non-short granules only */
     int32_t sc_en_tot, sc_xrmax, q0, nonzero;
+    uint16_t peak[MP3MI_PEAK_CELLS]; /* non-short granules only, by k_mdct's tail alone (mdct_peak_tail; k_prep leaves it): a line of cell c with the largest |xr| */
 } mp3mi_loop_prep;
+#define MP3MI_LOOP_PREP_HEAD 472     /* offsetof(mp3mi_loop_prep, peak) */
+
+/* Peak cells.  The quantiser is monotone in |xr| (ix = max{p : tab[p] <= |xr| / step}, k_loop.hip) and everything the search
+ * does to the spectrum -- pre-emphasis, amplification -- multiplies all lines of a scalefactor band by one positive factor,
+ * which keeps '<=' through the rounding.  So among lines that are always scaled together the one with the largest |xr| has the
+ * largest quantised value in every pass of the granule: k_loop's region maxima read that one line per cell instead of walking
+ * the region (loop_count_bits).  The 576 lines of a long / start / stop block are cut into at most MP3MI_PEAK_CELLS cells that
+ * refine the band structure (bands 0..20 and the lines from sfb_l[21] on, which are never scaled): a band of up to
+ * MP3MI_PEAK_CELL_LINES lines is one cell, a longer one is cut into cells of that many lines (its last one may be shorter), in line
+ * order; the cells behind the last one are empty (first line 576, no lines).  Every cell starts on an even line, as every band
+ * does.  Table build checks that MP3MI_PEAK_CELLS cells are enough (tables_host.cpp; at the three MPEG-1 rates they are exactly 32). */
+#define MP3MI_PEAK_CELL_LINES 32
+MP3MI_DEVFN void mp3mi_peak_cell(const int32_t *sfb_l, int c, int *first, int *lines)
+{
+    int f = 576, n = 0, cells = 0; // (no branch: every lane looks at every band)
+    for (int b = 0; b < 22; b++) {
+        const int lo = sfb_l[b], len = sfb_l[b + 1] - lo, nb = (len + MP3MI_PEAK_CELL_LINES - 1) / MP3MI_PEAK_CELL_LINES;
+        const bool here = c >= cells && c < cells + nb;
+        const int at = lo + (c - cells) * MP3MI_PEAK_CELL_LINES, left = lo + len - at;
+        f = here ? at : f;
+        n = here ? (left < MP3MI_PEAK_CELL_LINES ? left : MP3MI_PEAK_CELL_LINES) : n;
+        cells += nb;
+    }
+    *first = f;
+    *lines = n;
+}
+/* The peak line of a cell -- which of its `lines` lines from `cell` on has the largest |xr|, as an index within the cell --, the
+ * way k_mdct's tail walks its chains (k_fbmdct.hip): eight lines at a time, the loads first, all in flight together; `steps` is the
+ * longest cell of the wavefront, and a lane past its cell's end reads `zeros` (eight of them), which never win.  The first of tied
+ * lines stands (any would do: tied lines quantise alike); a cell of zeros names its first line. */
+template <class P>
+MP3MI_DEVFN int mp3mi_cell_peak(P cell, P zeros, int lines, int steps)
+{
+    double best = 0.0;
+    int at = 0;
+    for (int i0 = 0; i0 < steps; i0 += 8) {
+        P blk = cell + i0;
+        double v[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) v[j] = (i0 + j < lines ? blk : zeros)[j];
+        // (the peak as "the last line of these eight that went up": a small constant per line and one maximum, where an index and
+        // a selected double per line take eight index registers and two selects more)
+        int jb = 8;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            jb = __builtin_fabs(v[j]) > best ? j : jb;
+#if defined(MP3MI_EMU)
+            best = __builtin_fabs(v[j]) > best ? __builtin_fabs(v[j]) : best;
+#else
+            // (written out: as fmax(best, fabs(v)) the compiler first copies |v| through a maximum with itself, a register pair per line)
+            asm("v_max_f64 %0, %0, |%1|" : "+v"(best) : "v"(v[j]));
+#endif
+        }
+        at = jb < 8 ? i0 + jb : at;
+    }
+    return at;
+}
 
 /* Side information of one (granule, channel) as the iteration loop leaves it
  * (subset of gr_info, src/l3side.h:60-87, that the formatter needs). */

@@ -758,6 +758,11 @@ static int build_tables_unpinned(mp3mi_tables *T, int rate_idx)
         for (int l = SFB_S[ri][sfb]; l < SFB_S[ri][sfb + 1]; l++)
             for (int w = 0; w < 3; w++) T->sfb_of_line_s[l * 3 + w] = (uint8_t) (sfb * 3 + w);
 
+    { // k_loop's peak cells (mp3mi_dev.h): the bands, cut into cells of at most MP3MI_PEAK_CELL_LINES lines, take a lane of k_mdct's tail each
+        int cells = 0;
+        for (int sfb = 0; sfb < 22; sfb++) cells += (SFB_L[ri][sfb + 1] - SFB_L[ri][sfb] + MP3MI_PEAK_CELL_LINES - 1) / MP3MI_PEAK_CELL_LINES;
+        if (cells > MP3MI_PEAK_CELLS) return -13;
+    }
     // noise-sum jobs: split every band into parts of at most `target` elements, smallest target that fits 64 jobs
     for (int t = 0; t < 2; t++) {
         const int nb = t ? 36 : 21;
