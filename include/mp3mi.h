@@ -215,6 +215,69 @@ int mp3mi_batch_encode_slots_kbps(mp3mi_batch *b, const int16_t *pcm_dev, int n_
                                   uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev);
 int mp3mi_batch_slot_kbps(const mp3mi_batch *b, int32_t *kbps_host);
 
+/* Parking and resuming the streams of slots.  Every open slot must supply a full call of samples in every per-slot call; a
+ * stream whose next samples are late is PARKED instead: exported out of its slot into a record the caller owns, and imported
+ * later into any closed slot -- of this batch or of another batch of the same format, on another device too -- where the next
+ * call continues it with ctl 0.  The same two calls move a stream to a lower slot (so that the live slots stay dense) and
+ * take a checkpoint of a long stream.  The bytes the stream delivers from its START through its END, concatenated over every
+ * slot and batch it lived in, are its file, as if it had never moved.
+ *   A parked stream is a TICKET, host memory, and a STATE RECORD, device memory:
+ *   mp3mi_slot_ticket             what the host must know of the stream; plain data, may be stored and sent anywhere.
+ *     magic, version              MP3MI_SLOT_TICKET_MAGIC, MP3MI_SLOT_TICKET_VERSION (the layout of ticket and record)
+ *     state_bytes                 mp3mi_batch_slot_state_bytes of the batch that exported it
+ *     rate_hz, channels           the format of that batch, and what mp3mi_batch_set_mode, mp3mi_batch_set_header
+ *     hdr_mode, hdr_flags,        (copyright << 3 | original << 2 | emphasis) and mp3mi_batch_set_error_protection had been
+ *     error_protection            given when it was exported: a stream goes on under the header it began with
+ *     kbps                        the stream's bitrate (mp3mi_batch_slot_kbps)
+ *     frames                      frames encoded so far (mp3mi_batch_slot_frames)
+ *   mp3mi_batch_slot_state_bytes  the size of one stream's state record, a multiple of 16: opaque device data -- the
+ *                                 psychoacoustic state, the PCM history, the loop state with the bit reservoir and the stream's
+ *                                 status, the file position, the carried bytes and their count, the two live bitrate words.
+ *                                 It depends on the channel count only (and on the library's version: state_bytes is checked).
+ *   mp3mi_batch_slots_export      parks the streams of the n slots slots_host[0 .. n-1] (HOST array, copied before the call
+ *                                 returns): record i, of slot slots_host[i], is written at (char *) state_dev + i * state_stride,
+ *                                 tickets_host[i] is filled before the call returns.  The slots must be distinct, in range and
+ *                                 OPEN; n in 1 .. n_streams; state_stride >= mp3mi_batch_slot_state_bytes(b) and, like state_dev,
+ *                                 a multiple of 16.  close != 0: the slots are closed afterwards WITHOUT a flush -- nothing is
+ *                                 delivered, the pending bytes travel in the record -- so mp3mi_batch_slot_frames reports -1 for
+ *                                 them, mp3mi_batch_slot_kbps their create-time bitrate again, and every later call treats them
+ *                                 like any closed slot (out_len 0; a host call with a row map gives them no row).  close == 0:
+ *                                 the streams go on; the records are a snapshot, which may be imported elsewhere any number of
+ *                                 times (each import continues from the snapshot's frame).
+ *   mp3mi_batch_slots_import      resumes n parked streams: record i goes into slot slots_host[i], which must be CLOSED
+ *                                 (distinct, in range, n in 1 .. n_streams; stride and alignment as above).  Every ticket must
+ *                                 carry the library's magic and version, this batch's state_bytes, rate, channels, header mode,
+ *                                 header flags and error-protection setting, and a Layer III bitrate that does not exceed the
+ *                                 batch's ceiling (mp3mi_batch_slot_kbps); frames >= 0.  Afterwards the slot is open at the
+ *                                 ticket's frame count and bitrate -- whatever bitrate the slot was created with, exactly as
+ *                                 after a START at that bitrate -- and the next per-slot call continues the stream with ctl 0
+ *                                 (mp3mi_batch_encode_next too; a host call with a row map gives it a row).  Works as the first
+ *                                 call on a fresh batch, and after a flush or reset.
+ * Any broken rule returns MP3MI_ERR_ARG before anything is enqueued, and the batch is unchanged.
+ * Order: neither call waits for the device.  Both run behind everything the batch has been given before and ahead of everything
+ * it is given later, so a record may be imported into the batch that exported it at once.  Whoever else reads or writes a record
+ * -- another batch's import, a copy to another device or to the host -- waits for the exporting batch first
+ * (mp3mi_batch_sync), and an importing batch must be synced before its record is overwritten or freed.
+ * Status: the stream's status word travels in the record.  A stream the reference would have died on stays void after it
+ * resumes (out_len 0 in every call) and mp3mi_batch_stream_status reports the same code | frame << 8 from its new slot; the
+ * abort is not reported a second time by mp3mi_batch_sync.
+ * Until a batch's first export or import nothing of this exists: it launches and copies exactly what it did without. */
+#define MP3MI_SLOT_TICKET_MAGIC 0x4B54334Du /* "M3TK" */
+#define MP3MI_SLOT_TICKET_VERSION 1u
+typedef struct mp3mi_slot_ticket {
+    uint32_t magic, version;
+    uint64_t state_bytes;
+    int32_t rate_hz, channels;
+    int32_t hdr_mode, hdr_flags;
+    int32_t error_protection, kbps;
+    int64_t frames;
+} mp3mi_slot_ticket; /* 48 bytes, no padding */
+size_t mp3mi_batch_slot_state_bytes(const mp3mi_batch *b);
+int mp3mi_batch_slots_export(mp3mi_batch *b, int n, const int32_t *slots_host, int close, void *state_dev, size_t state_stride,
+                             mp3mi_slot_ticket *tickets_host);
+int mp3mi_batch_slots_import(mp3mi_batch *b, int n, const int32_t *slots_host, const void *state_dev, size_t state_stride,
+                             const mp3mi_slot_ticket *tickets_host);
+
 /* Ragged batch: stream s has n_samples_dev[s] valid samples per channel (0 <= n <= n_frames*1152) in
  * its row of pcm_dev (row pitch n_frames*1152*channels as above).  As the reference's get_audio /
  * read_samples do (/root/reference/src/encode.c:123-269, zero fill :162-166), the last partial frame

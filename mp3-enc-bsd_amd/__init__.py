@@ -37,6 +37,13 @@ class BatchOptions(ctypes.Structure):
                 ("dropin_stats", ctypes.c_int32), ("abi", ctypes.c_uint32)]
 
 
+class SlotTicket(ctypes.Structure):
+    """include/mp3mi.h: mp3mi_slot_ticket -- what the host knows of a parked stream (Batch.export_slots / import_slots)"""
+    _fields_ = [("magic", ctypes.c_uint32), ("version", ctypes.c_uint32), ("state_bytes", ctypes.c_uint64),
+                ("rate_hz", ctypes.c_int32), ("channels", ctypes.c_int32), ("hdr_mode", ctypes.c_int32), ("hdr_flags", ctypes.c_int32),
+                ("error_protection", ctypes.c_int32), ("kbps", ctypes.c_int32), ("frames", ctypes.c_int64)]
+
+
 def default_options(**kw):
     o = BatchOptions()
     lib().mp3mi_batch_options_default(ctypes.byref(o))
@@ -96,6 +103,11 @@ def lib():
         L.mp3mi_batch_encode_slots_kbps.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         L.mp3mi_batch_slot_kbps.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        L.mp3mi_batch_slot_state_bytes.restype = ctypes.c_size_t
+        L.mp3mi_batch_slot_state_bytes.argtypes = [ctypes.c_void_p]
+        L.mp3mi_batch_slots_export.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
+                                               ctypes.c_void_p]
+        L.mp3mi_batch_slots_import.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         L.mp3mi_batch_encode_slots_host_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         L.mp3mi_batch_encode_slots_kbps_host_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
@@ -289,6 +301,37 @@ class Batch:
         if rc < 0:
             raise Mp3miError("mp3mi_batch_slot_kbps failed with %d" % rc)
         return k, rc
+
+    def slot_state_bytes(self):
+        """bytes of one parked stream's device record (a multiple of 16): the least row size of export_slots' state tensor"""
+        return self.L.mp3mi_batch_slot_state_bytes(self.h)
+
+    def export_slots(self, slots, state, close=True):
+        """Parks the streams open in `slots` (distinct slot indices): row i of state -- a contiguous uint8 cuda tensor
+        [len(slots), stride], stride >= slot_state_bytes() and a multiple of 16 -- receives the device record of slots[i]'s
+        stream; returns the tickets, a ctypes array of SlotTicket, one per slot (host bookkeeping; no device wait).  close: the
+        slots are closed afterwards without a flush -- the pending bytes travel in the record; False: the streams go on and the
+        records are a snapshot.  sync() before the records are read by anything but this batch's own import_slots
+        (mp3mi_batch_slots_export)."""
+        import numpy as np
+        sl = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        assert state.is_cuda and state.is_contiguous() and state.dtype.itemsize == 1 and state.dim() == 2 and state.shape[0] >= len(sl)
+        tickets = (SlotTicket * max(len(sl), 1))()
+        self._check(self.L.mp3mi_batch_slots_export(self.h, len(sl), sl.ctypes.data, 1 if close else 0, state.data_ptr(), state.shape[1],
+                                                    ctypes.addressof(tickets)), "mp3mi_batch_slots_export")
+        return tickets
+
+    def import_slots(self, slots, state, tickets):
+        """Resumes parked streams in the closed slots `slots`: row i of state (as export_slots wrote it, of this batch or of
+        another batch of the same format) and tickets[i] go into slots[i], which is open afterwards at the ticket's frame count
+        and bitrate; the next encode_slots continues it (start and end false).  No device wait (mp3mi_batch_slots_import)."""
+        import numpy as np
+        sl = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        assert state.is_cuda and state.is_contiguous() and state.dtype.itemsize == 1 and state.dim() == 2 and state.shape[0] >= len(sl)
+        assert len(tickets) >= len(sl)
+        arr = (SlotTicket * max(len(sl), 1))(*list(tickets)[:len(sl)])
+        self._check(self.L.mp3mi_batch_slots_import(self.h, len(sl), sl.ctypes.data, state.data_ptr(), state.shape[1], ctypes.addressof(arr)),
+                    "mp3mi_batch_slots_import")
 
     def set_mode(self, mode):
         """0 stereo, 2 dual channel, 3 mono (the reference's -m s|d|m); joint stereo is refused as in the reference"""

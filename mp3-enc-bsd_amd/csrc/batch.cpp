@@ -121,6 +121,14 @@ struct mp3mi_batch {
     hipEvent_t ev_ctl[2], ev_ctl_up;
     bool ctl_used[2];
     unsigned ctl_calls;
+    // parking (mp3mi_batch_slots_export / _import): the slot list of such a call -- int32[S] -- in pinned staging and on the device,
+    // a ring of four by call, apart from the control block's two so that a tick, a park and a resume issued in a row do not wait
+    // for each other; ev_park[p] is recorded behind the last reader of copy p, and the host waits for it before it writes staging
+    // p again (the park call four before).  Created with the first such call: a batch that never parks holds none of it.
+    int32_t *park_stage[4], *park_dev[4];
+    hipEvent_t ev_park[4];
+    bool park_used[4];
+    unsigned park_calls;
     // Host-buffer calls (mp3mi_batch_encode_host_async): the call's PCM goes up and its file bytes come down chunk by
     // chunk on two copy streams of their own, beside the kernels; two calls may be in flight, so the device copies of
     // PCM and output exist twice (slot = call number & 1).  Created with the first such call.
@@ -511,6 +519,11 @@ extern "C" void mp3mi_batch_destroy(mp3mi_batch *b)
     for (hipEvent_t e : b->ev_loop) if (e) hipEventDestroy(e);
     for (int i = 0; i < 2; i++)
         if (b->ctl_stage[i]) hipHostFree(b->ctl_stage[i]);
+    for (int i = 0; i < 4; i++) {
+        if (b->park_stage[i]) hipHostFree(b->park_stage[i]);
+        if (b->park_dev[i]) hipFree(b->park_dev[i]);
+        if (b->ev_park[i]) hipEventDestroy(b->ev_park[i]);
+    }
     hipEvent_t evs[] = {b->ts[0].ev0, b->ts[0].ev1, b->ts[1].ev0, b->ts[1].ev1, b->ev_done, b->ev_hist, b->ev_ctl[0], b->ev_ctl[1], b->ev_ctl_up};
     for (hipEvent_t e : evs)
         if (e) hipEventDestroy(e);
@@ -914,6 +927,199 @@ extern "C" int mp3mi_batch_flush(mp3mi_batch *b, uint8_t *out_dev, size_t out_st
     CHK(hipEventRecord(b->ev_done, b->lstream));
     b->have_done = true;
     return reset_impl(b); // the streams are over: the next encode_next starts new ones
+}
+
+// ---- parking and resuming streams (mp3mi_batch_slots_export / mp3mi_batch_slots_import) ----
+// Everything a stream carries from call to call is a record per slot in eight regions.  The state record of a parked stream
+// holds them one after the other, each at a multiple of 16 bytes; front / loop: the regions by the HIP stream that owns them
+// (encode_impl), with their offsets.  Returns the record's size.
+static size_t park_tables(const mp3mi_batch *b, mp3mi_park_table *front, mp3mi_park_table *loop)
+{
+    const size_t C = (size_t) b->channels;
+    mp3mi_park_region r[8] = {{b->psy_state, (uint32_t) (mp3mi_psy_state_size() * C), 0},
+                              {b->pcm_hist, (uint32_t) (sizeof(int16_t) * MP3MI_PCM_HIST * C), 0},
+                              {b->loop_state, (uint32_t) mp3mi_loop_state_size(), 0},
+                              {b->out_base, (uint32_t) sizeof(int64_t), 0},
+                              {b->carry, MP3MI_CARRY_BYTES, 0},
+                              {b->carry_len, (uint32_t) sizeof(int32_t), 0},
+                              {b->bits_per_frame, (uint32_t) sizeof(int32_t), 0},   // (the live bitrate words last: an import leaves them out
+                              {b->bitrate_index, (uint32_t) sizeof(int32_t), 0}};   // where the live arrays hold nothing but create-time values)
+    uint32_t off = 0;
+    for (int k = 0; k < 8; k++) {
+        r[k].off = off;
+        off += (r[k].bytes + 15u) & ~15u;
+    }
+    if (front) {
+        memset(front, 0, sizeof(*front));
+        front->n = 2;
+        for (int k = 0; k < 2; k++) front->r[k] = r[k];
+    }
+    if (loop) {
+        memset(loop, 0, sizeof(*loop));
+        loop->n = 6;
+        for (int k = 0; k < 6; k++) loop->r[k] = r[2 + k];
+    }
+    return off;
+}
+static_assert(MP3MI_PARK_REGIONS >= 6, "the loop stream's regions of a parked stream");
+
+extern "C" size_t mp3mi_batch_slot_state_bytes(const mp3mi_batch *b) { return b ? park_tables(b, NULL, NULL) : 0; }
+
+// What export and import ask of their arguments alike (state_bytes: park_tables)
+static bool park_args_ok(const mp3mi_batch *b, int n, const int32_t *slots_host, const void *state_dev, size_t state_stride, const void *tickets,
+                         size_t state_bytes)
+{
+    if (!b || !slots_host || !state_dev || !tickets || n < 1 || n > b->n_streams) return false;
+    if (state_stride < state_bytes || state_stride % 16 != 0 || (uintptr_t) state_dev % 16 != 0) return false;
+    std::vector<char> seen((size_t) b->n_streams, 0);
+    for (int i = 0; i < n; i++) {
+        const int32_t s = slots_host[i];
+        if (s < 0 || s >= b->n_streams || seen[s]) return false;
+        seen[s] = 1;
+    }
+    return true;
+}
+
+// Whether the readers of a ring entry of the slot lists are through (four park calls ago: as a rule long since, and then the
+// host neither waits nor lets a held k_loop go, which would cost the next call its place beside that k_loop)
+static bool park_entry_free(hipEvent_t ev)
+{
+#if defined(MP3MI_EMU)
+    (void) ev;
+    return true; // (the emulator runs every launch where it is issued)
+#else
+    return hipEventQuery(ev) == hipSuccess;
+#endif
+}
+
+// The launches of an export (to_state) or an import: the slot list goes up on the front stream, like a per-slot call's control
+// block, and each stream moves the regions it owns -- the next call's feed-forward kernels do not wait for the loop stream, so
+// the psy state and the PCM history are read and written on the front stream only; everything k_loop, k_format and
+// k_stream_tail carry, the live bitrate words among them, on the loop stream only, behind the k_loop of the call before
+// (held or not: nothing here lets a hold go, the next call's first transforms do as ever, and neither launch waits for the
+// other stream's kernels).  An import's writes are also behind a reset's memsets, which run on the front stream (ev_ctl_up).
+static int park_run(mp3mi_batch *b, int n, const int32_t *slots_host, const mp3mi_park_table &front, const mp3mi_park_table &loop,
+                    void *state_dev, size_t state_stride, int to_state)
+{
+    const int p = (int) (b->park_calls & 3u);
+    if (!b->park_stage[p]) {
+        CHK(hipHostMalloc((void **) &b->park_stage[p], sizeof(int32_t) * (size_t) b->n_streams, 0));
+        CHK(hipMalloc((void **) &b->park_dev[p], sizeof(int32_t) * (size_t) b->n_streams));
+        CHK(hipEventCreateWithFlags(&b->ev_park[p], hipEventDisableTiming));
+    }
+    if (b->park_used[p] && !park_entry_free(b->ev_park[p])) {
+        hold_release(b); // (the host is about to wait for work that may be queued behind the held k_loop)
+        CHK(hipEventSynchronize(b->ev_park[p]));
+    }
+    memcpy(b->park_stage[p], slots_host, sizeof(int32_t) * (size_t) n);
+    CHK(hipMemcpyAsync(b->park_dev[p], b->park_stage[p], sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, b->stream));
+    CHK(hipEventRecord(b->ev_ctl_up, b->stream));
+    mp3mi_launch_slot_park(b->park_dev[p], n, front, state_dev, state_stride, to_state, b->stream);
+    CHK(hipGetLastError());
+    CHK(hipEventRecord(b->ev_hist, b->stream));
+    CHK(hipStreamWaitEvent(b->lstream, b->ev_ctl_up, 0));
+    if (!to_state && b->status_kept) {
+        // the last flush ended every stream and reset the state: the ended streams' status goes back into their slots now, as with a
+        // per-slot call, so that the call after this one does not write it over the status the resumed streams bring along
+        mp3mi_launch_status_scatter(b->n_streams, (int32_t *) b->loop_state, (int) (mp3mi_loop_state_size() / 4), b->status_dev, b->lstream);
+        CHK(hipGetLastError());
+        b->status_kept = false;
+    }
+    mp3mi_launch_slot_park(b->park_dev[p], n, loop, state_dev, state_stride, to_state, b->lstream);
+    CHK(hipGetLastError());
+    CHK(hipStreamWaitEvent(b->lstream, b->ev_hist, 0)); // both readers of the list are ahead of ev_park; ev_done covers both streams
+    CHK(hipEventRecord(b->ev_park[p], b->lstream));
+    b->park_used[p] = true;
+    b->park_calls++;
+    CHK(hipEventRecord(b->ev_done, b->lstream));
+    b->have_done = true;
+    return MP3MI_OK;
+}
+
+extern "C" int mp3mi_batch_slots_export(mp3mi_batch *b, int n, const int32_t *slots_host, int close, void *state_dev, size_t state_stride,
+                                        mp3mi_slot_ticket *tickets_host)
+{
+    if (!b) return MP3MI_ERR_ARG;
+    mp3mi_park_table front, loop;
+    const size_t state_bytes = park_tables(b, &front, &loop);
+    if (!park_args_ok(b, n, slots_host, state_dev, state_stride, tickets_host, state_bytes)) return MP3MI_ERR_ARG;
+    std::vector<int64_t> f((size_t) b->n_streams);
+    slot_frames_now(b, f.data());
+    for (int i = 0; i < n; i++)
+        if (f[slots_host[i]] < 0) return MP3MI_ERR_ARG; // no stream open there
+    ON_DEVICE(b);
+    for (int i = 0; i < n; i++) { // all of it host bookkeeping: no wait
+        const int32_t s = slots_host[i];
+        mp3mi_slot_ticket &t = tickets_host[i];
+        memset(&t, 0, sizeof(t));
+        t.magic = MP3MI_SLOT_TICKET_MAGIC;
+        t.version = MP3MI_SLOT_TICKET_VERSION;
+        t.state_bytes = (uint64_t) state_bytes;
+        t.rate_hz = b->rate_hz;
+        t.channels = b->channels;
+        t.hdr_mode = b->hdr_mode;
+        t.hdr_flags = b->hdr_flags;
+        t.error_protection = b->crc;
+        t.kbps = b->slot_kbps_h[s];
+        t.frames = f[s];
+    }
+    const int rc = park_run(b, n, slots_host, front, loop, state_dev, state_stride, 1);
+    if (rc != MP3MI_OK) return rc;
+    if (close) {
+        // (the whole-batch bookkeeping cannot say "all but these": the per-slot one takes over; slots_settle hands back as ever)
+        for (int i = 0; i < n; i++) {
+            const int32_t s = slots_host[i];
+            f[s] = -1;
+            b->slot_kbps_h[s] = b->kbps_h[s]; // the stream takes its bitrate with it
+        }
+    }
+    b->slot_frames_h.assign(f.begin(), f.end());
+    b->slots_on = true;
+    slots_settle(b);
+    return MP3MI_OK;
+}
+
+extern "C" int mp3mi_batch_slots_import(mp3mi_batch *b, int n, const int32_t *slots_host, const void *state_dev, size_t state_stride,
+                                        const mp3mi_slot_ticket *tickets_host)
+{
+    if (!b) return MP3MI_ERR_ARG;
+    mp3mi_park_table front, loop;
+    const size_t state_bytes = park_tables(b, &front, &loop);
+    if (!park_args_ok(b, n, slots_host, state_dev, state_stride, tickets_host, state_bytes)) return MP3MI_ERR_ARG;
+    std::vector<int64_t> f((size_t) b->n_streams);
+    slot_frames_now(b, f.data());
+    bool other_rate = false; // a stream arrives at another bitrate than its slot was created with
+    for (int i = 0; i < n; i++) {
+        const int32_t s = slots_host[i];
+        const mp3mi_slot_ticket &t = tickets_host[i];
+        int bi, bits;
+        if (f[s] >= 0) return MP3MI_ERR_ARG; // a stream is open there
+        if (t.magic != MP3MI_SLOT_TICKET_MAGIC || t.version != MP3MI_SLOT_TICKET_VERSION || t.state_bytes != (uint64_t) state_bytes) return MP3MI_ERR_ARG;
+        if (t.rate_hz != b->rate_hz || t.channels != b->channels || t.hdr_mode != b->hdr_mode || t.hdr_flags != b->hdr_flags ||
+            t.error_protection != b->crc)
+            return MP3MI_ERR_ARG;
+        if (t.kbps > b->ceil_kbps || !rate_of_kbps(b->rate_idx, t.kbps, &bi, &bits) || t.frames < 0) return MP3MI_ERR_ARG;
+        other_rate |= t.kbps != b->kbps_h[s];
+    }
+    ON_DEVICE(b);
+    // the streams' bitrate words go into the live arrays once any slot of the batch may hold another bitrate than its create-time
+    // one -- the rule of a START (slots_impl); otherwise the arrays already hold what the records hold
+    if (!(b->rate_dirty || other_rate)) loop.n -= 2;
+    const int rc = park_run(b, n, slots_host, front, loop, const_cast<void *>(state_dev), state_stride, 0);
+    if (rc != MP3MI_OK) return rc;
+    for (int i = 0; i < n; i++) {
+        const int32_t s = slots_host[i];
+        f[s] = tickets_host[i].frames;
+        b->slot_kbps_h[s] = tickets_host[i].kbps;
+    }
+    b->rate_dirty |= other_rate;
+    // the per-slot bookkeeping from here on, also on a batch nothing has run on yet: no later call takes the "first call clears
+    // every stream's state" branch of encode_impl over the resumed streams (slots_settle hands back only with every slot open)
+    b->slot_frames_h.assign(f.begin(), f.end());
+    b->slots_on = true;
+    b->fresh = false;
+    slots_settle(b);
+    return MP3MI_OK;
 }
 
 static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_samples_dev, int n_frames, uint8_t *out_dev,

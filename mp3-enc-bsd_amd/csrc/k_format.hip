@@ -563,6 +563,47 @@ void mp3mi_launch_slot_rate(const int32_t *list, int n_list, const int32_t *bits
     hipLaunchKernelGGL(k_slot_rate, dim3((unsigned) ((n_list + 63) / 64)), dim3(64), 0, st, list, n_list, bits, index, bits_per_frame, bitrate_index);
 }
 
+// ---- parking and resuming the streams of slots (mp3mi_batch_slots_export / mp3mi_batch_slots_import) ----
+// Everything a stream carries from call to call is a record per slot in a handful of regions (batch.cpp).  k_slot_park moves
+// the listed slots' records between those regions and the caller's state records (one per listed slot, `stride` bytes apart;
+// region k at offset t.r[k].off, a multiple of 16): to_state != 0 gathers (export), 0 scatters (import).  Workgroup (i, y):
+// the i-th listed slot -- one load of the list, uniform -- and every gridDim.y-th access of each region.  A region whose
+// record size is a multiple of 16 moves 16 bytes per lane and access (its base comes from hipMalloc, the state records are
+// 16-byte aligned with a stride of a multiple of 16: batch.cpp checks); the others -- the file position, the carry length, the
+// two bitrate words -- move words.  Nothing is reused: no LDS.  batch.cpp launches it twice per direction, once per HIP stream
+// with the regions that stream owns, exactly as k_slot_begin.
+__global__ void __launch_bounds__(256) k_slot_park(const int32_t *__restrict__ list, mp3mi_park_table t, uint8_t *__restrict__ state,
+                                                   size_t stride, int to_state)
+{
+    const size_t i = blockIdx.x, s = (size_t) list[i];
+    const size_t lane = (size_t) blockIdx.y * 256 + threadIdx.x, step = (size_t) 256 * gridDim.y;
+#pragma unroll
+    for (int k = 0; k < MP3MI_PARK_REGIONS; k++) {
+        if (k >= t.n) break;
+        const size_t bytes = t.r[k].bytes;
+        uint8_t *live = (uint8_t *) t.r[k].base + s * bytes, *rec = state + i * stride + t.r[k].off;
+        const uint8_t *src = to_state ? live : rec;
+        uint8_t *dst = to_state ? rec : live;
+        if (bytes % 16 == 0) {
+            const size_t n = bytes / 16;
+            for (size_t j = lane; j < n; j += step) ((uint4 *) dst)[j] = ((const uint4 *) src)[j];
+        } else {
+            const size_t n = bytes / 4;
+            for (size_t j = lane; j < n; j += step) ((uint32_t *) dst)[j] = ((const uint32_t *) src)[j];
+        }
+    }
+}
+
+void mp3mi_launch_slot_park(const int32_t *list, int n_list, const mp3mi_park_table &t, void *state, size_t stride, int to_state, hipStream_t st)
+{
+    if (n_list <= 0 || t.n <= 0) return;
+    size_t most = 0;
+    for (int k = 0; k < t.n; k++) most = t.r[k].bytes > most ? t.r[k].bytes : most;
+    size_t ny = (most + 256 * 16 - 1) / (256 * 16); // an access per lane of the largest region, at most four workgroups a slot
+    if (ny > 4) ny = 4;
+    hipLaunchKernelGGL(k_slot_park, dim3((unsigned) n_list, (unsigned) ny), dim3(256), 0, st, list, t, (uint8_t *) state, stride, to_state);
+}
+
 // ---- per-slot streaming on host buffers (mp3mi_batch_encode_slots_host_async) ----
 // The caller's buffers hold one ROW per live slot, dense; the encoder's kernels read and write one row per SLOT.  Two bandwidth
 // kernels sit between the copies and the encoder: both move 16 bytes per lane and access (one wavefront-instruction = 1 KiB,

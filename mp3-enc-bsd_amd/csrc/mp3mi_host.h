@@ -145,6 +145,13 @@ void mp3mi_launch_slot_begin(const int32_t *list, int n_list, mp3mi_slot_region 
    streams a call STARTs; list values are slots of the two live arrays, checked on the host) */
 void mp3mi_launch_slot_rate(const int32_t *list, int n_list, const int32_t *bits, const int32_t *index, int32_t *bits_per_frame,
                             int32_t *bitrate_index, hipStream_t st);
+/* k_slot_park: the listed slots' records of up to MP3MI_PARK_REGIONS regions to (to_state != 0) or from the caller's state
+   records: record i, of list[i], at state + i * stride, region k of it at offset r[k].off (a multiple of 16; stride and state too).
+   bytes: the region's record size per slot, a multiple of 4; a multiple of 16 moves as 16-byte accesses */
+#define MP3MI_PARK_REGIONS 6
+struct mp3mi_park_region { void *base; uint32_t bytes, off; };
+struct mp3mi_park_table { mp3mi_park_region r[MP3MI_PARK_REGIONS]; int n; };
+void mp3mi_launch_slot_park(const int32_t *list, int n_list, const mp3mi_park_table &t, void *state, size_t stride, int to_state, hipStream_t st);
 /* per-slot streaming on host buffers: dense rows (one per live slot, row_slot[r] = its slot) to and from the rows per slot.
    k_rows_in: bytes [col0, col0 + width) of every dense PCM row into the same columns of its slot's row (all multiples of 16);
    k_rows_out: out_len[slot] bytes of every listed slot's output row and the length into dense rows of dense_stride, rest zeroed */

@@ -21,7 +21,13 @@ to back, tick t collected with mp3mi_batch_host_wait(1) after tick t + 1 has bee
   (g) host_churn          the host call; in every tick 1/32 of the live slots END and as many closed ones START, so the row
                           set changes from tick to tick
 
-usage: slots_bench.py [--calls 20] [--frames 32] [--streams 4096] [--reps 3] [--mixed-kbps] [--host [--occupancy 1.0] [--map]]"""
+--park N: one more resident case.  In every tick after the first, N streams are PARKED (mp3mi_batch_slots_export, closing their
+slots) and the N streams parked one tick before RESUME in the slots they left (mp3mi_batch_slots_import): 2 N <= streams, and
+streams - N of them are live in every tick:
+  (p) slots_park          import N, export N, encode_slots per tick, issued back to back like the others
+The line then carries park_vs_continue and the bytes of a state record.
+
+usage: slots_bench.py [--calls 20] [--frames 32] [--streams 4096] [--reps 3] [--mixed-kbps] [--park N] [--host [--occupancy 1.0] [--map]]"""
 import argparse
 import importlib
 import json
@@ -41,13 +47,14 @@ def main():
     ap.add_argument("--streams", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=3, help="runs of every case; the fastest counts")
     ap.add_argument("--mixed-kbps", action="store_true", help="a batch created at 320 kbps; every START draws 64 / 128 / 192 / 320")
+    ap.add_argument("--park", type=int, default=0, help="per tick, park this many streams and resume as many parked ones")
     ap.add_argument("--host", action="store_true", help="the per-slot cases on page-locked host buffers")
     ap.add_argument("--occupancy", type=float, default=1.0, help="--host: fraction of the slots that are live")
     ap.add_argument("--map", action="store_true", help="--host: a row map at occupancy 1.0 too (k_rows_in / k_rows_out run)")
     a = ap.parse_args()
     if a.host:
-        if a.mixed_kbps:
-            ap.error("--mixed-kbps times the resident cases (without --host)")
+        if a.mixed_kbps or a.park:
+            ap.error("--mixed-kbps and --park time the resident cases (without --host)")
         return host_main(a)
     import torch
     mp3 = importlib.import_module("mp3-enc-bsd_amd")
@@ -94,7 +101,25 @@ def main():
             b.encode_slots(pcm, nf, out, out_len, start=start, end=end, n_samples=ns, kbps=draw(start))
             closed = end
 
-    cases = (("encode_next", run_next), ("slots_continue", run_continue), ("slots_churn", run_churn))
+    N = a.park
+    if N and not 0 < 2 * N <= S:
+        ap.error("--park N needs 2 N <= streams")
+    state = [torch.zeros((N, b.slot_state_bytes()), dtype=torch.uint8, device=dev) for _ in range(2)] if N else None
+
+    def run_park():
+        """every slot STARTs; tick k >= 1 resumes the N streams tick k - 1 parked, in the slots they left, parks the streams of the
+        next N slots of a random walk (record sets by the tick's parity), and encodes: S - N streams are live in every tick"""
+        order = rng.permutation(S).astype(np.int32)
+        b.encode_slots(pcm, nf, out, out_len, start=every)
+        away = None  # (slots, tickets) of the tick before
+        for k in range(1, a.calls):
+            if away is not None:
+                b.import_slots(away[0], state[(k - 1) & 1], away[1])
+            sl = order[((k - 1) * N + np.arange(N)) % S]
+            away = (sl, b.export_slots(sl, state[k & 1]))
+            b.encode_slots(pcm, nf, out, out_len)
+
+    cases = (("encode_next", run_next), ("slots_continue", run_continue), ("slots_churn", run_churn)) + ((("slots_park", run_park),) if N else ())
     res = {}
     for name, fn in cases:
         best = None
@@ -109,12 +134,15 @@ def main():
             if r > 0:
                 best = ms if best is None else min(best, ms)
         res[name] = round(best, 3)
+    b_state_bytes = b.slot_state_bytes() if N else 0
     b.close()
     print(json.dumps({"tool": "slots_bench", "streams": S, "frames_per_call": nf, "calls": a.calls, "rate": rate, "channels": ch,
                       "kbps": kbps, "mixed_kbps": bool(a.mixed_kbps), "mean_kbps_continue": round(float(drawn[0].mean()), 1) if drawn else kbps,
                       "ms_per_call": res,
                       "continue_vs_next": round(res["slots_continue"] / res["encode_next"], 4),
                       "churn_vs_continue": round(res["slots_churn"] / res["slots_continue"], 4),
+                      **({"park": N, "park_vs_continue": round(res["slots_park"] / res["slots_continue"], 4),
+                          "state_bytes": b_state_bytes} if N else {}),
                       "source_hash": mp3.lib().mp3mi_source_hash().decode()}))
 
 
