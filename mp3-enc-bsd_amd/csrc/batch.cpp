@@ -23,38 +23,82 @@
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
-#include "mp3mi_host.h"
+#include "host_util.h"
 #include "mp3mi.h"
 
 size_t mp3mi_psy_state_size(void);
 size_t mp3mi_loop_state_size(void);
 
-#define CHK(call)                                                                              \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            fprintf(stderr, "mp3mi: %s failed: %s (%s:%d)\n", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return MP3MI_ERR_HIP;                                                              \
-        }                                                                                      \
-    } while (0)
+// What a stream carries from call to call: one record per slot in each of these regions.  mp3mi_batch::carried is the ONE list
+// of them (carried_init, once the buffers exist), in the order of a parked stream's state record -- that order is part of the
+// slot-state format (park_tables).  Whoever clears, starts, parks or resumes streams walks it.
+//   loop: the HIP stream that owns the region, the only one it is read or written on (encode_impl): the psy state and the PCM
+//         history belong to the front stream, whose feed-forward kernels do not wait for the loop stream; everything k_loop,
+//         k_format and k_stream_tail carry belongs to the loop stream
+//   zero: a fresh stream needs its record zeroed (what the reference's function statics and the caller's buffers hold when its
+//         main() starts).  Not carry's contents -- carry_len says how much of them counts -- and not the live bitrate words:
+//         rates_restore and k_slot_rate see to those
+struct carried_region {
+    void *base;
+    size_t bytes; // per slot
+    bool loop, zero;
+};
+enum { N_CARRIED = 8 };
 
+// The control block of a per-slot call:
+//   fabs int64[S] | n_samples int32[S] | START list int32[S] | ctl uint8[S] | row map int32[S] (host-buffer calls, n_rows used) |
+//   by position in the START list: bits per frame int32[S] | bitrate index int32[S] (k_slot_rate)
+// The offsets are computed once (batch_build); at() gives the typed pointers of a block from its base -- of the staging copy and
+// of the device copy alike.
+struct ctl_block {
+    int64_t *fabs;       // [S] index of the call's first frame in the stream of each slot
+    int32_t *n_samples;  // [S] valid samples per channel of each slot in the call
+    int32_t *list;       // [n_start] the slots that START
+    uint8_t *ctl;        // [S] MP3MI_SLOT_DEV_* bits
+    int32_t *rows;       // [n_rows] row_slot of a host-buffer call with a row map
+    int32_t *rate_bits, *rate_index; // [n_start] of the streams that START, by position in `list`
+};
+struct ctl_layout {
+    size_t n_samples, list, ctl, rows, rate_bits, rate_index; // byte offsets (fabs: 0)
+    size_t base_bytes; // the block without the bitrates: all that goes up while no call writes the live bitrate arrays
+    size_t bytes;      // the whole block
+    void init(size_t S)
+    {
+        n_samples = 8 * S; list = n_samples + 4 * S; ctl = list + 4 * S;
+        rows = (ctl + S + 3) & ~(size_t) 3;
+        rate_bits = rows + 4 * S; rate_index = rate_bits + 4 * S;
+        base_bytes = (rate_bits + 255) & ~(size_t) 255;
+        bytes = (rate_index + 4 * S + 255) & ~(size_t) 255;
+    }
+    ctl_block at(uint8_t *p) const
+    {
+        return {(int64_t *) p, (int32_t *) (p + n_samples), (int32_t *) (p + list), p + ctl, (int32_t *) (p + rows), (int32_t *) (p + rate_bits),
+                (int32_t *) (p + rate_index)};
+    }
+};
+
+// The batch, in this order: what it was created as; the two HIP streams and the fences between them and between calls; the
+// per-chunk scratch; what a stream carries (carried); the two stream-position bookkeepings; the two upload rings (control block,
+// park list); host-buffer calls; timing.  Ownership: every device and pinned buffer is allocated through dev_alloc / pinned_alloc,
+// which note it in `owned`, and mp3mi_batch_destroy frees what was noted -- a new buffer needs no line there.  (One exception,
+// host_io::io_slot::out_rows, which is freed and reallocated as calls grow: by hand.)  Events are destroyed by name.
 struct mp3mi_batch {
     int device;              // the HIP device everything of this batch lives on (current at create time)
     int n_streams, rate_idx, rate_hz, channels, max_frames, chunk_frames;
     std::vector<int> bits_per_frame_h, bitrate_index_h, kbps_h; // as created, per stream index
     int max_frame_bytes, ceil_kbps; // of the largest bitrate the batch was created with: what the output rows are sized for
+    struct owned_buf { void *p; bool pinned; };
+    std::vector<owned_buf> owned; // every buffer of dev_alloc / pinned_alloc, in the order of allocation
     hipStream_t stream;      // front stream: feed-forward kernels (and the initial memsets)
     hipStream_t lstream;     // loop stream: k_loop + k_format
     // A batch of more streams than k_loop holds resident is cut into PARTS (contiguous stream ranges); a part's frames of
     // one chunk are an "item", and the items go through the two HIP streams one after the other (encode_impl).
     // Per (double-buffer slot, part), index slot * n_parts + part:
     std::vector<hipEvent_t> ev_front; // the item's front kernels are done
-    std::vector<hipEvent_t> ev_loop;  // its k_loop is done (the slot's region of this part may be overwritten)
-    std::vector<char> slot_used;      // ev_loop has been recorded: the region's last reader is a k_loop that may still run
+    std::vector<fence> ev_loop;       // its k_loop is done (the slot's region of this part may be overwritten): the region's last reader is a k_loop that may still run
     int n_parts, part_streams;
-    hipEvent_t ev_done;      // everything of the previous encode call is done
+    fence ev_done;           // everything of the previous encode call is done
     hipEvent_t ev_hist;      // the front stream's last work of a call (the PCM history hand-over) is enqueued
-    bool have_done;
     // The last k_loop of a call is HELD on the device (k_hold, k_loop.hip) until the next call's first transforms are through:
     // hold_flag is one word of host memory mapped into the device's address space, hold_seq the ticket of the hold in
     // force (tickets only grow), held = a hold is in force that neither a next call nor the host has let go yet
@@ -95,66 +139,64 @@ struct mp3mi_batch {
     mp3mi_psy_out *psy[2];
     mp3mi_loop_prep *prep[2];
     mp3mi_prep_fixlist *prep_fix; // the records k_mdct's tail could not decide (k_prep works through the list); front stream only
-    void *psy_state, *loop_state;
     int16_t *ix;
     mp3mi_frame_side *side;
-    // streaming (encode_next / flush): what a stream carries from call to call besides psy_state / loop_state
-    long frames_done;        // frames of every stream encoded since the last reset
-    bool fresh;              // reset since the last encode (or never encoded): state buffers are zero
+    // what a stream carries from call to call (whole-file calls clear it, streaming calls continue from it): `carried` lists it all
+    void *psy_state, *loop_state;
     int16_t *pcm_hist;       // [S][MP3MI_PCM_HIST][C]: the samples before the next call's first
     int64_t *out_base;       // [S]: file bytes delivered so far
     uint8_t *carry;          // [S][MP3MI_CARRY_BYTES]: file bytes formatted but not final yet
     int32_t *carry_len;      // [S]
+    carried_region carried[N_CARRIED];
+    // streaming (encode_next / flush), the whole-batch bookkeeping
+    long frames_done;        // frames of every stream encoded since the last reset
+    bool fresh;              // reset since the last encode (or never encoded): state buffers are zero
     int debug, last_nf;
     // per-slot streaming (mp3mi_batch_encode_slots): a stream index is a SLOT through which one stream after another passes.
     // While slots_on is false the slots are as frames_done says (all open at frames_done when it is > 0, else all closed) and
     // every call runs the whole-batch path above; a per-slot call sets slots_on, and the slots are as slot_frames_h says.
     bool slots_on;
     std::vector<int64_t> slot_frames_h; // frames encoded by the stream open in each slot, -1: no stream open there
-    // the control block of a per-slot call -- fabs_s int64[S] | n_samples int32[S] | START list int32[S] | ctl uint8[S] | (row map) |
-    // at ctl_rate_off, by position in the START list: bits per frame int32[S] | bitrate index int32[S] (k_slot_rate) -- in
-    // pinned staging and on the device, twice (by the parity of the per-slot call: ctl_calls & 1); ev_ctl[p] is recorded behind the
-    // last reader of copy p, and the host waits for it before it writes staging p again (the per-slot call two before)
-    uint8_t *ctl_stage[2], *ctl_dev[2];
-    size_t ctl_bytes, ctl_rows_off, ctl_rate_off; // (behind the four arrays, for host-buffer calls: row_slot int32[n_rows] at ctl_rows_off)
-    size_t ctl_base_bytes;   // the block without the bitrates: all that goes up while no call writes the live bitrate arrays
-    hipEvent_t ev_ctl[2], ev_ctl_up;
-    bool ctl_used[2];
-    unsigned ctl_calls;
-    // parking (mp3mi_batch_slots_export / _import): the slot list of such a call -- int32[S] -- in pinned staging and on the device,
-    // a ring of four by call, apart from the control block's two so that a tick, a park and a resume issued in a row do not wait
-    // for each other; ev_park[p] is recorded behind the last reader of copy p, and the host waits for it before it writes staging
-    // p again (the park call four before).  Created with the first such call: a batch that never parks holds none of it.
-    int32_t *park_stage[4], *park_dev[4];
-    hipEvent_t ev_park[4];
-    bool park_used[4];
-    unsigned park_calls;
+    // the control block of a per-slot call (ctl_layout), twice, taken in turn by the per-slot calls: an entry's fence is recorded
+    // behind the last reader of its device copy, and the host waits for it before it writes the staging again (the per-slot call
+    // two before: ctl_take)
+    ctl_layout ctl_at;
+    typedef upload_ring<uint8_t, 2> ctl_ring;
+    ctl_ring ctl;
+    hipEvent_t ev_ctl_up;    // the front stream has uploaded the block (or the park list) of the call
+    // parking (mp3mi_batch_slots_export / _import): the slot list of such a call -- int32[S] --, a ring of four by call, apart from
+    // the control block's two so that a tick, a park and a resume issued in a row do not wait for each other; an entry's fence is
+    // recorded behind the last reader of its device copy, and the host waits for it before it writes the staging again (the park
+    // call four before).  Each entry is created with its first turn: a batch that never parks holds none of it.
+    typedef upload_ring<int32_t, 4> park_ring;
+    park_ring park;
     // Host-buffer calls (mp3mi_batch_encode_host_async): the call's PCM goes up and its file bytes come down chunk by
     // chunk on two copy streams of their own, beside the kernels; two calls may be in flight, so the device copies of
     // PCM and output exist twice (slot = call number & 1).  Created with the first such call.
     struct host_io {
         bool ready;
         hipStream_t h2d, d2h;
-        int16_t *pcm[2];          // [S][max_frames * 1152][C]
-        uint8_t *out[2];          // [S][out_stride]
-        uint32_t *len[2];         // [S]
         size_t out_stride;
-        hipEvent_t pcm_free[2], out_free[2]; // the slot's PCM has been read by its last kernel / its output by its last copy
-        bool pcm_used[2], out_used[2];
-        std::vector<hipEvent_t> ev_fmt[2];   // per chunk: the chunk's formatter is done
-        std::vector<hipEvent_t> t_up[2], t_dn[2]; // per chunk two events around the copy (the second is what consumers wait for)
-        // per-slot calls on host buffers with a row map (mp3mi_batch_encode_slots_host_async): the caller's rows are DENSE, one
-        // per live slot; they cross PCIe as they are, into and out of dense device buffers, and k_rows_in / k_rows_out
-        // (k_format.hip) move them to and from the rows per slot above.  Created with the first such call of a slot.
-        int16_t *pcm_rows[2];     // [n_rows][max_frames * 1152][C]
-        uint8_t *out_rows[2];     // [n_rows][the caller's out_stride]
-        size_t out_rows_cap[2];   // bytes
-        uint32_t *len_rows[2];    // [n_rows]
-        std::vector<hipEvent_t> ev_in[2]; // per chunk: the chunk's columns are in the slot rows (k_rows_in, on the upload stream)
-        unsigned hold_of[2];      // the ticket of the call hold the slot's call left in force (0: none)
-        int n_chunks[2];
-        double bytes_up[2], bytes_dn[2];
-        bool pending[2];
+        struct io_slot {
+            int16_t *pcm;             // [S][max_frames * 1152][C]
+            uint8_t *out;             // [S][out_stride]
+            uint32_t *len;            // [S]
+            fence pcm_free, out_free; // the slot's PCM has been read by its last kernel / its output by its last copy
+            std::vector<hipEvent_t> ev_fmt;     // per chunk: the chunk's formatter is done
+            std::vector<hipEvent_t> t_up, t_dn; // per chunk two events around the copy (the second is what consumers wait for)
+            // per-slot calls on host buffers with a row map (mp3mi_batch_encode_slots_host_async): the caller's rows are DENSE, one
+            // per live slot; they cross PCIe as they are, into and out of dense device buffers, and k_rows_in / k_rows_out
+            // (k_format.hip) move them to and from the rows per slot above.  Created with the first such call of a slot.
+            int16_t *pcm_rows;        // [n_rows][max_frames * 1152][C]
+            uint8_t *out_rows;        // [n_rows][the caller's out_stride]; NOT in mp3mi_batch::owned: host_rows_init regrows it
+            size_t out_rows_cap;      // bytes
+            uint32_t *len_rows;       // [n_rows]
+            std::vector<hipEvent_t> ev_in; // per chunk: the chunk's columns are in the slot rows (k_rows_in, on the upload stream)
+            unsigned hold_of;         // the ticket of the call hold the slot's call left in force (0: none)
+            int n_chunks;
+            double bytes_up, bytes_dn;
+            bool pending;
+        } slot[2];
         unsigned call_no;
         double tot_up_bytes, tot_dn_bytes, tot_up_ms, tot_dn_ms;
         long tot_calls;
@@ -176,21 +218,27 @@ struct mp3mi_batch {
     long tot_launches, tot_calls;
 };
 
-// Every entry point runs on the batch's own device whatever the calling thread's current device is, and leaves
-// the caller's current device as it found it.
-struct device_scope {
-    int prev;
-    bool ok;
-    explicit device_scope(int dev) : prev(-1), ok(true)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) { ok = false; prev = -1; return; }
-        if (prev != dev && hipSetDevice(dev) != hipSuccess) ok = false;
-    }
-    ~device_scope() { if (prev >= 0) (void) hipSetDevice(prev); }
-};
-#define ON_DEVICE(b)                                                                                     \
-    device_scope dev_scope_((b)->device);                                                                \
-    if (!dev_scope_.ok) { fprintf(stderr, "mp3mi: cannot select device %d\n", (b)->device); return MP3MI_ERR_HIP; }
+// Device and pinned buffers of a batch: allocated here and nowhere else, so that mp3mi_batch_destroy knows them all
+template <typename T> static hipError_t dev_alloc(mp3mi_batch *b, T **p, size_t bytes)
+{
+    const hipError_t e = hipMalloc((void **) p, bytes);
+    if (e == hipSuccess) b->owned.push_back({*p, false});
+    return e;
+}
+template <typename T> static hipError_t pinned_alloc(mp3mi_batch *b, T **p, size_t bytes, unsigned flags)
+{
+    const hipError_t e = hipHostMalloc((void **) p, bytes, flags);
+    if (e == hipSuccess) b->owned.push_back({*p, true});
+    return e;
+}
+// A ring entry: staging, device copy, fence -- in this order
+template <typename E> static hipError_t ring_entry_create(mp3mi_batch *b, E &en, size_t bytes)
+{
+    hipError_t e = pinned_alloc(b, &en.stage, bytes, 0);
+    if (e == hipSuccess) e = dev_alloc(b, &en.dev, bytes);
+    if (e == hipSuccess) e = en.free.create();
+    return e;
+}
 
 static const int BITRATES[15] = {0, 32, 40, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256, 320}; // src/common.c:124
 
@@ -199,25 +247,16 @@ static const int BITRATES[15] = {0, 32, 40, 48, 56, 64, 80, 96, 112, 128, 160, 1
 // the check of mp3mi_batch_create_ex and of a per-slot call's kbps_host alike.
 static bool rate_of_kbps(int ri, int k, int *bitrate_index, int *bits_per_frame)
 {
-    static const double s_freq[3] = {44.1, 48, 32}; // src/common.c:113
     int bi;
     for (bi = 1; bi < 15; bi++)
         if (BITRATES[bi] == k) break;
     if (bi == 15 || ri < 0 || ri > 2) return false;
-    const int whole_SpF = (int) (((double) 1152 / s_freq[ri]) * ((double) k / 8.0));
     *bitrate_index = bi;
-    *bits_per_frame = 8 * whole_SpF;
+    *bits_per_frame = frame_bits(1152, ri, k, 8);
     return true;
 }
 
 static int rate_idx_of(int rate_hz) { return rate_hz == 44100 ? 0 : rate_hz == 48000 ? 1 : rate_hz == 32000 ? 2 : -1; }
-
-static int have_device(void)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return 0;
-    return 1;
-}
 
 #if !defined(MP3MI_SOURCE_HASH)
 #define MP3MI_SOURCE_HASH "unknown"
@@ -281,31 +320,49 @@ extern "C" void mp3mi_batch_options_from_env(mp3mi_batch_options *o)
     if ((e = getenv("MP3MI_DROPIN_LOOKAHEAD")) && atoi(e) >= 0 && atoi(e) <= 4) o->dropin_lookahead = atoi(e);
 }
 
+// MP3MI_TEST_* flags as the kernels and the scheduler take them (checked by the caller)
+static void set_test_flags(mp3mi_batch *b, unsigned flags)
+{
+    b->test_flags = (int) (flags & 15u) | ((flags & MP3MI_TEST_CW_EXACT) ? 16 : 0) | ((flags & MP3MI_TEST_PREP_LIST) ? 32 : 0);
+    b->prep_exact = (flags & MP3MI_TEST_PREP_EXACT) ? 1 : 0;
+}
+
+// The list of what a stream carries (carried_region), once the buffers exist
+static void carried_init(mp3mi_batch *b)
+{
+    const size_t C = (size_t) b->channels;
+    const carried_region r[N_CARRIED] = {{b->psy_state, mp3mi_psy_state_size() * C, false, true},
+                                         {b->pcm_hist, sizeof(int16_t) * MP3MI_PCM_HIST * C, false, true},
+                                         {b->loop_state, mp3mi_loop_state_size(), true, true},
+                                         {b->out_base, sizeof(int64_t), true, true}, // (0: a flush before the first encode delivers nothing)
+                                         {b->carry, MP3MI_CARRY_BYTES, true, false},
+                                         {b->carry_len, sizeof(int32_t), true, true},
+                                         {b->bits_per_frame, sizeof(int32_t), true, false},  // (the live bitrate words last: an import leaves them
+                                         {b->bitrate_index, sizeof(int32_t), true, false}};  // out where the arrays hold nothing but create-time values)
+    for (int k = 0; k < N_CARRIED; k++) b->carried[k] = r[k];
+}
+
 // Fills *b step by step; on any failure the caller destroys the partially built object (every pointer and handle
-// starts out null, and mp3mi_batch_destroy skips what was never created).
+// starts out null, and mp3mi_batch_destroy skips what was never created; so does every counter and flag: only what is not zero
+// is set here).  The arguments are mp3mi_batch_create_ex's, checked there.
 static int batch_build(mp3mi_batch *b, int n_streams, int rate_hz, int channels, const int *kbps, int kbps_all, int max_frames,
                        const mp3mi_batch_options &opt)
 {
     const int ri = rate_idx_of(rate_hz);
-    if (ri < 0) return MP3MI_ERR_ARG; // the reference's L3psycho_anal exits on anything else (src/l3psy.c:170-176)
-    if (n_streams <= 0 || max_frames <= 0 || (channels != 1 && channels != 2)) return MP3MI_ERR_ARG;
     CHK(hipGetDevice(&b->device));
     b->n_streams = n_streams; b->rate_idx = ri; b->rate_hz = rate_hz; b->channels = channels;
-    b->max_frames = max_frames; b->debug = 0; b->last_nf = 0;
+    b->max_frames = max_frames;
     b->bits_per_frame_h.resize(n_streams);
     b->bitrate_index_h.resize(n_streams);
     b->kbps_h.resize(n_streams);
-    b->max_frame_bytes = 0;
-    b->ceil_kbps = 0;
     for (int s = 0; s < n_streams; s++) {
         const int k = kbps ? kbps[s] : kbps_all;
-        if (!rate_of_kbps(ri, k, &b->bitrate_index_h[s], &b->bits_per_frame_h[s])) return MP3MI_ERR_ARG;
+        (void) rate_of_kbps(ri, k, &b->bitrate_index_h[s], &b->bits_per_frame_h[s]);
         b->kbps_h[s] = k;
         if (k > b->ceil_kbps) b->ceil_kbps = k;
         if (b->bits_per_frame_h[s] / 8 > b->max_frame_bytes) b->max_frame_bytes = b->bits_per_frame_h[s] / 8;
     }
     b->slot_kbps_h.assign(b->kbps_h.begin(), b->kbps_h.end());
-    b->rate_dirty = false;
     // chunk size from a scratch budget (bytes per frame and stream of the per-chunk buffers)
     const size_t per_gc = MP3MI_HBLK_P * 4 + MP3MI_PART_P * 12 + 3 * MP3MI_HBLK_S * 4 + MP3MI_FFT_BINS * 4 + 50 * 8 + 12 * 4 +
                           2 * (sizeof(mp3mi_psy_out) + sizeof(mp3mi_loop_prep) + 576 * 8) + 576 * 8 + 576 * 2;
@@ -324,7 +381,7 @@ static int batch_build(mp3mi_batch *b, int n_streams, int rate_hz, int channels,
         if (trc == -8) return MP3MI_ERR_TABLES; // the host's libm does not reproduce the pinned tables (tables_host.cpp)
         if (trc != 0) return MP3MI_ERR_ARG;
     }
-    const size_t ngc = (size_t) n_streams * 2 * (size_t) cf * (size_t) channels;
+    const size_t S = (size_t) n_streams, ngc = S * 2 * (size_t) cf * (size_t) channels;
     {
         int least = 0, greatest = 0;
         CHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
@@ -338,36 +395,27 @@ static int batch_build(mp3mi_batch *b, int n_streams, int rate_hz, int channels,
         b->part_streams = ps;
         b->n_parts = (n_streams + ps - 1) / ps;
         b->ev_front.assign(2 * (size_t) b->n_parts, (hipEvent_t) 0);
-        b->ev_loop.assign(2 * (size_t) b->n_parts, (hipEvent_t) 0);
-        b->slot_used.assign(2 * (size_t) b->n_parts, 0);
+        b->ev_loop.assign(2 * (size_t) b->n_parts, fence());
         for (size_t i = 0; i < b->ev_front.size(); i++) {
             CHK(hipEventCreateWithFlags(&b->ev_front[i], hipEventDisableTiming));
-            CHK(hipEventCreateWithFlags(&b->ev_loop[i], hipEventDisableTiming));
+            CHK(b->ev_loop[i].create());
         }
     }
-    CHK(hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
+    CHK(b->ev_done.create());
     CHK(hipEventCreateWithFlags(&b->ev_hist, hipEventDisableTiming));
-    b->have_done = false;
-    b->last_slot = 0;
-    b->slot_base = 0;
-    b->test_flags = (int) (opt.test_flags & 15u) | ((opt.test_flags & MP3MI_TEST_CW_EXACT) ? 16 : 0) | ((opt.test_flags & MP3MI_TEST_PREP_LIST) ? 32 : 0);
-    b->prep_exact = (opt.test_flags & MP3MI_TEST_PREP_EXACT) ? 1 : 0;
-    b->hdr_flags = 0;
+    set_test_flags(b, opt.test_flags);
     b->hdr_mode = (channels == 1) ? 3 : 0;
-    b->crc = 0;
-    b->gate_total = 0; b->gate_first = 0;
     b->hold_calls = opt.call_hold != 0;
     if (b->hold_calls) {
-        CHK(hipHostMalloc((void **) &b->hold_flag_h, 64, hipHostMallocMapped));
+        CHK(pinned_alloc(b, &b->hold_flag_h, 64, hipHostMallocMapped));
         for (int i = 0; i < 16; i++) b->hold_flag_h[i] = 0;
         CHK(hipHostGetDevicePointer((void **) &b->hold_flag_d, b->hold_flag_h, 0));
     }
-    CHK(hipMalloc((void **) &b->gate_count, 2 * sizeof(unsigned))); // [0] start census, [1] frames finished in this launch
+    CHK(dev_alloc(b, &b->gate_count, 2 * sizeof(unsigned))); // [0] start census, [1] frames finished in this launch
     CHK(hipMemset(b->gate_count, 0, 2 * sizeof(unsigned)));
-    CHK(hipMalloc((void **) &b->voided, sizeof(unsigned)));
+    CHK(dev_alloc(b, &b->voided, sizeof(unsigned)));
     CHK(hipMemset(b->voided, 0, sizeof(unsigned)));
-    CHK(hipMalloc((void **) &b->status_dev, sizeof(int32_t) * (size_t) n_streams));
-    b->place_order = NULL; b->place_cost = NULL; b->place_zero = NULL; b->n_simd = 0;
+    CHK(dev_alloc(b, &b->status_dev, sizeof(int32_t) * S));
     {
         hipDeviceProp_t prop;
         int dev = 0;
@@ -375,86 +423,64 @@ static int batch_build(mp3mi_batch *b, int n_streams, int rate_hz, int channels,
         CHK(hipGetDeviceProperties(&prop, dev));
         b->n_simd = prop.multiProcessorCount * 4;
         if (n_streams >= 2 * b->n_simd) { // placement only matters when SIMDs hold several streams
-            CHK(hipMalloc((void **) &b->place_order, sizeof(int) * n_streams));
-            CHK(hipMalloc((void **) &b->place_cost, sizeof(int) * n_streams));
-            CHK(hipMalloc((void **) &b->place_zero, sizeof(unsigned) * ((size_t) n_streams + 2 * MP3MI_PLACE_KEYS + 2)));
+            CHK(dev_alloc(b, &b->place_order, sizeof(int) * S));
+            CHK(dev_alloc(b, &b->place_cost, sizeof(int) * S));
+            CHK(dev_alloc(b, &b->place_zero, sizeof(unsigned) * (S + 2 * MP3MI_PLACE_KEYS + 2)));
         }
     }
-    CHK(hipMalloc((void **) &b->T, sizeof(mp3mi_tables)));
+    CHK(dev_alloc(b, &b->T, sizeof(mp3mi_tables)));
     CHK(hipMemcpy(b->T, Th, sizeof(mp3mi_tables), hipMemcpyHostToDevice));
-    CHK(hipMalloc((void **) &b->rate_live, 2 * sizeof(int32_t) * n_streams));
-    CHK(hipMalloc((void **) &b->rate_create, 2 * sizeof(int32_t) * n_streams));
+    CHK(dev_alloc(b, &b->rate_live, 2 * sizeof(int32_t) * S));
+    CHK(dev_alloc(b, &b->rate_create, 2 * sizeof(int32_t) * S));
     b->bits_per_frame = b->rate_live;
     b->bitrate_index = b->rate_live + n_streams;
     for (int32_t *dst : {b->rate_live, b->rate_create}) {
-        CHK(hipMemcpy(dst, b->bits_per_frame_h.data(), sizeof(int32_t) * n_streams, hipMemcpyHostToDevice));
-        CHK(hipMemcpy(dst + n_streams, b->bitrate_index_h.data(), sizeof(int32_t) * n_streams, hipMemcpyHostToDevice));
+        CHK(hipMemcpy(dst, b->bits_per_frame_h.data(), sizeof(int32_t) * S, hipMemcpyHostToDevice));
+        CHK(hipMemcpy(dst + n_streams, b->bitrate_index_h.data(), sizeof(int32_t) * S, hipMemcpyHostToDevice));
     }
-    CHK(hipMalloc((void **) &b->energy_l, ngc * MP3MI_HBLK_P * sizeof(float)));
-    CHK(hipMalloc((void **) &b->part_eb, ngc * MP3MI_PART_P * sizeof(double)));
+    CHK(dev_alloc(b, &b->energy_l, ngc * MP3MI_HBLK_P * sizeof(float)));
+    CHK(dev_alloc(b, &b->part_eb, ngc * MP3MI_PART_P * sizeof(double)));
 #if defined(MP3MI_ULP_CENSUS) // (diagnostic build: two shadow copies behind the sums, mp3mi_geom::census_cb_stride)
-    CHK(hipMalloc((void **) &b->part_cb, 3 * ngc * MP3MI_PART_P * sizeof(float)));
+    CHK(dev_alloc(b, &b->part_cb, 3 * ngc * MP3MI_PART_P * sizeof(float)));
     CHK(hipMemset(b->part_cb, 0, 3 * ngc * MP3MI_PART_P * sizeof(float)));
 #else
-    CHK(hipMalloc((void **) &b->part_cb, ngc * MP3MI_PART_P * sizeof(float)));
+    CHK(dev_alloc(b, &b->part_cb, ngc * MP3MI_PART_P * sizeof(float)));
 #endif
-    CHK(hipMalloc((void **) &b->energy_s, ngc * 3 * MP3MI_HBLK_S * sizeof(float)));
-    CHK(hipMalloc((void **) &b->hist6, ngc * 12 * sizeof(float)));
-    CHK(hipMalloc((void **) &b->fft_bins, ngc * MP3MI_FFT_BINS * sizeof(float)));
-    CHK(hipMalloc((void **) &b->cw_mid, ngc * 50 * sizeof(double)));
-    CHK(hipMalloc((void **) &b->cw_fix, mp3mi_cw_fixlist_bytes(ngc)));
+    CHK(dev_alloc(b, &b->energy_s, ngc * 3 * MP3MI_HBLK_S * sizeof(float)));
+    CHK(dev_alloc(b, &b->hist6, ngc * 12 * sizeof(float)));
+    CHK(dev_alloc(b, &b->fft_bins, ngc * MP3MI_FFT_BINS * sizeof(float)));
+    CHK(dev_alloc(b, &b->cw_mid, ngc * 50 * sizeof(double)));
+    CHK(dev_alloc(b, &b->cw_fix, mp3mi_cw_fixlist_bytes(ngc)));
     CHK(hipMemset(b->cw_fix, 0, sizeof(mp3mi_cw_fixlist)));
-    CHK(hipMalloc((void **) &b->prep_fix, mp3mi_prep_fixlist_bytes(ngc)));
+    CHK(dev_alloc(b, &b->prep_fix, mp3mi_prep_fixlist_bytes(ngc)));
     CHK(hipMemset(b->prep_fix, 0, sizeof(mp3mi_prep_fixlist)));
     for (int i = 0; i < 2; i++) {
-        CHK(hipMalloc((void **) &b->xr[i], ngc * 576 * sizeof(double)));
-        CHK(hipMalloc((void **) &b->psy[i], ngc * sizeof(mp3mi_psy_out)));
-        CHK(hipMalloc((void **) &b->prep[i], ngc * sizeof(mp3mi_loop_prep)));
+        CHK(dev_alloc(b, &b->xr[i], ngc * 576 * sizeof(double)));
+        CHK(dev_alloc(b, &b->psy[i], ngc * sizeof(mp3mi_psy_out)));
+        CHK(dev_alloc(b, &b->prep[i], ngc * sizeof(mp3mi_loop_prep)));
     }
-    CHK(hipMalloc((void **) &b->sbs, (ngc + (size_t) n_streams * channels) * 576 * sizeof(double)));
-    CHK(hipMalloc((void **) &b->ix, ngc * 576 * sizeof(int16_t)));
-    CHK(hipMalloc((void **) &b->side, (size_t) n_streams * (size_t) cf * sizeof(mp3mi_frame_side)));
-    CHK(hipMalloc((void **) &b->psy_state, mp3mi_psy_state_size() * (size_t) n_streams * channels));
-    CHK(hipMalloc((void **) &b->loop_state, mp3mi_loop_state_size() * (size_t) n_streams));
-    CHK(hipMalloc((void **) &b->pcm_hist, sizeof(int16_t) * MP3MI_PCM_HIST * (size_t) channels * (size_t) n_streams));
-    CHK(hipMalloc((void **) &b->out_base, sizeof(int64_t) * (size_t) n_streams));
-    CHK(hipMalloc((void **) &b->carry, (size_t) MP3MI_CARRY_BYTES * (size_t) n_streams));
-    CHK(hipMalloc((void **) &b->carry_len, sizeof(int32_t) * (size_t) n_streams));
+    CHK(dev_alloc(b, &b->sbs, (ngc + S * channels) * 576 * sizeof(double)));
+    CHK(dev_alloc(b, &b->ix, ngc * 576 * sizeof(int16_t)));
+    CHK(dev_alloc(b, &b->side, S * (size_t) cf * sizeof(mp3mi_frame_side)));
+    CHK(dev_alloc(b, &b->psy_state, mp3mi_psy_state_size() * S * channels));
+    CHK(dev_alloc(b, &b->loop_state, mp3mi_loop_state_size() * S));
+    CHK(dev_alloc(b, &b->pcm_hist, sizeof(int16_t) * MP3MI_PCM_HIST * (size_t) channels * S));
+    CHK(dev_alloc(b, &b->out_base, sizeof(int64_t) * S));
+    CHK(dev_alloc(b, &b->carry, (size_t) MP3MI_CARRY_BYTES * S));
+    CHK(dev_alloc(b, &b->carry_len, sizeof(int32_t) * S));
+    carried_init(b);
     // (zero state from the start: a per-slot call runs every slot's stream through the kernels, the closed ones on silence, and a
     // slot that never had a stream must hold a valid -- fresh -- encoder state for that)
-    CHK(hipMemset(b->psy_state, 0, mp3mi_psy_state_size() * (size_t) n_streams * channels));
-    CHK(hipMemset(b->loop_state, 0, mp3mi_loop_state_size() * (size_t) n_streams));
-    CHK(hipMemset(b->pcm_hist, 0, sizeof(int16_t) * MP3MI_PCM_HIST * (size_t) channels * (size_t) n_streams));
-    CHK(hipMemset(b->out_base, 0, sizeof(int64_t) * (size_t) n_streams)); // a flush before the first encode delivers nothing
-    CHK(hipMemset(b->carry_len, 0, sizeof(int32_t) * (size_t) n_streams));
-    b->frames_done = 0;
-    b->fresh = false;
-    b->sb_dbg = NULL;
-    b->slots_on = false;
-    b->slot_frames_h.assign((size_t) n_streams, -1);
-    b->ctl_rows_off = ((size_t) n_streams * 17 + 3) & ~(size_t) 3;
-    b->ctl_rate_off = b->ctl_rows_off + (size_t) n_streams * 4;
-    b->ctl_base_bytes = (b->ctl_rate_off + 255) & ~(size_t) 255;
-    b->ctl_bytes = (b->ctl_rate_off + (size_t) n_streams * 8 + 255) & ~(size_t) 255;
-    for (int i = 0; i < 2; i++) {
-        CHK(hipHostMalloc((void **) &b->ctl_stage[i], b->ctl_bytes, 0));
-        CHK(hipMalloc((void **) &b->ctl_dev[i], b->ctl_bytes));
-        CHK(hipEventCreateWithFlags(&b->ev_ctl[i], hipEventDisableTiming));
-        b->ctl_used[i] = false;
-    }
+    for (const carried_region &r : b->carried)
+        if (r.zero) CHK(hipMemset(r.base, 0, r.bytes * S));
+    b->slot_frames_h.assign(S, -1);
+    b->ctl_at.init(S);
+    for (mp3mi_batch::ctl_ring::entry &en : b->ctl.e) CHK(ring_entry_create(b, en, b->ctl_at.bytes));
     CHK(hipEventCreateWithFlags(&b->ev_ctl_up, hipEventDisableTiming));
-    b->ctl_calls = 0;
-    for (int i = 0; i < 2; i++) {
-        CHK(hipEventCreate(&b->ts[i].ev0));
-        CHK(hipEventCreate(&b->ts[i].ev1));
-        b->ts[i].launches = 0;
-        b->ts[i].pending = false;
+    for (mp3mi_batch::timing_set &ts : b->ts) {
+        CHK(hipEventCreate(&ts.ev0));
+        CHK(hipEventCreate(&ts.ev1));
     }
-    b->call_no = 0;
-    b->last_loop_ms = b->last_all_ms = 0;
-    b->last_launches = 0;
-    b->tot_loop_ms = b->tot_all_ms = 0;
-    b->tot_launches = b->tot_calls = 0;
     return MP3MI_OK;
 }
 
@@ -507,67 +533,50 @@ extern "C" void mp3mi_batch_destroy(mp3mi_batch *b)
     if (!b) return;
     device_scope ds(b->device);
     hold_release(b);
-    if (b->stream) hipStreamSynchronize(b->stream);
-    if (b->lstream) hipStreamSynchronize(b->lstream);
-    void *bufs[] = {b->T, b->rate_live, b->rate_create, b->energy_l, b->energy_s, b->hist6, b->fft_bins, b->cw_mid, b->cw_fix,
-                    b->part_eb, b->part_cb, b->xr[0], b->xr[1], b->psy[0], b->psy[1], b->prep[0], b->prep[1], b->prep_fix, b->sbs, b->ix, b->side,
-                    b->psy_state, b->loop_state, b->pcm_hist, b->out_base, b->carry, b->carry_len, b->gate_count, b->place_order, b->place_cost, b->place_zero, b->sb_dbg, b->voided, b->status_dev,
-                    b->ctl_dev[0], b->ctl_dev[1]};
-    for (void *p : bufs)
-        if (p) hipFree(p);
-    for (hipEvent_t e : b->ev_front) if (e) hipEventDestroy(e);
-    for (hipEvent_t e : b->ev_loop) if (e) hipEventDestroy(e);
-    for (int i = 0; i < 2; i++)
-        if (b->ctl_stage[i]) hipHostFree(b->ctl_stage[i]);
-    for (int i = 0; i < 4; i++) {
-        if (b->park_stage[i]) hipHostFree(b->park_stage[i]);
-        if (b->park_dev[i]) hipFree(b->park_dev[i]);
-        if (b->ev_park[i]) hipEventDestroy(b->ev_park[i]);
+    mp3mi_batch::host_io &H = b->hio;
+    for (hipStream_t st : {b->stream, b->lstream, H.h2d, H.d2h}) // (whatever exists, also after a build that failed half-way)
+        if (st) hipStreamSynchronize(st);
+    // the buffers: what dev_alloc / pinned_alloc noted, the last first, and the one kept by hand
+    for (size_t i = b->owned.size(); i-- > 0;) {
+        if (b->owned[i].pinned) hipHostFree(b->owned[i].p);
+        else hipFree(b->owned[i].p);
     }
-    hipEvent_t evs[] = {b->ts[0].ev0, b->ts[0].ev1, b->ts[1].ev0, b->ts[1].ev1, b->ev_done, b->ev_hist, b->ev_ctl[0], b->ev_ctl[1], b->ev_ctl_up};
+    for (mp3mi_batch::host_io::io_slot &io : H.slot)
+        if (io.out_rows) hipFree(io.out_rows);
+    // the fences, then the plain events
+    b->ev_done.destroy();
+    for (fence &f : b->ev_loop) f.destroy();
+    for (mp3mi_batch::ctl_ring::entry &en : b->ctl.e) en.free.destroy();
+    for (mp3mi_batch::park_ring::entry &en : b->park.e) en.free.destroy();
+    std::vector<hipEvent_t> evs = {b->ev_hist, b->ev_ctl_up, b->ts[0].ev0, b->ts[0].ev1, b->ts[1].ev0, b->ts[1].ev1};
+    for (const std::vector<hipEvent_t> *v : {&b->ev_front, &b->ts[0].loop_ev, &b->ts[1].loop_ev}) evs.insert(evs.end(), v->begin(), v->end());
+    for (mp3mi_batch::host_io::io_slot &io : H.slot) {
+        io.pcm_free.destroy();
+        io.out_free.destroy();
+        for (const std::vector<hipEvent_t> *v : {&io.ev_fmt, &io.t_up, &io.t_dn, &io.ev_in}) evs.insert(evs.end(), v->begin(), v->end());
+    }
     for (hipEvent_t e : evs)
         if (e) hipEventDestroy(e);
-    for (int k = 0; k < 2; k++)
-        for (size_t i = 0; i < b->ts[k].loop_ev.size(); i++) hipEventDestroy(b->ts[k].loop_ev[i]);
-    {   // (whatever of the host-buffer state exists, also after an allocation that failed half-way)
-        if (b->hio.h2d) hipStreamSynchronize(b->hio.h2d);
-        if (b->hio.d2h) hipStreamSynchronize(b->hio.d2h);
-        for (int i = 0; i < 2; i++) {
-            if (b->hio.pcm[i]) hipFree(b->hio.pcm[i]);
-            if (b->hio.out[i]) hipFree(b->hio.out[i]);
-            if (b->hio.len[i]) hipFree(b->hio.len[i]);
-            if (b->hio.pcm_rows[i]) hipFree(b->hio.pcm_rows[i]);
-            if (b->hio.out_rows[i]) hipFree(b->hio.out_rows[i]);
-            if (b->hio.len_rows[i]) hipFree(b->hio.len_rows[i]);
-            if (b->hio.pcm_free[i]) hipEventDestroy(b->hio.pcm_free[i]);
-            if (b->hio.out_free[i]) hipEventDestroy(b->hio.out_free[i]);
-            for (std::vector<hipEvent_t> *v : {&b->hio.ev_fmt[i], &b->hio.t_up[i], &b->hio.t_dn[i], &b->hio.ev_in[i]})
-                for (hipEvent_t e : *v) hipEventDestroy(e);
-        }
-        if (b->hio.h2d) hipStreamDestroy(b->hio.h2d);
-        if (b->hio.d2h) hipStreamDestroy(b->hio.d2h);
-    }
-    if (b->stream) hipStreamDestroy(b->stream);
-    if (b->lstream) hipStreamDestroy(b->lstream);
-    if (b->hold_flag_h) hipHostFree(b->hold_flag_h);
+    for (hipStream_t st : {H.h2d, H.d2h, b->stream, b->lstream})
+        if (st) hipStreamDestroy(st);
     delete b;
 }
 
-extern "C" size_t mp3mi_batch_out_stride(const mp3mi_batch *b, int n_frames)
+// The least out_stride a call of n_frames takes: whole frames, the byte under construction that close writes, and -- for
+// streaming calls -- the bytes an earlier call formatted but could not deliver yet, which lead the row
+static size_t min_out_stride(const mp3mi_batch *b, int n_frames, bool streaming)
 {
-    // whole frames, the byte under construction that close writes, and -- for streaming calls -- the bytes an
-    // earlier call formatted but could not deliver yet, which lead the row
-    size_t n = (size_t) n_frames * (size_t) b->max_frame_bytes + 1 + MP3MI_CARRY_BYTES;
-    return (n + 255) & ~(size_t) 255;
+    return (size_t) n_frames * (size_t) b->max_frame_bytes + 1 + (streaming ? MP3MI_CARRY_BYTES : 0);
 }
+
+extern "C" size_t mp3mi_batch_out_stride(const mp3mi_batch *b, int n_frames) { return (min_out_stride(b, n_frames, true) + 255) & ~(size_t) 255; }
 
 extern "C" void mp3mi_batch_debug_enable(mp3mi_batch *b, int on) { b->debug = on; }
 
 extern "C" int mp3mi_batch_set_test_flags(mp3mi_batch *b, unsigned flags)
 {
     if (!b || (flags & ~(unsigned) (MP3MI_TEST_ALL_EXACT | MP3MI_TEST_PREP_LIST))) return MP3MI_ERR_ARG;
-    b->test_flags = (int) (flags & 15u) | ((flags & MP3MI_TEST_CW_EXACT) ? 16 : 0) | ((flags & MP3MI_TEST_PREP_LIST) ? 32 : 0);
-    b->prep_exact = (flags & MP3MI_TEST_PREP_EXACT) ? 1 : 0;
+    set_test_flags(b, flags);
     return MP3MI_OK;
 }
 
@@ -607,16 +616,13 @@ struct host_call { // a call on host buffers (mp3mi_batch_encode_host_async): wh
     int n_rows;
     const int32_t *rows_host, *rows_dev;
 };
-struct slot_call { // a per-slot call (mp3mi_batch_encode_slots): its control block on the device (mp3mi_batch::ctl_dev)
-    const int64_t *fabs;  // [S] index of the call's first frame in the stream of each slot
-    const int32_t *ns;    // [S] valid samples per channel of each slot in the call
-    const int32_t *list;  // [n_start] the slots that START
-    const uint8_t *ctl;   // [S] MP3MI_SLOT_DEV_* bits
+struct slot_call { // a per-slot call (mp3mi_batch_encode_slots)
+    mp3mi_batch::ctl_ring::entry *blk; // its control block: the ring entry the call took
+    ctl_block dev;        // ... and the fields of the device copy
     int n_start;
-    const int32_t *rate_bits; // [n_start] bits per frame, then at [S] the bitrate index, of the streams that START, by position in
-                              // `list`; NULL: the live bitrate arrays hold the create-time values and stay as they are
+    bool set_rates;       // the START slots' bitrates go into the live arrays (dev.rate_bits / rate_index); false: the arrays hold
+                          // the create-time values and stay as they are
     bool any_continue;    // a stream that earlier calls began goes on in the call: its carried bytes lead its row
-    int par;              // which copy of the control block
 };
 static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_samples_dev, int n_frames, uint8_t *out_dev,
                        size_t out_stride, uint32_t *out_len_dev, bool whole_file, const host_call *hc = NULL, const slot_call *sc = NULL);
@@ -658,14 +664,10 @@ static int rates_restore(mp3mi_batch *b)
 // its main() starts (all zero).  Enqueued on the front stream behind whatever is still running.
 static int reset_impl(mp3mi_batch *b)
 {
-    const int S = b->n_streams, C = b->channels;
     if (rates_restore(b) != MP3MI_OK) return MP3MI_ERR_HIP;
-    if (b->have_done) CHK(hipStreamWaitEvent(b->stream, b->ev_done, 0)); // the previous call's kernels may still be running on the loop stream
-    CHK(hipMemsetAsync(b->psy_state, 0, mp3mi_psy_state_size() * (size_t) S * C, b->stream));
-    CHK(hipMemsetAsync(b->loop_state, 0, mp3mi_loop_state_size() * (size_t) S, b->stream));
-    CHK(hipMemsetAsync(b->pcm_hist, 0, sizeof(int16_t) * MP3MI_PCM_HIST * (size_t) C * (size_t) S, b->stream));
-    CHK(hipMemsetAsync(b->out_base, 0, sizeof(int64_t) * (size_t) S, b->stream));
-    CHK(hipMemsetAsync(b->carry_len, 0, sizeof(int32_t) * (size_t) S, b->stream));
+    CHK(b->ev_done.wait_on(b->stream)); // the previous call's kernels may still be running on the loop stream
+    for (const carried_region &r : b->carried) // (all on the front stream, the loop stream's regions too: behind ev_done)
+        if (r.zero) CHK(hipMemsetAsync(r.base, 0, r.bytes * (size_t) b->n_streams, b->stream));
     b->frames_done = 0;
     b->fresh = true;
     b->slots_on = false;
@@ -701,10 +703,13 @@ static void slot_frames_now(const mp3mi_batch *b, int64_t *f)
     for (int s = 0; s < b->n_streams; s++) f[s] = b->slots_on ? b->slot_frames_h[s] : (b->frames_done > 0 ? (int64_t) b->frames_done : -1);
 }
 
-// When every slot is open at the same frame, or none is, the per-slot bookkeeping hands over to the whole-batch one: the next
-// call then runs exactly as if there had never been a per-slot call (a batch whose streams all began together)
-static void slots_settle(mp3mi_batch *b)
+// The per-slot bookkeeping is in force, with the slots as f says -- unless every slot is open at the same frame: then it hands over to
+// the whole-batch one, and the next call runs exactly as if there had never been a per-slot call (a batch whose streams all
+// began together)
+static void slots_settle(mp3mi_batch *b, const std::vector<int64_t> &f)
 {
+    b->slot_frames_h = f;
+    b->slots_on = true;
     const int64_t f0 = b->slot_frames_h[0];
     for (int s = 1; s < b->n_streams; s++)
         if (b->slot_frames_h[s] != f0) return;
@@ -716,11 +721,10 @@ static void slots_settle(mp3mi_batch *b)
 
 // Writes the staging copy of the control block this per-slot call takes (waits for the per-slot call two before, whose kernels
 // read the device copy of the same parity and whose upload read this staging)
-static int ctl_take(mp3mi_batch *b, int *par)
+static int ctl_take(mp3mi_batch *b, mp3mi_batch::ctl_ring::entry **blk)
 {
-    const int p = (int) (b->ctl_calls & 1u);
-    if (b->ctl_used[p]) CHK(hipEventSynchronize(b->ev_ctl[p]));
-    *par = p;
+    *blk = &b->ctl.take();
+    CHK((*blk)->free.sync());
     return MP3MI_OK;
 }
 
@@ -751,7 +755,7 @@ static int slots_impl(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, cons
                       const int32_t *kbps_host, uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev, host_call *hc = NULL)
 {
     if (!b || !pcm_dev || !ctl_host || !out_dev || !out_len_dev || n_frames <= 0 || n_frames > b->max_frames) return MP3MI_ERR_ARG;
-    if (out_stride < (size_t) n_frames * (size_t) b->max_frame_bytes + 1 + MP3MI_CARRY_BYTES) return MP3MI_ERR_ARG;
+    if (out_stride < min_out_stride(b, n_frames, true)) return MP3MI_ERR_ARG;
     const int S = b->n_streams;
     const int32_t full = (int32_t) n_frames * 1152;
     std::vector<int64_t> f((size_t) S);
@@ -760,16 +764,13 @@ static int slots_impl(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, cons
     if (!slots_rules_ok(b, f.data(), n_frames, ctl_host, n_samples_host, kbps_host)) return MP3MI_ERR_ARG;
     ON_DEVICE(b);
     slot_call sc;
-    if (ctl_take(b, &sc.par) != MP3MI_OK) return MP3MI_ERR_HIP;
-    uint8_t *blk = b->ctl_stage[sc.par];
+    if (ctl_take(b, &sc.blk) != MP3MI_OK) return MP3MI_ERR_HIP;
+    const ctl_block st = b->ctl_at.at(sc.blk->stage); // the staging copy: written here
+    sc.dev = b->ctl_at.at(sc.blk->dev);
     if (hc && hc->rows_host) {
-        memcpy(blk + b->ctl_rows_off, hc->rows_host, sizeof(int32_t) * (size_t) hc->n_rows);
-        hc->rows_dev = (const int32_t *) (b->ctl_dev[sc.par] + b->ctl_rows_off);
+        memcpy(st.rows, hc->rows_host, sizeof(int32_t) * (size_t) hc->n_rows);
+        hc->rows_dev = sc.dev.rows;
     }
-    int64_t *fabs = (int64_t *) blk;
-    int32_t *ns = (int32_t *) (blk + 8 * (size_t) S), *list = (int32_t *) (blk + 12 * (size_t) S);
-    uint8_t *ctl = blk + 16 * (size_t) S;
-    int32_t *rate_bits = (int32_t *) (blk + b->ctl_rate_off), *rate_index = rate_bits + S; // by position in the START list
     std::vector<int32_t> kb(b->slot_kbps_h);
     bool other_rate = false; // a stream STARTs at another bitrate than its slot was created with
     sc.n_start = 0;
@@ -777,18 +778,18 @@ static int slots_impl(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, cons
     for (int s = 0; s < S; s++) {
         const int c = ctl_host[s];
         const bool open = f[s] >= 0, start = c & MP3MI_SLOT_START, part = open || start;
-        fabs[s] = (start || !open) ? 0 : f[s];
-        ns[s] = n_samples_host ? n_samples_host[s] : (part ? full : 0);
-        ctl[s] = (uint8_t) ((c & MP3MI_SLOT_START ? MP3MI_SLOT_DEV_START : 0) | (c & MP3MI_SLOT_END ? MP3MI_SLOT_DEV_END : 0) |
+        st.fabs[s] = (start || !open) ? 0 : f[s];
+        st.n_samples[s] = n_samples_host ? n_samples_host[s] : (part ? full : 0);
+        st.ctl[s] = (uint8_t) ((c & MP3MI_SLOT_START ? MP3MI_SLOT_DEV_START : 0) | (c & MP3MI_SLOT_END ? MP3MI_SLOT_DEV_END : 0) |
                             (part ? MP3MI_SLOT_DEV_ACTIVE : 0));
         if (start) {
             kb[s] = (kbps_host && kbps_host[s]) ? kbps_host[s] : b->kbps_h[s];
             int bi = 0, bits = 0;
             (void) rate_of_kbps(b->rate_idx, kb[s], &bi, &bits); // (checked: slots_rules_ok, create)
-            rate_bits[sc.n_start] = bits;
-            rate_index[sc.n_start] = bi;
+            st.rate_bits[sc.n_start] = bits;
+            st.rate_index[sc.n_start] = bi;
             other_rate |= kb[s] != b->kbps_h[s];
-            list[sc.n_start++] = s;
+            st.list[sc.n_start++] = s;
         } else if (open)
             sc.any_continue = true;
         if (c & MP3MI_SLOT_END) kb[s] = b->kbps_h[s]; // the stream takes its bitrate with it
@@ -796,15 +797,10 @@ static int slots_impl(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, cons
     // the START slots' bitrates go into the live arrays (encode_impl) once any slot of the batch may hold another than its
     // create-time one -- a START with kbps 0, or without kbps_host, then brings its slot back; a batch that never saw another
     // bitrate launches what it always launched
-    sc.rate_bits = (b->rate_dirty || other_rate) ? (const int32_t *) (b->ctl_dev[sc.par] + b->ctl_rate_off) : NULL;
-    const uint8_t *dev = b->ctl_dev[sc.par];
-    sc.fabs = (const int64_t *) dev;
-    sc.ns = (const int32_t *) (dev + 8 * (size_t) S);
-    sc.list = (const int32_t *) (dev + 12 * (size_t) S);
-    sc.ctl = dev + 16 * (size_t) S;
+    sc.set_rates = b->rate_dirty || other_rate;
     const int rc = encode_impl(b, pcm_dev, NULL, n_frames, out_dev, out_stride, out_len_dev, false, hc, &sc);
     if (rc != MP3MI_OK) return rc;
-    b->ctl_calls++;
+    b->ctl.next();
     b->slot_kbps_h.swap(kb);
     b->rate_dirty |= other_rate;
     for (int s = 0; s < S; s++) {
@@ -813,9 +809,7 @@ static int slots_impl(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, cons
         if (c & MP3MI_SLOT_END) f[s] = -1;
         else if (f[s] >= 0) f[s] += n_frames;
     }
-    b->slot_frames_h.assign(f.begin(), f.end());
-    b->slots_on = true;
-    slots_settle(b);
+    slots_settle(b, f);
     return MP3MI_OK;
 }
 
@@ -860,8 +854,7 @@ extern "C" int mp3mi_batch_encode_next(mp3mi_batch *b, const int16_t *pcm_dev, i
             std::vector<uint8_t> ctl((size_t) b->n_streams, 0);
             return slots_impl(b, pcm_dev, n_frames, ctl.data(), NULL, NULL, out_dev, out_stride, out_len_dev);
         }
-        if (!pcm_dev || !out_dev || !out_len_dev || n_frames <= 0 || n_frames > b->max_frames ||
-            out_stride < (size_t) n_frames * (size_t) b->max_frame_bytes + 1 + MP3MI_CARRY_BYTES)
+        if (!pcm_dev || !out_dev || !out_len_dev || n_frames <= 0 || n_frames > b->max_frames || out_stride < min_out_stride(b, n_frames, true))
             return MP3MI_ERR_ARG; // (before the bookkeeping changes)
         b->slots_on = false;
         b->frames_done = 0;
@@ -870,98 +863,113 @@ extern "C" int mp3mi_batch_encode_next(mp3mi_batch *b, const int16_t *pcm_dev, i
     return encode_impl(b, pcm_dev, NULL, n_frames, out_dev, out_stride, out_len_dev, false);
 }
 
+// What a call is to the kernels beyond the frames of a chunk, and its geometry (mp3mi_geom) for frames [f0, f0 + nf) -- a chunk;
+// 0, 0: no frames, a flush -- and the n streams from s0: the whole batch's (s0 = 0, n = n_streams), or a PART's, which is the
+// whole batch's with every per-stream pointer advanced to the part's first stream.
+struct call_shape {
+    int n_frames;
+    const int32_t *n_samples; // device, per stream (mp3mi_geom::n_samples), or NULL
+    long fabs0;               // frames of every stream before the call (a per-slot call: 0, and ...)
+    const int64_t *fabs_s;    // ... device, per slot (mp3mi_geom::fabs_s), with
+    const uint8_t *slot_ctl;  // device, per slot: MP3MI_SLOT_DEV_* (mp3mi_geom::slot_ctl); both NULL otherwise
+    bool whole_file;
+};
+static mp3mi_geom call_geom(const mp3mi_batch *b, const call_shape &c, int f0, int nf, size_t s0, int n)
+{
+    mp3mi_geom g = mp3mi_make_geom(n, b->channels, b->rate_idx, c.n_frames, f0, nf);
+    g.test_flags = b->test_flags;
+    g.n_samples = c.n_samples ? c.n_samples + s0 : NULL;
+    g.hdr_flags |= b->hdr_flags;
+    g.hdr_mode = b->hdr_mode;
+    g.crc = b->crc;
+    g.fabs0 = c.fabs0;
+    g.fabs_s = c.fabs_s ? c.fabs_s + s0 : NULL;
+    g.slot_ctl = c.slot_ctl ? c.slot_ctl + s0 : NULL;
+    g.hist = b->pcm_hist + s0 * MP3MI_PCM_HIST * (size_t) b->channels;
+    g.out_base = c.whole_file ? NULL : b->out_base + s0;
+    g.whole_file = c.whole_file ? 1 : 0;
+#if defined(MP3MI_ULP_CENSUS)
+    g.census_cb_stride = (size_t) b->n_streams * 2 * (size_t) b->chunk_frames * (size_t) b->channels * MP3MI_PART_P;
+#endif
+    return g;
+}
+
 extern "C" int mp3mi_batch_flush(mp3mi_batch *b, uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev)
 {
-    if (!b || !out_dev || !out_len_dev || out_stride < (size_t) MP3MI_CARRY_BYTES + 1) return MP3MI_ERR_ARG;
+    if (!b || !out_dev || !out_len_dev || out_stride < min_out_stride(b, 0, true)) return MP3MI_ERR_ARG;
     ON_DEVICE(b);
     hold_release(b);
+    const int S = b->n_streams;
+    call_shape cs = {0, NULL, b->frames_done, NULL, NULL, false};
+    mp3mi_batch::ctl_ring::entry *blk = NULL;
     if (b->slots_on) { // some slots open, not all at the same frame (slots_settle), or none: end the open ones
-        const int S = b->n_streams;
-        int par = 0, n_open = 0;
+        int n_open = 0;
         for (int s = 0; s < S; s++) n_open += b->slot_frames_h[s] >= 0;
         if (n_open == 0) { // nothing to end; the ended streams' status stays in their slots
             CHK(hipMemsetAsync(out_len_dev, 0, sizeof(uint32_t) * (size_t) S, b->lstream));
             return MP3MI_OK;
         }
-        if (ctl_take(b, &par) != MP3MI_OK) return MP3MI_ERR_HIP;
-        uint8_t *blk = b->ctl_stage[par];
-        memset(blk, 0, b->ctl_base_bytes); // (k_stream_tail reads fabs_s and ctl only)
+        if (ctl_take(b, &blk) != MP3MI_OK) return MP3MI_ERR_HIP;
+        memset(blk->stage, 0, b->ctl_at.base_bytes); // (k_stream_tail reads fabs_s and ctl only)
+        const ctl_block st = b->ctl_at.at(blk->stage), dev = b->ctl_at.at(blk->dev);
         for (int s = 0; s < S; s++) {
             const bool open = b->slot_frames_h[s] >= 0;
-            ((int64_t *) blk)[s] = open ? b->slot_frames_h[s] : 0;
-            blk[16 * (size_t) S + s] = open ? MP3MI_SLOT_DEV_ACTIVE : 0;
+            st.fabs[s] = open ? b->slot_frames_h[s] : 0;
+            st.ctl[s] = open ? MP3MI_SLOT_DEV_ACTIVE : 0;
         }
-        CHK(hipMemcpyAsync(b->ctl_dev[par], blk, b->ctl_base_bytes, hipMemcpyHostToDevice, b->lstream));
-        mp3mi_geom g = mp3mi_make_geom(S, b->channels, b->rate_idx, 0, 0, 0);
-        g.crc = b->crc;
-        g.fabs_s = (const int64_t *) b->ctl_dev[par];
-        g.slot_ctl = b->ctl_dev[par] + 16 * (size_t) S;
-        mp3mi_launch_stream_tail(g, 1, (int32_t *) b->loop_state, (int) (mp3mi_loop_state_size() / 4), b->bits_per_frame, out_dev, out_stride,
-                                 b->out_base, b->carry, b->carry_len, out_len_dev, b->voided, b->lstream);
-        CHK(hipGetLastError());
-        mp3mi_launch_status_gather(S, (const int32_t *) b->loop_state, (int) (mp3mi_loop_state_size() / 4), b->status_dev, b->lstream);
-        CHK(hipGetLastError());
-        CHK(hipEventRecord(b->ev_ctl[par], b->lstream));
-        b->ctl_used[par] = true;
-        b->ctl_calls++;
-        b->status_kept = true;
-        CHK(hipEventRecord(b->ev_done, b->lstream));
-        b->have_done = true;
-        return reset_impl(b);
-    }
-    if (b->fresh) { // nothing was encoded since the reset: no file body (the reference would write one byte; see mp3mi.h)
-        CHK(hipMemsetAsync(out_len_dev, 0, sizeof(uint32_t) * (size_t) b->n_streams, b->lstream));
+        CHK(hipMemcpyAsync(blk->dev, blk->stage, b->ctl_at.base_bytes, hipMemcpyHostToDevice, b->lstream));
+        cs.fabs0 = 0;
+        cs.fabs_s = dev.fabs;
+        cs.slot_ctl = dev.ctl;
+    } else if (b->fresh) { // nothing was encoded since the reset: no file body (the reference would write one byte; see mp3mi.h)
+        CHK(hipMemsetAsync(out_len_dev, 0, sizeof(uint32_t) * (size_t) S, b->lstream));
         return MP3MI_OK;
     }
-    mp3mi_geom g = mp3mi_make_geom(b->n_streams, b->channels, b->rate_idx, 0, 0, 0);
-    g.fabs0 = b->frames_done;
-    g.crc = b->crc;
-    mp3mi_launch_stream_tail(g, 1, (int32_t *) b->loop_state, (int) (mp3mi_loop_state_size() / 4), b->bits_per_frame, out_dev, out_stride,
-                             b->out_base, b->carry, b->carry_len, out_len_dev, b->voided, b->lstream); // behind the last call's k_format
+    // the tail of either kind of flush
+    const int words = (int) (mp3mi_loop_state_size() / 4);
+    mp3mi_launch_stream_tail(call_geom(b, cs, 0, 0, 0, S), 1, (int32_t *) b->loop_state, words, b->bits_per_frame, out_dev, out_stride, b->out_base,
+                             b->carry, b->carry_len, out_len_dev, b->voided, b->lstream); // behind the last call's k_format
     CHK(hipGetLastError());
     // the streams' status words go with the state the reset clears: keep what mp3mi_batch_stream_status is asked for
     // after the flush (until the next encode starts new streams)
-    mp3mi_launch_status_gather(b->n_streams, (const int32_t *) b->loop_state, (int) (mp3mi_loop_state_size() / 4), b->status_dev, b->lstream);
+    mp3mi_launch_status_gather(S, (const int32_t *) b->loop_state, words, b->status_dev, b->lstream);
     CHK(hipGetLastError());
+    if (blk) {
+        CHK(blk->free.record(b->lstream));
+        b->ctl.next();
+    }
     b->status_kept = true;
-    CHK(hipEventRecord(b->ev_done, b->lstream));
-    b->have_done = true;
+    CHK(b->ev_done.record(b->lstream));
     return reset_impl(b); // the streams are over: the next encode_next starts new ones
 }
 
 // ---- parking and resuming streams (mp3mi_batch_slots_export / mp3mi_batch_slots_import) ----
-// Everything a stream carries from call to call is a record per slot in eight regions.  The state record of a parked stream
-// holds them one after the other, each at a multiple of 16 bytes; front / loop: the regions by the HIP stream that owns them
-// (encode_impl), with their offsets.  Returns the record's size.
+// Everything a stream carries from call to call is a record per slot in the regions of mp3mi_batch::carried.  The state record
+// of a parked stream holds them one after the other, in that order, each at a multiple of 16 bytes; front / loop: the regions
+// by the HIP stream that owns them (encode_impl), with their offsets.  Returns the record's size.
 static size_t park_tables(const mp3mi_batch *b, mp3mi_park_table *front, mp3mi_park_table *loop)
 {
-    const size_t C = (size_t) b->channels;
-    mp3mi_park_region r[8] = {{b->psy_state, (uint32_t) (mp3mi_psy_state_size() * C), 0},
-                              {b->pcm_hist, (uint32_t) (sizeof(int16_t) * MP3MI_PCM_HIST * C), 0},
-                              {b->loop_state, (uint32_t) mp3mi_loop_state_size(), 0},
-                              {b->out_base, (uint32_t) sizeof(int64_t), 0},
-                              {b->carry, MP3MI_CARRY_BYTES, 0},
-                              {b->carry_len, (uint32_t) sizeof(int32_t), 0},
-                              {b->bits_per_frame, (uint32_t) sizeof(int32_t), 0},   // (the live bitrate words last: an import leaves them out
-                              {b->bitrate_index, (uint32_t) sizeof(int32_t), 0}};   // where the live arrays hold nothing but create-time values)
+    if (front) memset(front, 0, sizeof(*front));
+    if (loop) memset(loop, 0, sizeof(*loop));
     uint32_t off = 0;
-    for (int k = 0; k < 8; k++) {
-        r[k].off = off;
-        off += (r[k].bytes + 15u) & ~15u;
-    }
-    if (front) {
-        memset(front, 0, sizeof(*front));
-        front->n = 2;
-        for (int k = 0; k < 2; k++) front->r[k] = r[k];
-    }
-    if (loop) {
-        memset(loop, 0, sizeof(*loop));
-        loop->n = 6;
-        for (int k = 0; k < 6; k++) loop->r[k] = r[2 + k];
+    for (const carried_region &c : b->carried) {
+        mp3mi_park_table *t = c.loop ? loop : front;
+        if (t && t->n < MP3MI_PARK_REGIONS) t->r[t->n++] = {c.base, (uint32_t) c.bytes, off};
+        off += ((uint32_t) c.bytes + 15u) & ~15u;
     }
     return off;
 }
-static_assert(MP3MI_PARK_REGIONS >= 6, "the loop stream's regions of a parked stream");
+static_assert(MP3MI_PARK_REGIONS >= N_CARRIED - 2, "the loop stream's regions of a parked stream");
+
+// k_slot_begin over the regions of one HIP stream that a fresh stream needs zeroed (at most three per launch: the kernel's arguments)
+static void slot_begin(const mp3mi_batch *b, bool loop, const int32_t *list, int n_list)
+{
+    mp3mi_slot_region r[3] = {{NULL, 0}, {NULL, 0}, {NULL, 0}};
+    int k = 0;
+    for (const carried_region &c : b->carried)
+        if (c.zero && c.loop == loop && k < 3) r[k++] = {c.base, c.bytes};
+    mp3mi_launch_slot_begin(list, n_list, r[0], r[1], r[2], loop ? b->lstream : b->stream);
+}
 
 extern "C" size_t mp3mi_batch_slot_state_bytes(const mp3mi_batch *b) { return b ? park_tables(b, NULL, NULL) : 0; }
 
@@ -980,18 +988,6 @@ static bool park_args_ok(const mp3mi_batch *b, int n, const int32_t *slots_host,
     return true;
 }
 
-// Whether the readers of a ring entry of the slot lists are through (four park calls ago: as a rule long since, and then the
-// host neither waits nor lets a held k_loop go, which would cost the next call its place beside that k_loop)
-static bool park_entry_free(hipEvent_t ev)
-{
-#if defined(MP3MI_EMU)
-    (void) ev;
-    return true; // (the emulator runs every launch where it is issued)
-#else
-    return hipEventQuery(ev) == hipSuccess;
-#endif
-}
-
 // The launches of an export (to_state) or an import: the slot list goes up on the front stream, like a per-slot call's control
 // block, and each stream moves the regions it owns -- the next call's feed-forward kernels do not wait for the loop stream, so
 // the psy state and the PCM history are read and written on the front stream only; everything k_loop, k_format and
@@ -1001,20 +997,18 @@ static bool park_entry_free(hipEvent_t ev)
 static int park_run(mp3mi_batch *b, int n, const int32_t *slots_host, const mp3mi_park_table &front, const mp3mi_park_table &loop,
                     void *state_dev, size_t state_stride, int to_state)
 {
-    const int p = (int) (b->park_calls & 3u);
-    if (!b->park_stage[p]) {
-        CHK(hipHostMalloc((void **) &b->park_stage[p], sizeof(int32_t) * (size_t) b->n_streams, 0));
-        CHK(hipMalloc((void **) &b->park_dev[p], sizeof(int32_t) * (size_t) b->n_streams));
-        CHK(hipEventCreateWithFlags(&b->ev_park[p], hipEventDisableTiming));
-    }
-    if (b->park_used[p] && !park_entry_free(b->ev_park[p])) {
+    mp3mi_batch::park_ring::entry &en = b->park.take();
+    if (!en.stage) CHK(ring_entry_create(b, en, sizeof(int32_t) * (size_t) b->n_streams));
+    // Whether the readers of the entry are through (four park calls ago: as a rule long since, and then the host neither waits
+    // nor lets a held k_loop go, which would cost the next call its place beside that k_loop)
+    if (!en.free.done()) {
         hold_release(b); // (the host is about to wait for work that may be queued behind the held k_loop)
-        CHK(hipEventSynchronize(b->ev_park[p]));
+        CHK(en.free.sync());
     }
-    memcpy(b->park_stage[p], slots_host, sizeof(int32_t) * (size_t) n);
-    CHK(hipMemcpyAsync(b->park_dev[p], b->park_stage[p], sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, b->stream));
+    memcpy(en.stage, slots_host, sizeof(int32_t) * (size_t) n);
+    CHK(hipMemcpyAsync(en.dev, en.stage, sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, b->stream));
     CHK(hipEventRecord(b->ev_ctl_up, b->stream));
-    mp3mi_launch_slot_park(b->park_dev[p], n, front, state_dev, state_stride, to_state, b->stream);
+    mp3mi_launch_slot_park(en.dev, n, front, state_dev, state_stride, to_state, b->stream);
     CHK(hipGetLastError());
     CHK(hipEventRecord(b->ev_hist, b->stream));
     CHK(hipStreamWaitEvent(b->lstream, b->ev_ctl_up, 0));
@@ -1025,14 +1019,12 @@ static int park_run(mp3mi_batch *b, int n, const int32_t *slots_host, const mp3m
         CHK(hipGetLastError());
         b->status_kept = false;
     }
-    mp3mi_launch_slot_park(b->park_dev[p], n, loop, state_dev, state_stride, to_state, b->lstream);
+    mp3mi_launch_slot_park(en.dev, n, loop, state_dev, state_stride, to_state, b->lstream);
     CHK(hipGetLastError());
-    CHK(hipStreamWaitEvent(b->lstream, b->ev_hist, 0)); // both readers of the list are ahead of ev_park; ev_done covers both streams
-    CHK(hipEventRecord(b->ev_park[p], b->lstream));
-    b->park_used[p] = true;
-    b->park_calls++;
-    CHK(hipEventRecord(b->ev_done, b->lstream));
-    b->have_done = true;
+    CHK(hipStreamWaitEvent(b->lstream, b->ev_hist, 0)); // both readers of the list are ahead of the entry's fence; ev_done covers both streams
+    CHK(en.free.record(b->lstream));
+    b->park.next();
+    CHK(b->ev_done.record(b->lstream));
     return MP3MI_OK;
 }
 
@@ -1073,9 +1065,7 @@ extern "C" int mp3mi_batch_slots_export(mp3mi_batch *b, int n, const int32_t *sl
             b->slot_kbps_h[s] = b->kbps_h[s]; // the stream takes its bitrate with it
         }
     }
-    b->slot_frames_h.assign(f.begin(), f.end());
-    b->slots_on = true;
-    slots_settle(b);
+    slots_settle(b, f);
     return MP3MI_OK;
 }
 
@@ -1115,10 +1105,8 @@ extern "C" int mp3mi_batch_slots_import(mp3mi_batch *b, int n, const int32_t *sl
     b->rate_dirty |= other_rate;
     // the per-slot bookkeeping from here on, also on a batch nothing has run on yet: no later call takes the "first call clears
     // every stream's state" branch of encode_impl over the resumed streams (slots_settle hands back only with every slot open)
-    b->slot_frames_h.assign(f.begin(), f.end());
-    b->slots_on = true;
     b->fresh = false;
-    slots_settle(b);
+    slots_settle(b, f);
     return MP3MI_OK;
 }
 
@@ -1126,12 +1114,12 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
                        size_t out_stride, uint32_t *out_len_dev, bool whole_file, const host_call *hc, const slot_call *sc)
 {
     if (!b || !pcm_dev || !out_dev || !out_len_dev || n_frames <= 0 || n_frames > b->max_frames) return MP3MI_ERR_ARG;
-    if (out_stride < (size_t) n_frames * (size_t) b->max_frame_bytes + 1 + (whole_file ? 0 : MP3MI_CARRY_BYTES)) return MP3MI_ERR_ARG;
+    if (out_stride < min_out_stride(b, n_frames, !whole_file)) return MP3MI_ERR_ARG;
     ON_DEVICE(b);
     const int S = b->n_streams, C = b->channels;
     if (b->debug && !b->sb_dbg) {
         const size_t ngc = (size_t) S * 2 * (size_t) b->chunk_frames * (size_t) C;
-        CHK(hipMalloc((void **) &b->sb_dbg, ngc * 576 * sizeof(double)));
+        CHK(dev_alloc(b, &b->sb_dbg, ngc * 576 * sizeof(double)));
     }
     // The call before this one may still be running.  Its kernels and this call's share nothing but the batch's own
     // buffers, and every one of those is either touched on ONE stream only (in-order: the FFT outputs, the subband
@@ -1143,11 +1131,8 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
     // a whole-file call starts every stream afresh; a streaming call continues (the first one after create / reset /
     // flush / a whole-file call starts afresh too)
     if (whole_file || (!sc && b->frames_done == 0 && !b->fresh)) {
-        CHK(hipMemsetAsync(b->psy_state, 0, mp3mi_psy_state_size() * (size_t) S * C, b->stream));
-        CHK(hipMemsetAsync(b->pcm_hist, 0, sizeof(int16_t) * MP3MI_PCM_HIST * (size_t) C * (size_t) S, b->stream));
-        CHK(hipMemsetAsync(b->loop_state, 0, mp3mi_loop_state_size() * (size_t) S, b->lstream));
-        CHK(hipMemsetAsync(b->out_base, 0, sizeof(int64_t) * (size_t) S, b->lstream));
-        CHK(hipMemsetAsync(b->carry_len, 0, sizeof(int32_t) * (size_t) S, b->lstream));
+        for (const carried_region &r : b->carried) // (each region on the stream that owns it)
+            if (r.zero) CHK(hipMemsetAsync(r.base, 0, r.bytes * (size_t) S, r.loop ? b->lstream : b->stream));
         // streams that per-slot calls began at bitrates of their own end here.  (The host mirror is reset with the copy's enqueue, not
         // with the call's success: a HIP error further down leaves a call half enqueued, like any MP3MI_ERR_HIP of this function,
         // and no entry point recovers a batch from that, so the mirror is not rolled back.)
@@ -1157,35 +1142,31 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
     // (a per-slot call: every slot has its own frame index, in the control block; k_loop counts the frame of a status from the
     // call's first, and k_stream_tail places it in the stream)
     const long fabs0 = sc ? 0 : b->frames_done;
-    if (sc) n_samples_dev = sc->ns;
+    if (sc) n_samples_dev = sc->dev.n_samples;
     const bool kept = b->status_kept;
     b->fresh = false;
     b->status_kept = false;
     if (b->place_cost) CHK(hipMemsetAsync(b->place_cost, 0, sizeof(int) * (size_t) S, b->lstream)); // first chunk: order = identity
-    if (hc && b->hio.out_used[hc->slot]) CHK(hipStreamWaitEvent(b->lstream, b->hio.out_free[hc->slot], 0)); // the call two before this one copied out of it
+    if (hc) CHK(b->hio.slot[hc->slot].out_free.wait_on(b->lstream)); // the call two before this one copied out of it
     CHK(hipMemsetAsync(out_dev, 0, out_stride * (size_t) S, b->lstream)); // (behind the formatter of the call before: it may be the same buffer)
     if (sc) {
         // the control block goes up on the front stream, ahead of everything of the call that reads it; the START slots' state is
         // cleared on the stream that owns it: psy state and PCM history before the call's first transform, the loop state, the
         // file position and the carry length before carry_in and the call's first k_loop
         // (the bitrates behind it travel only where k_slot_rate will read them: otherwise the copy is the size it always had)
-        CHK(hipMemcpyAsync(b->ctl_dev[sc->par], b->ctl_stage[sc->par], sc->rate_bits ? b->ctl_bytes : b->ctl_base_bytes, hipMemcpyHostToDevice,
-                           b->stream));
+        CHK(hipMemcpyAsync(sc->blk->dev, sc->blk->stage, sc->set_rates ? b->ctl_at.bytes : b->ctl_at.base_bytes, hipMemcpyHostToDevice, b->stream));
         CHK(hipEventRecord(b->ev_ctl_up, b->stream));
-        const mp3mi_slot_region none = {NULL, 0};
-        mp3mi_launch_slot_begin(sc->list, sc->n_start, {b->psy_state, mp3mi_psy_state_size() * (size_t) C},
-                                {b->pcm_hist, sizeof(int16_t) * MP3MI_PCM_HIST * (size_t) C}, none, b->stream);
+        slot_begin(b, false, sc->dev.list, sc->n_start);
         CHK(hipGetLastError());
         CHK(hipStreamWaitEvent(b->lstream, b->ev_ctl_up, 0));
         if (kept) { // the last flush ended every stream and reset the state: the ended streams' status stays until their slot STARTs
             mp3mi_launch_status_scatter(S, (int32_t *) b->loop_state, (int) (mp3mi_loop_state_size() / 4), b->status_dev, b->lstream);
             CHK(hipGetLastError());
         }
-        mp3mi_launch_slot_begin(sc->list, sc->n_start, {b->loop_state, mp3mi_loop_state_size()}, {b->out_base, sizeof(int64_t)},
-                                {b->carry_len, sizeof(int32_t)}, b->lstream);
+        slot_begin(b, true, sc->dev.list, sc->n_start);
         CHK(hipGetLastError());
-        if (sc->rate_bits) { // ... and their bitrates: here, behind the readers of the call before and ahead of this call's first
-            mp3mi_launch_slot_rate(sc->list, sc->n_start, sc->rate_bits, sc->rate_bits + S, b->bits_per_frame, b->bitrate_index, b->lstream);
+        if (sc->set_rates) { // ... and their bitrates: here, behind the readers of the call before and ahead of this call's first
+            mp3mi_launch_slot_rate(sc->dev.list, sc->n_start, sc->dev.rate_bits, sc->dev.rate_index, b->bits_per_frame, b->bitrate_index, b->lstream);
             CHK(hipGetLastError());
         }
     }
@@ -1197,11 +1178,7 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
     const int P = b->n_parts, n_items = nchunks * P;
     if (harvest_timing(b, (int) (b->call_no & 1)) != MP3MI_OK) return MP3MI_ERR_HIP; // (the call before the last one)
     mp3mi_batch::timing_set &ts = b->ts[b->call_no & 1];
-    while ((int) ts.loop_ev.size() < 2 * n_items) {
-        hipEvent_t e;
-        CHK(hipEventCreate(&e));
-        ts.loop_ev.push_back(e);
-    }
+    CHK(grow_events(ts.loop_ev, 2 * (size_t) n_items, 0));
     ts.launches = n_items;
     ts.kernels = 0;
     CHK(hipEventRecord(ts.ev0, b->stream));
@@ -1223,6 +1200,7 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
     // parts k_psy was still running when the second part started and that part took 65 ms instead of 37:
     // profiles/r03_experiments.txt.  12 288 / 16 384 / 20 000 streams: 5.8 -> ... M frames/s.)
     const int cfr = (n_frames + nchunks - 1) / nchunks; // equal chunks: a short last one would run without overlap
+    const call_shape cs = {n_frames, n_samples_dev, fabs0, sc ? sc->dev.fabs : NULL, sc ? sc->dev.ctl : NULL, whole_file};
     struct item_view {
         mp3mi_geom g;      // of the part: n_streams, n_samples / hist / out_base advanced
         int slot, ev;      // double-buffer slot of the chunk; index of the (slot, part) events
@@ -1235,22 +1213,7 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         const int nf = (n_frames - f0 < cfr) ? n_frames - f0 : cfr;
         v.s0 = (size_t) part * (size_t) b->part_streams;
         const int n = S - (int) v.s0 < b->part_streams ? S - (int) v.s0 : b->part_streams;
-        mp3mi_geom g = mp3mi_make_geom(n, C, b->rate_idx, n_frames, f0, nf);
-        g.test_flags = b->test_flags;
-        g.n_samples = n_samples_dev ? n_samples_dev + v.s0 : NULL;
-        g.hdr_flags |= b->hdr_flags;
-        g.hdr_mode = b->hdr_mode;
-        g.crc = b->crc;
-        g.fabs0 = fabs0;
-        g.fabs_s = sc ? sc->fabs + v.s0 : NULL;
-        g.slot_ctl = sc ? sc->ctl + v.s0 : NULL;
-        g.hist = b->pcm_hist + v.s0 * MP3MI_PCM_HIST * (size_t) C;
-        g.out_base = whole_file ? NULL : b->out_base + v.s0;
-        g.whole_file = whole_file ? 1 : 0;
-#if defined(MP3MI_ULP_CENSUS)
-        g.census_cb_stride = (size_t) S * 2 * (size_t) b->chunk_frames * (size_t) C * MP3MI_PART_P;
-#endif
-        v.g = g;
+        v.g = call_geom(b, cs, f0, nf, v.s0, n);
         v.slot = (c + b->slot_base) & 1;
         v.ev = v.slot * P + part;
         v.rec0 = v.s0 * 2 * (size_t) nf * (size_t) C;
@@ -1267,33 +1230,28 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         // kernels read -- on the upload stream, so a chunk's rows are in place while the chunk before is encoded.  (The map is
         // in the control block, which the front stream uploads: ev_ctl_up.)
         mp3mi_batch::host_io &H = b->hio;
-        const int sl = hc->slot;
+        mp3mi_batch::host_io::io_slot &io = H.slot[hc->slot];
         const bool mapped = hc->rows_dev != NULL;
         const size_t R = mapped ? (size_t) hc->n_rows : (size_t) S;
-        if (H.pcm_used[sl]) CHK(hipStreamWaitEvent(H.h2d, H.pcm_free[sl], 0)); // (the kernels of the call two before this one)
-        while ((int) H.t_up[sl].size() < 2 * nchunks) {
-            hipEvent_t e;
-            for (std::vector<hipEvent_t> *v : {&H.t_up[sl], &H.t_dn[sl]}) { CHK(hipEventCreate(&e)); v->push_back(e); }
-            if (H.t_up[sl].size() % 2 == 0) {
-                for (std::vector<hipEvent_t> *v : {&H.ev_fmt[sl], &H.ev_in[sl]}) { CHK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); v->push_back(e); }
-            }
-        }
-        H.n_chunks[sl] = nchunks;
-        H.bytes_up[sl] = H.bytes_dn[sl] = 0.0;
+        CHK(io.pcm_free.wait_on(H.h2d)); // (the kernels of the call two before this one)
+        for (std::vector<hipEvent_t> *v : {&io.t_up, &io.t_dn}) CHK(grow_events(*v, 2 * (size_t) nchunks, 0));
+        for (std::vector<hipEvent_t> *v : {&io.ev_fmt, &io.ev_in}) CHK(grow_events(*v, (size_t) nchunks, hipEventDisableTiming));
+        io.n_chunks = nchunks;
+        io.bytes_up = io.bytes_dn = 0.0;
         if (mapped) CHK(hipStreamWaitEvent(H.h2d, b->ev_ctl_up, 0));
         for (int c = 0; c < nchunks; c++) {
             const int f0 = c * cfr, nf = (n_frames - f0 < cfr) ? n_frames - f0 : cfr;
             const size_t off = (size_t) f0 * 1152 * (size_t) C, width = (size_t) nf * 1152 * (size_t) C * sizeof(int16_t);
-            int16_t *dst = mapped ? H.pcm_rows[sl] : H.pcm[sl];
-            CHK(hipEventRecord(H.t_up[sl][2 * c], H.h2d));
+            int16_t *dst = mapped ? io.pcm_rows : io.pcm;
+            CHK(hipEventRecord(io.t_up[2 * c], H.h2d));
             CHK(hipMemcpy2DAsync(dst + off, pcm_pitch * sizeof(int16_t), hc->pcm + off, pcm_pitch * sizeof(int16_t), width, R,
                                  hipMemcpyHostToDevice, H.h2d));
-            CHK(hipEventRecord(H.t_up[sl][2 * c + 1], H.h2d));
-            H.bytes_up[sl] += (double) width * (double) R;
+            CHK(hipEventRecord(io.t_up[2 * c + 1], H.h2d));
+            io.bytes_up += (double) width * (double) R;
             if (mapped) {
-                mp3mi_launch_rows_in(hc->rows_dev, hc->n_rows, H.pcm_rows[sl], H.pcm[sl], pcm_pitch * sizeof(int16_t), off * sizeof(int16_t), width, H.h2d);
+                mp3mi_launch_rows_in(hc->rows_dev, hc->n_rows, io.pcm_rows, io.pcm, pcm_pitch * sizeof(int16_t), off * sizeof(int16_t), width, H.h2d);
                 CHK(hipGetLastError());
-                CHK(hipEventRecord(H.ev_in[sl][c], H.h2d));
+                CHK(hipEventRecord(io.ev_in[c], H.h2d));
             }
         }
     }
@@ -1303,13 +1261,13 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         const item_view v = view(k);
         const size_t r = v.rec0;
         if (hc && (which & 1) && k % P == 0) // the chunk's PCM is up (and in its slots' rows)
-            CHK(hipStreamWaitEvent(b->stream, hc->rows_dev ? b->hio.ev_in[hc->slot][k / P] : b->hio.t_up[hc->slot][2 * (k / P) + 1], 0));
+            CHK(hipStreamWaitEvent(b->stream, hc->rows_dev ? b->hio.slot[hc->slot].ev_in[k / P] : b->hio.slot[hc->slot].t_up[2 * (k / P) + 1], 0));
         mp3mi_launch_fft(b->T, v.g, pcm_dev + v.s0 * pcm_pitch, b->energy_l + r * MP3MI_HBLK_P, b->energy_s + r * 3 * MP3MI_HBLK_S,
                          b->fft_bins + r * MP3MI_FFT_BINS, b->cw_mid + r * 50, b->hist6 + r * 12, b->stream, which);
         CHK(hipGetLastError());
         if (which & 2) {
             // the k_loop that read this region of the slot last (two chunks ago, maybe in the call before)
-            if (b->slot_used[v.ev]) CHK(hipStreamWaitEvent(b->stream, b->ev_loop[v.ev], 0));
+            CHK(b->ev_loop[v.ev].wait_on(b->stream));
             mp3mi_launch_psy(b->T, v.g, b->energy_l + r * MP3MI_HBLK_P, b->energy_s + r * 3 * MP3MI_HBLK_S, b->cw_mid + r * 50, b->hist6 + r * 12,
                              b->fft_bins + r * MP3MI_FFT_BINS, b->cw_fix, (char *) b->psy_state + v.s0 * psy_state_bytes, b->part_eb + r * MP3MI_PART_P,
                              b->part_cb + r * MP3MI_PART_P, b->psy[v.slot] + r, b->stream);
@@ -1351,28 +1309,27 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
     // that the copy is plain whatever the stride and moves the live rows only.
     auto download = [&]() -> int {
         mp3mi_batch::host_io &H = b->hio;
-        const int sl = hc->slot;
+        mp3mi_batch::host_io::io_slot &io = H.slot[hc->slot];
         const bool mapped = hc->rows_dev != NULL;
         const size_t R = mapped ? (size_t) hc->n_rows : (size_t) S;
         const size_t row = mapped ? hc->out_stride : (hc->out_stride < out_stride ? hc->out_stride : out_stride);
         if (mapped) {
-            mp3mi_launch_rows_out(hc->rows_dev, hc->n_rows, out_dev, out_stride, out_len_dev, H.out_rows[sl], hc->out_stride, H.len_rows[sl], b->lstream);
+            mp3mi_launch_rows_out(hc->rows_dev, hc->n_rows, out_dev, out_stride, out_len_dev, io.out_rows, hc->out_stride, io.len_rows, b->lstream);
             CHK(hipGetLastError());
         }
-        CHK(hipEventRecord(H.ev_fmt[sl][0], b->lstream));
-        CHK(hipStreamWaitEvent(H.d2h, H.ev_fmt[sl][0], 0));
-        CHK(hipEventRecord(H.t_dn[sl][0], H.d2h));
+        CHK(hipEventRecord(io.ev_fmt[0], b->lstream));
+        CHK(hipStreamWaitEvent(H.d2h, io.ev_fmt[0], 0));
+        CHK(hipEventRecord(io.t_dn[0], H.d2h));
         if (mapped)
-            CHK(hipMemcpyAsync(hc->out, H.out_rows[sl], hc->out_stride * R, hipMemcpyDeviceToHost, H.d2h));
+            CHK(hipMemcpyAsync(hc->out, io.out_rows, hc->out_stride * R, hipMemcpyDeviceToHost, H.d2h));
         else if (hc->out_stride == out_stride)
             CHK(hipMemcpyAsync(hc->out, out_dev, out_stride * (size_t) S, hipMemcpyDeviceToHost, H.d2h));
         else
             CHK(hipMemcpy2DAsync(hc->out, hc->out_stride, out_dev, out_stride, row, (size_t) S, hipMemcpyDeviceToHost, H.d2h));
-        CHK(hipMemcpyAsync(hc->out_len, mapped ? H.len_rows[sl] : out_len_dev, sizeof(uint32_t) * R, hipMemcpyDeviceToHost, H.d2h));
-        CHK(hipEventRecord(H.t_dn[sl][1], H.d2h));
-        H.bytes_dn[sl] += (double) row * (double) R;
-        CHK(hipEventRecord(H.out_free[sl], H.d2h));
-        H.out_used[sl] = true;
+        CHK(hipMemcpyAsync(hc->out_len, mapped ? io.len_rows : out_len_dev, sizeof(uint32_t) * R, hipMemcpyDeviceToHost, H.d2h));
+        CHK(hipEventRecord(io.t_dn[1], H.d2h));
+        io.bytes_dn += (double) row * (double) R;
+        CHK(io.out_free.record(H.d2h));
         return MP3MI_OK;
     };
     for (int k = 0; k < n_items; k++) {
@@ -1387,7 +1344,7 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         // ---- front stream: everything that does not depend on the bit reservoir ----
         if (k >= 1 && !beside) { // (the k_loop before this item's: view(k - 1))
             const item_view pv = view(k - 1);
-            CHK(hipStreamWaitEvent(b->stream, b->ev_loop[pv.ev], 0));
+            CHK(b->ev_loop[pv.ev].wait_on(b->stream));
         } else if (follows) // this item's kernels run behind k_loop(k - 1), once that is resident (<= 300 us)
             mp3mi_launch_gate(b->gate_count, b->gate_first - 16u, 30000u, b->stream);
         if (beside && follows && stage_x(k, 2) != MP3MI_OK) return MP3MI_ERR_HIP;
@@ -1448,8 +1405,7 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         }
         ts.kernels += 1;
         CHK(hipEventRecord(ts.loop_ev[2 * k + 1], b->lstream));
-        CHK(hipEventRecord(b->ev_loop[v.ev], b->lstream));
-        b->slot_used[v.ev] = 1;
+        CHK(b->ev_loop[v.ev].record(b->lstream));
         mp3mi_launch_format(b->T, g, b->ix + r * 576, b->side + v.s0 * (size_t) g.nf, b->bits_per_frame + v.s0, b->bitrate_index + v.s0,
                             out_dev + v.s0 * out_stride, out_stride, out_len_dev + v.s0, (int32_t *) ((char *) b->loop_state + v.s0 * loop_state_bytes),
                             (int) (loop_state_bytes / 4), b->voided, b->lstream);
@@ -1458,26 +1414,9 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         b->last_nf = g.nf;
         b->last_slot = v.slot;
     }
-    auto geom_of = [&](int c) { // the whole batch's geometry of chunk c (hand-over kernels below)
-        const int f0 = c * cfr;
-        const int nf = (n_frames - f0 < cfr) ? n_frames - f0 : cfr;
-        mp3mi_geom g = mp3mi_make_geom(S, C, b->rate_idx, n_frames, f0, nf);
-        g.test_flags = b->test_flags;
-        g.n_samples = n_samples_dev;
-        g.hdr_flags |= b->hdr_flags;
-        g.hdr_mode = b->hdr_mode;
-        g.crc = b->crc;
-        g.fabs0 = fabs0;
-        g.fabs_s = sc ? sc->fabs : NULL;
-        g.slot_ctl = sc ? sc->ctl : NULL;
-        g.hist = b->pcm_hist;
-        g.out_base = whole_file ? NULL : b->out_base;
-        g.whole_file = whole_file ? 1 : 0;
-        return g;
-    };
     {   // hand over to the next call: PCM history (front stream: behind the last kernels that read the old one) and,
         // for a streaming call, what became final / what waits (loop stream: behind the last k_format)
-        const mp3mi_geom g = geom_of(0);
+        const mp3mi_geom g = call_geom(b, cs, 0, n_frames < cfr ? n_frames : cfr, 0, S); // the whole batch's, of chunk 0
         mp3mi_launch_hist_save(g, pcm_dev, b->pcm_hist, b->stream);
         CHK(hipGetLastError());
         if (!whole_file) {
@@ -1490,23 +1429,19 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         CHK(hipStreamWaitEvent(b->lstream, b->ev_hist, 0)); // ev_done below then covers both streams
     }
     if (hc) { // (lstream has just joined the front stream: every kernel that reads the slot's PCM is ahead of this)
-        CHK(hipEventRecord(b->hio.pcm_free[hc->slot], b->lstream));
-        b->hio.pcm_used[hc->slot] = true;
-        b->hio.pending[hc->slot] = true;
-        b->hio.hold_of[hc->slot] = b->held ? b->hold_seq : 0u;
+        mp3mi_batch::host_io::io_slot &io = b->hio.slot[hc->slot];
+        CHK(io.pcm_free.record(b->lstream));
+        io.pending = true;
+        io.hold_of = b->held ? b->hold_seq : 0u;
     }
-    if (sc) { // (lstream has joined the front stream: every reader of this copy of the control block is ahead of this)
-        CHK(hipEventRecord(b->ev_ctl[sc->par], b->lstream));
-        b->ctl_used[sc->par] = true;
-    }
+    if (sc) CHK(sc->blk->free.record(b->lstream)); // (lstream has joined the front stream: every reader of this copy of the control block is ahead of this)
     b->slot_base = (b->slot_base + nchunks) & 1;
     b->frames_done = (whole_file || sc) ? 0 : fabs0 + n_frames; // a whole-file call leaves finished streams behind
     if (whole_file) b->slots_on = false;
     CHK(hipEventRecord(ts.ev1, b->lstream));
     ts.pending = true;
     b->call_no++;
-    CHK(hipEventRecord(b->ev_done, b->lstream));
-    b->have_done = true;
+    CHK(b->ev_done.record(b->lstream));
     CHK(hipGetLastError());
     return MP3MI_OK;
 }
@@ -1576,12 +1511,19 @@ extern "C" int mp3mi_batch_debug_prep_fixups(mp3mi_batch *b, int *n_listed)
     return MP3MI_OK;
 }
 
-extern "C" int mp3mi_batch_last_timing(mp3mi_batch *b, float *loop_kernel_ms, float *all_kernels_ms, int *launches)
+// both timing sets read out, the older first (waits for the calls issued so far)
+static int harvest_all(mp3mi_batch *b)
 {
-    if (!b || !b->have_done || b->call_no == 0) return MP3MI_ERR_ARG; // nothing has been encoded yet
     ON_DEVICE(b);
     hold_release(b);
     if (harvest_timing(b, (int) (b->call_no & 1)) != MP3MI_OK || harvest_timing(b, (int) ((b->call_no - 1) & 1)) != MP3MI_OK) return MP3MI_ERR_HIP;
+    return MP3MI_OK;
+}
+
+extern "C" int mp3mi_batch_last_timing(mp3mi_batch *b, float *loop_kernel_ms, float *all_kernels_ms, int *launches)
+{
+    if (!b || !b->ev_done.recorded || b->call_no == 0) return MP3MI_ERR_ARG; // nothing has been encoded yet
+    if (harvest_all(b) != MP3MI_OK) return MP3MI_ERR_HIP;
     if (loop_kernel_ms) *loop_kernel_ms = b->last_loop_ms;
     if (all_kernels_ms) *all_kernels_ms = b->last_all_ms;
     if (launches) *launches = b->last_launches;
@@ -1591,9 +1533,7 @@ extern "C" int mp3mi_batch_last_timing(mp3mi_batch *b, float *loop_kernel_ms, fl
 extern "C" int mp3mi_batch_total_timing(mp3mi_batch *b, double *loop_kernel_ms, double *all_kernels_ms, long *launches, long *calls)
 {
     if (!b) return MP3MI_ERR_ARG;
-    ON_DEVICE(b);
-    hold_release(b);
-    if (harvest_timing(b, (int) (b->call_no & 1)) != MP3MI_OK || harvest_timing(b, (int) ((b->call_no - 1) & 1)) != MP3MI_OK) return MP3MI_ERR_HIP;
+    if (harvest_all(b) != MP3MI_OK) return MP3MI_ERR_HIP;
     if (loop_kernel_ms) *loop_kernel_ms = b->tot_loop_ms;
     if (all_kernels_ms) *all_kernels_ms = b->tot_all_ms;
     if (launches) *launches = b->tot_launches;
@@ -1643,21 +1583,22 @@ extern "C" long mp3mi_batch_debug_fetch(mp3mi_batch *b, int what, void *host_dst
 static int host_io_harvest(mp3mi_batch *b, int sl)
 {
     mp3mi_batch::host_io &H = b->hio;
-    if (!H.pending[sl]) return MP3MI_OK;
-    const int n = H.n_chunks[sl];
-    CHK(hipEventSynchronize(H.t_dn[sl][1]));
-    CHK(hipEventSynchronize(H.t_up[sl][2 * n - 1]));
+    mp3mi_batch::host_io::io_slot &io = H.slot[sl];
+    if (!io.pending) return MP3MI_OK;
+    const int n = io.n_chunks;
+    CHK(hipEventSynchronize(io.t_dn[1]));
+    CHK(hipEventSynchronize(io.t_up[2 * n - 1]));
     float ms = 0;
     for (int c = 0; c < n; c++) {
-        CHK(hipEventElapsedTime(&ms, H.t_up[sl][2 * c], H.t_up[sl][2 * c + 1]));
+        CHK(hipEventElapsedTime(&ms, io.t_up[2 * c], io.t_up[2 * c + 1]));
         H.tot_up_ms += ms;
     }
-    CHK(hipEventElapsedTime(&ms, H.t_dn[sl][0], H.t_dn[sl][1]));
+    CHK(hipEventElapsedTime(&ms, io.t_dn[0], io.t_dn[1]));
     H.tot_dn_ms += ms;
-    H.tot_up_bytes += H.bytes_up[sl];
-    H.tot_dn_bytes += H.bytes_dn[sl];
+    H.tot_up_bytes += io.bytes_up;
+    H.tot_dn_bytes += io.bytes_dn;
     H.tot_calls++;
-    H.pending[sl] = false;
+    io.pending = false;
     return MP3MI_OK;
 }
 
@@ -1674,11 +1615,12 @@ static int host_io_init(mp3mi_batch *b, int sl)
         if (!H.d2h) CHK(hipStreamCreateWithFlags(&H.d2h, hipStreamNonBlocking));
         H.ready = true;
     }
-    if (!H.pcm[sl]) CHK(hipMalloc((void **) &H.pcm[sl], S * (size_t) b->max_frames * 1152 * (size_t) b->channels * sizeof(int16_t)));
-    if (!H.out[sl]) CHK(hipMalloc((void **) &H.out[sl], S * H.out_stride));
-    if (!H.len[sl]) CHK(hipMalloc((void **) &H.len[sl], S * sizeof(uint32_t)));
-    if (!H.pcm_free[sl]) CHK(hipEventCreateWithFlags(&H.pcm_free[sl], hipEventDisableTiming));
-    if (!H.out_free[sl]) CHK(hipEventCreateWithFlags(&H.out_free[sl], hipEventDisableTiming));
+    mp3mi_batch::host_io::io_slot &io = H.slot[sl];
+    if (!io.pcm) CHK(dev_alloc(b, &io.pcm, S * (size_t) b->max_frames * 1152 * (size_t) b->channels * sizeof(int16_t)));
+    if (!io.out) CHK(dev_alloc(b, &io.out, S * H.out_stride));
+    if (!io.len) CHK(dev_alloc(b, &io.len, S * sizeof(uint32_t)));
+    if (!io.pcm_free.ev) CHK(io.pcm_free.create());
+    if (!io.out_free.ev) CHK(io.out_free.create());
     return MP3MI_OK;
 }
 
@@ -1686,14 +1628,14 @@ extern "C" int mp3mi_batch_encode_host_async(mp3mi_batch *b, const int16_t *pcm_
                                              uint32_t *out_len_host)
 {
     if (!b || !pcm_host || !out_host || !out_len_host || n_frames <= 0 || n_frames > b->max_frames) return MP3MI_ERR_ARG;
-    if (out_stride < (size_t) n_frames * (size_t) b->max_frame_bytes + 1) return MP3MI_ERR_ARG;
+    if (out_stride < min_out_stride(b, n_frames, false)) return MP3MI_ERR_ARG;
     ON_DEVICE(b);
     mp3mi_batch::host_io &H = b->hio;
     const int sl = (int) (H.call_no & 1);
     if (host_io_init(b, sl) != MP3MI_OK) return MP3MI_ERR_HIP;
     if (host_io_harvest(b, sl) != MP3MI_OK) return MP3MI_ERR_HIP; // (waits for the call two before this one: at most two in flight)
     const host_call hc = {pcm_host, out_host, out_stride, out_len_host, sl};
-    const int rc = encode_impl(b, H.pcm[sl], NULL, n_frames, H.out[sl], H.out_stride, H.len[sl], true, &hc);
+    const int rc = encode_impl(b, H.slot[sl].pcm, NULL, n_frames, H.slot[sl].out, H.out_stride, H.slot[sl].len, true, &hc);
     if (rc == MP3MI_OK) H.call_no++; // (a call that failed took no slot)
     return rc;
 }
@@ -1703,19 +1645,19 @@ extern "C" int mp3mi_batch_encode_host_async(mp3mi_batch *b, const int16_t *pcm_
 // last download -- the host has waited for it: host_io_harvest).
 static int host_rows_init(mp3mi_batch *b, int sl, size_t out_stride)
 {
-    mp3mi_batch::host_io &H = b->hio;
+    mp3mi_batch::host_io::io_slot &io = b->hio.slot[sl];
     const size_t S = (size_t) b->n_streams;
-    if (!H.pcm_rows[sl]) CHK(hipMalloc((void **) &H.pcm_rows[sl], S * (size_t) b->max_frames * 1152 * (size_t) b->channels * sizeof(int16_t)));
-    if (!H.len_rows[sl]) CHK(hipMalloc((void **) &H.len_rows[sl], S * sizeof(uint32_t)));
-    if (H.out_rows_cap[sl] < S * out_stride) {
-        if (H.out_rows[sl]) {
-            if (H.out_used[sl]) CHK(hipEventSynchronize(H.out_free[sl]));
-            CHK(hipFree(H.out_rows[sl]));
-            H.out_rows[sl] = NULL;
-            H.out_rows_cap[sl] = 0;
+    if (!io.pcm_rows) CHK(dev_alloc(b, &io.pcm_rows, S * (size_t) b->max_frames * 1152 * (size_t) b->channels * sizeof(int16_t)));
+    if (!io.len_rows) CHK(dev_alloc(b, &io.len_rows, S * sizeof(uint32_t)));
+    if (io.out_rows_cap < S * out_stride) { // (by hand, not dev_alloc: the one buffer that is freed before the batch is)
+        if (io.out_rows) {
+            CHK(io.out_free.sync());
+            CHK(hipFree(io.out_rows));
+            io.out_rows = NULL;
+            io.out_rows_cap = 0;
         }
-        CHK(hipMalloc((void **) &H.out_rows[sl], S * out_stride));
-        H.out_rows_cap[sl] = S * out_stride;
+        CHK(hipMalloc((void **) &io.out_rows, S * out_stride));
+        io.out_rows_cap = S * out_stride;
     }
     return MP3MI_OK;
 }
@@ -1765,7 +1707,7 @@ extern "C" int mp3mi_batch_encode_slots_kbps_host_async(mp3mi_batch *b, const in
     if (host_io_harvest(b, sl) != MP3MI_OK) return MP3MI_ERR_HIP; // (waits for the call two before this one: at most two in flight)
     if (row_slot_host && host_rows_init(b, sl, out_stride) != MP3MI_OK) return MP3MI_ERR_HIP;
     host_call hc = {pcm_host, out_host, out_stride, out_len_host, sl, n_rows, row_slot_host, NULL};
-    const int rc = slots_impl(b, H.pcm[sl], n_frames, ctl, ns, kbps, H.out[sl], H.out_stride, H.len[sl], &hc);
+    const int rc = slots_impl(b, H.slot[sl].pcm, n_frames, ctl, ns, kbps, H.slot[sl].out, H.out_stride, H.slot[sl].len, &hc);
     if (rc == MP3MI_OK) H.call_no++; // (a call that failed took no slot)
     return rc;
 }
@@ -1787,8 +1729,8 @@ extern "C" int mp3mi_batch_host_wait(mp3mi_batch *b, int calls_back)
     if (!H.ready || H.call_no <= (unsigned) calls_back) return MP3MI_ERR_ARG;
     ON_DEVICE(b);
     const int sl = (int) ((H.call_no - 1u - (unsigned) calls_back) & 1u);
-    if (b->held && H.hold_of[sl] == b->hold_seq) hold_release(b);
-    CHK(hipEventSynchronize(H.t_dn[sl][1]));
+    if (b->held && H.slot[sl].hold_of == b->hold_seq) hold_release(b);
+    CHK(hipEventSynchronize(H.slot[sl].t_dn[1]));
     return MP3MI_OK;
 }
 

@@ -8,7 +8,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include "mp3mi_host.h"
+#include "host_util.h"
 #include "mp3mi.h"
 
 static const int FD_BITRATES[15] = {0, 32, 40, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256, 320}; // src/common.c:124
@@ -111,8 +111,7 @@ extern "C" int mp3mi_debug_format_frames(int rate_hz, int channels, int kbps, in
                                          int n_frames, const int32_t *n_frames_s, const int16_t *ix, const void *side_v,
                                          uint8_t *out, size_t out_stride, uint32_t *out_len, int32_t *status)
 {
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return MP3MI_ERR_NO_DEVICE;
+    if (!have_device()) return MP3MI_ERR_NO_DEVICE;
     const mp3mi_frame_side *side = (const mp3mi_frame_side *) side_v;
     const int ri = rate_hz == 44100 ? 0 : (rate_hz == 48000 ? 1 : (rate_hz == 32000 ? 2 : -1));
     int bi = 1;
@@ -121,8 +120,7 @@ extern "C" int mp3mi_debug_format_frames(int rate_hz, int channels, int kbps, in
         (hdr_flags & ~63) || (crc & ~1) || n_streams <= 0 || n_frames < 0 || !n_frames_s || !out_len || !status ||
         (n_frames > 0 && (!ix || !side || !out)))
         return MP3MI_ERR_ARG;
-    static const double s_freq[3] = {44.1, 48, 32}; // src/common.c:113, src/musicin.c:562-566
-    const int frame_bytes = (int) (((double) 1152 / s_freq[ri]) * ((double) kbps / 8.0));
+    const int frame_bytes = frame_bits(1152, ri, kbps, 8) / 8;
     const int si_bytes = 4 + 2 * crc + (channels == 2 ? 32 : 17), slot = frame_bytes - si_bytes;
     if (slot <= 0 || out_stride < (size_t) n_frames * frame_bytes + 1) return MP3MI_ERR_ARG;
     mp3mi_tables *Th = (mp3mi_tables *) malloc(sizeof(mp3mi_tables));

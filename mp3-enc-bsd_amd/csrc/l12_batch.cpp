@@ -9,18 +9,9 @@
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
-#include "mp3mi_host.h"
+#include "host_util.h"
 #include "l12_dev.h"
 #include "mp3mi_l12.h"
-
-#define CHK(call)                                                                              \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            fprintf(stderr, "mp3mi: %s failed: %s (%s:%d)\n", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return MP3MI_ERR_HIP;                                                              \
-        }                                                                                      \
-    } while (0)
 
 static const int L12_BITRATES[2][15] = { /* src/common.c:122-123 */
     {0, 32, 64, 96, 128, 160, 192, 224, 256, 288, 320, 352, 384, 416, 448},
@@ -57,30 +48,6 @@ struct mp3mi_l12_batch {
     long fabs0;              // frames every stream has been given by mp3mi_l12_batch_encode_next since the last reset
 };
 
-static int l12_have_device(void)
-{
-    int n = 0;
-    return hipGetDeviceCount(&n) == hipSuccess && n > 0;
-}
-
-struct l12_device_scope {
-    int prev;
-    bool ok;
-    explicit l12_device_scope(int dev) : prev(-1), ok(true)
-    {
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess) { ok = false; return; }
-        if (cur != dev) {
-            if (hipSetDevice(dev) != hipSuccess) { ok = false; return; }
-            prev = cur;
-        }
-    }
-    ~l12_device_scope() { if (prev >= 0) (void) hipSetDevice(prev); }
-};
-#define ON_DEVICE(b)                                                                                     \
-    l12_device_scope dev_scope_((b)->device);                                                            \
-    if (!dev_scope_.ok) { fprintf(stderr, "mp3mi: cannot select device %d\n", (b)->device); return MP3MI_ERR_HIP; }
-
 static size_t l12_per_frame_bytes(int layer, int channels, int spf)
 {
     const size_t rec = (size_t) 3 * L12_ROW * sizeof(float) + 32 * sizeof(float);
@@ -90,7 +57,6 @@ static size_t l12_per_frame_bytes(int layer, int channels, int spf)
 extern "C" int mp3mi_l12_batch_create(mp3mi_l12_batch **out, int layer, int n_streams, int rate_hz, int channels,
                                       const int *kbps, int kbps_all, int max_frames, unsigned scratch_mb)
 {
-    static const double s_freq[3] = {44.1, 48, 32}; // src/common.c:113
     if (!out) return MP3MI_ERR_ARG;
     *out = NULL;
     if ((layer != 1 && layer != 2) || n_streams < 1 || max_frames < 1 || (channels != 1 && channels != 2)) return MP3MI_ERR_ARG;
@@ -99,7 +65,7 @@ extern "C" int mp3mi_l12_batch_create(mp3mi_l12_batch **out, int layer, int n_st
     else if (rate_hz == 48000) ri = 1;
     else if (rate_hz == 32000) ri = 2;
     else return MP3MI_ERR_ARG; // (MPEG-2 LSF rates: psycho_anal exits on them, src/psy.c:131-136)
-    if (!l12_have_device()) {
+    if (!have_device()) {
         fprintf(stderr, "mp3mi: no usable HIP device -- this library has no CPU fallback\n");
         return MP3MI_ERR_NO_DEVICE;
     }
@@ -127,11 +93,9 @@ extern "C" int mp3mi_l12_batch_create(mp3mi_l12_batch **out, int layer, int n_st
         if (bi == 15) { delete b; return MP3MI_ERR_ARG; }
         l12_stream_cfg &c = b->cfg_h[(size_t) s];
         c.bitrate_index = bi;
-        // src/musicin.c:562-569: slots per frame, the fraction dropped (and with it every padding decision)
-        const int whole_SpF = (int) (((double) b->spf / s_freq[ri]) * ((double) k / (double) (layer == 1 ? 32 : 8)));
-        c.frame_bits = whole_SpF * (layer == 1 ? 32 : 8);
+        c.frame_bits = frame_bits(b->spf, ri, k, layer == 1 ? 32 : 8);
         if (layer == 2) { // pick_table, src/common.c:291-318
-            const int br_per_ch = k / channels, sfrq = (int) s_freq[ri];
+            const int br_per_ch = k / channels, sfrq = rate_hz / 1000; // (int) s_freq: 44, 48, 32
             if ((sfrq == 48 && br_per_ch >= 56) || (br_per_ch >= 56 && br_per_ch <= 80)) c.table = 0;
             else if (sfrq != 48 && br_per_ch >= 96) c.table = 1;
             else if (sfrq != 32 && br_per_ch <= 48) c.table = 2;
@@ -189,7 +153,7 @@ extern "C" void mp3mi_l12_batch_destroy(mp3mi_l12_batch *b)
 {
     if (!b) return;
     {
-        l12_device_scope sc(b->device);
+        device_scope sc(b->device);
         if (b->stream) (void) hipStreamSynchronize(b->stream);
         (void) hipFree(b->T3); (void) hipFree(b->T); (void) hipFree(b->cfg); (void) hipFree(b->erp);
         (void) hipFree(b->snr); (void) hipFree(b->sbs); (void) hipFree(b->dbg);
@@ -265,14 +229,7 @@ static int l12_encode_impl(mp3mi_l12_batch *b, const int16_t *pcm_dev, const int
     const int S = b->n_streams, C = b->channels, layer = b->layer;
     if (b->debug && !b->dbg) CHK(hipMalloc((void **) &b->dbg, sizeof(l12_frame_dbg) * (size_t) S * (size_t) b->chunk_frames));
     CHK(hipEventRecord(b->ev0, b->stream));
-    {
-        const size_t want = 5 * (size_t) ((n_frames + b->chunk_frames - 1) / b->chunk_frames);
-        while (b->kev.size() < want) {
-            hipEvent_t e;
-            CHK(hipEventCreate(&e));
-            b->kev.push_back(e);
-        }
-    }
+    CHK(grow_events(b->kev, 5 * (size_t) ((n_frames + b->chunk_frames - 1) / b->chunk_frames), 0));
     // equal chunks (as batch.cpp cuts a Layer III call): a short remainder -- 191 + 191 + 1 frames of the 383-frame bench call --
     // costs four full launches over all streams and recomputes the warm-up passes for one frame
     const int nchunks = (n_frames + b->chunk_frames - 1) / b->chunk_frames, cfr = (n_frames + nchunks - 1) / nchunks;
