@@ -466,6 +466,25 @@ int mp3mi_debug_peak_lines(int rate_hz, int n_gran, const double *xr, uint16_t *
 int mp3mi_debug_format_frames(int rate_hz, int channels, int kbps, int hdr_mode, int hdr_flags, int crc, int n_streams, int n_frames,
                               const int32_t *n_frames_s, const int16_t *ix, const void *side, uint8_t *out, size_t out_stride,
                               uint32_t *out_len, int32_t *status);
+/* Self-test hook: the iteration loop on n_streams chains of n_frames frames of GIVEN records, through the three launches of the
+ * drop-in iteration_loop (csrc/dropin.cpp): k_prep_tail, k_prep on the list it leaves, k_loop with no placement and no gate
+ * (csrc/loop_debug.cpp; k_loop.hip is the product's).  One format per call -- rate_hz, channels, crc (error protection) -- and a
+ * bitrate per stream, kbps[n_streams].  xr[n_streams][2 * n_frames][channels][576] is the spectrum, psy the mp3mi_psy_out records
+ * (csrc/mp3mi_dev.h: pe, ratio_l[21], ratio_s[12][3], block_type) in the same order; state_in is NULL (fresh streams) or one loop
+ * state per stream, as state_out returns them: int32 words, [0] ResvSize, then sc_en_tot[2][2], sc_en[2][2][21], sc_xm[2][2][21],
+ * sc_xrmax[2][2], addr[2][2][3] (address1..3 of the last frame) and, last, the status word (0 or MP3MI_STREAM_* | frame << 8).
+ * Out: the signed quantised values ix[n_streams][2 * n_frames][channels][576], the mp3mi_frame_side records
+ * side[n_streams][n_frames], state_out, and *n_listed = the records k_mdct's tail could not decide and k_prep redid.
+ * MP3MI_ERR_ARG, and nothing is launched, for anything outside the loop's domain ("iteration_loop"; the bounds are
+ * derived in csrc/loop_debug.cpp): every xr is 0 (either sign) or 2^-500 <= |xr| <= 2^64; pe in [0, 1e8]; every ratio in [0, 1e30]
+ * (no NaN, no infinity anywhere); block_type 0..3; a known bitrate; at most 4096 streams of at most 64 frames; an initial state
+ * whose ResvSize is a multiple of 8 in [0, ResvMax] (ResvMax = min(7680 - bits per frame, 4088), 0 if negative), whose status word
+ * is 0, whose addresses lie in 0..576 and whose stored logarithms (sc_en_tot, sc_en, sc_xm) are within +-2^20 -- sc_xrmax, which is
+ * only compared with 0, may hold anything: every state_out of a legal chain is a legal state_in --; and no granule whose start step
+ * (quantanf_init, recomputed on the host in double, plus a margin of 1e-6 on 8 ln sfm) or whose all-zero step lies above 400,
+ * the end of the table of step sizes the search reads.  MP3MI_ERR_NO_DEVICE without a GPU. */
+int mp3mi_debug_iteration_loop(int rate_hz, int channels, int crc, int n_streams, int n_frames, const int32_t *kbps, const double *xr,
+                               const void *psy, const void *state_in, int16_t *ix, void *side, void *state_out, int32_t *n_listed);
 /* diagnostics: of the (granule, channel) records of the last call's LAST chunk, how many needed the second tier of
  * the unpredictability (k_part's check); *n_records receives their number.  Call after
  * mp3mi_batch_sync. */

@@ -462,7 +462,7 @@ __device__ __attribute__((noinline)) void mdct_prep_tail(const mp3mi_tables *T, 
         tp = 170;
     }
     if (band == 0 && wr) {
-        out->q0 = tp - 70;
+        out->q0 = mp3mi_clamp_q0(tp - 70); // (the end of k_loop's table of step sizes: k_prep.hip says why nothing changes with it)
         out->sc_en_tot = en_tot;
         out->sc_xrmax = (int) amax;
         out->nonzero = (amax != 0.0) ? 1 : 0;

@@ -180,7 +180,17 @@ __global__ void __launch_bounds__(64, 3) k_prep(const mp3mi_tables *__restrict__
             if (exact || !wave_any(S.amb && live)) break;
         }
         if (!live) continue; // (no collective below)
-        out->q0 = tp - 70;
+        // The start step is clamped to the end of the table of step sizes (mp3mi_tables::step, q <= 400) that k_loop reads at every
+        // step it visits.  8 ln sfm has no upper bound -- sfm is the geometric mean of the NON-ZERO lines, raised to their share of
+        // 576, over the arithmetic mean of all: one line of 2^-40 behind silence gives 493, a start step of 423 -- and the bisection
+        // between the start step and 200 then probes up to one below it.  Nothing a stream shows changes with the clamp: a granule
+        // that starts at 46 or above ends at or above it (the bisection stays between its ends, inner_loop only raises the step), so
+        // with global_gain >= 256, the reference's assertion (src/loop.c:358), and the stream is void either way; a start step
+        // above 400 needs every line below 1e-10, which quantises to 0 at every step from 46 on, so every pass counts 0 bits and the
+        // band noise is the band's energy whatever the step: the distortion loop takes the same decisions, an earlier event
+        // (huff_bits < 0) happens or does not happen in both, and the status word -- the first event's code and frame -- is the same.
+        // (tests/hipemu/loop_steps_main.cpp runs such granules under a bounds check.)
+        out->q0 = mp3mi_clamp_q0(tp - 70);
         out->sc_en_tot = prep_ilog2(T, S.tot);
         out->sc_xrmax = (int) S.amax;
         out->nonzero = (S.amax != 0.0) ? 1 : 0;

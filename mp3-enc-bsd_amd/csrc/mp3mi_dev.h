@@ -197,6 +197,8 @@ typedef struct {
     uint16_t peak[MP3MI_PEAK_CELLS]; /* non-short granules only, by k_mdct's tail alone (mdct_peak_tail; k_prep leaves it): a line of cell c with the largest |xr| */
 } mp3mi_loop_prep;
 #define MP3MI_LOOP_PREP_HEAD 472     /* offsetof(mp3mi_loop_prep, peak) */
+/* q0 as its two writers store it (k_prep.hip, k_fbmdct.hip): never past the last entry of step[] */
+MP3MI_DEVFN int mp3mi_clamp_q0(int q0) { return q0 > MP3MI_STEP_MIN + MP3MI_STEP_N - 1 ? MP3MI_STEP_MIN + MP3MI_STEP_N - 1 : q0; }
 
 /* Peak cells.  The quantiser is monotone in |xr| (ix = max{p : tab[p] <= |xr| / step}, k_loop.hip) and everything the search
  * does to the spectrum -- pre-emphasis, amplification -- multiplies all lines of a scalefactor band by one positive factor,

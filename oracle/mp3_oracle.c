@@ -711,6 +711,10 @@ static void mdct_frame(mp3o_stream *s, double xr[2][2][576])
 /* ------------------------------------------------------------------------- */
 typedef struct { double l[21]; double s[12][3]; } xmin_t;
 
+/* mp3o_iteration_loop's record of the granule in progress (NULL everywhere else): what the search reached */
+static mp3o_loop_trace_t *g_trace;
+static int g_trace_iter; /* the iteration whose xfsf / xmin the record keeps (0: the last one) */
+
 static int r_nint(double in)
 { /* src/loop.c:2020-2029 (HAVE_NINT undefined) */
     return (in < 0) ? (int) (in - 0.5) : (int) (in + 0.5);
@@ -1140,6 +1144,11 @@ static void bin_search_StepSize(const mp3o_stream *s, int desired_rate, double s
         g->quantizerStepSize = next;
         quantize(s, xrs, ix, g);
         bit = count_bits(s, ix, g);
+        if (g_trace) {
+            g_trace->n_passes++; g_trace->n_probes++;
+            if (bit == desired_rate) g_trace->bisect_equal = 1;
+            g_trace->probe_prev = (int) last; g_trace->probe_last = (int) next;
+        }
         CENSUS(CEN_BISECT, 1); CENSUS(CEN_BISECT_OVER, bit > desired_rate); CENSUS(CEN_BISECT_EQUAL, bit == desired_rate);
         CENSUS(CEN_BISECT_ALLZERO, ix_max(ix, 0, 576) == 0);
         if (bit > desired_rate) top = next;
@@ -1161,6 +1170,7 @@ static int inner_loop(const mp3o_stream *s, const double *xrs, int *ix, int max_
             g->quantizerStepSize += 1.0;
             quantize(s, xrs, ix, g);
         } while (ix_max(ix, 0, 576) > 8191 + 14);
+        if (g_trace) g_trace->n_passes++;
         CENSUS(CEN_INNER_EXTRA, 1); CENSUS(CEN_PASS_ALLZERO, ix_max(ix, 0, 576) == 0);
         calc_runlen(ix, g);
         bits = count1_bitcount(ix, g);
@@ -1301,6 +1311,26 @@ static int quantanf_init(const double *xr)
     return (int) (tp - 70.0);
 }
 
+/* the noise of every band against its allowed distortion as the loop is about to compare them: the closeness measure of k_loop's
+   loop_noise_close, and the values themselves for the chosen iteration (after = 1: behind pre-emphasis' multiplication) */
+static void trace_noise(const gr_info_t *g, double xfsf[4][21], const xmin_t *xm, int iteration, int after)
+{
+    int sfb, w;
+    const int keep = g_trace_iter == 0 || g_trace_iter == iteration;
+    for (sfb = 0; sfb < (int) g->sfb_lmax; sfb++) {
+        const double n = xfsf[0][sfb], m = xm->l[sfb];
+        if (m > 0.0 && fabs(n - m) / m < g_trace->closest) g_trace->closest = fabs(n - m) / m;
+        if (keep) { g_trace->xfsf[sfb] = n; (after ? g_trace->xmin_pre : g_trace->xmin)[sfb] = m; }
+    }
+    for (sfb = (int) g->sfb_smax; sfb < 12; sfb++)
+        for (w = 0; w < 3; w++) {
+            const double n = xfsf[w + 1][sfb], m = xm->s[sfb][w];
+            if (m > 0.0 && fabs(n - m) / m < g_trace->closest) g_trace->closest = fabs(n - m) / m;
+            if (keep) { g_trace->xfsf[sfb * 3 + w] = n; (after ? g_trace->xmin_pre : g_trace->xmin)[sfb * 3 + w] = m; }
+        }
+    if (keep) g_trace->kept_iter = iteration;
+}
+
 static int outer_loop(mp3o_stream *s, double *xr, int max_bits, xmin_t *xm, int gr, int ch)
 { /* src/loop.c:415-558 */
     gr_info_t *g = &s->side.gr[gr][ch];
@@ -1322,11 +1352,26 @@ static int outer_loop(mp3o_stream *s, double *xr, int max_bits, xmin_t *xm, int 
             for (i = 0; i < 3; i++) scalesave_s[sfb][i] = s->scalefac_s[gr][ch][sfb][i];
         save_preflag = (int) g->preflag;
         save_compress = (int) g->scalefac_compress;
+        if (g_trace) trace_noise(g, xfsf, xm, iteration, 0);
         preemphasis(s, xr, xfsf, xm, gr, ch);
+        if (g_trace && g->preflag && !save_preflag && !g_trace->pre_iter) {
+            int m = 0, b;
+            for (b = 0; b < 4; b++) m |= (int) s->side.scfsi[ch][b];
+            if (!(gr == 1 && m)) { /* fired here, not inherited from granule 0 */
+                g_trace->pre_iter = iteration;
+                trace_noise(g, xfsf, xm, iteration, 1); /* the second comparison: against the thresholds it moved */
+            }
+        }
         over = amp_scalefac_bands(s, xr, xfsf, xm, gr, ch, iteration);
         CENSUS(CEN_OUTER_NO_AMP, over == 0);
-        if ((status = loop_break(s, g, gr, ch)) == 0) status = scale_bitcount(s, gr, ch);
+        if ((status = loop_break(s, g, gr, ch)) == 0) {
+            status = scale_bitcount(s, gr, ch);
+            if (g_trace && status) g_trace->exit_how = MP3O_EXIT_SCALE_BITCOUNT;
+        } else if (g_trace)
+            g_trace->exit_how = MP3O_EXIT_LOOP_BREAK;
+        if (g_trace && over == 0) g_trace->exit_how = MP3O_EXIT_NO_OVER; /* (the reference's while tests both: over == 0 is named first) */
     } while (status == 0 && over > 0);
+    if (g_trace) g_trace->n_outer = iteration;
     g->preflag = (unsigned) save_preflag;
     g->scalefac_compress = (unsigned) save_compress;
     for (sfb = 0; sfb < 21; sfb++) s->scalefac_l[gr][ch][sfb] = scalesave_l[sfb];
@@ -1349,10 +1394,15 @@ static int ResvMaxBits(const mp3o_stream *s, double pe, int mean_bits)
     if (more_bits > 100) {
         int frac = (s->ResvSize * 6) / 10;
         add_bits = (frac < more_bits) ? frac : more_bits;
+        if (g_trace) g_trace->add_branch |= 1;
     }
     over_bits = s->ResvSize - ((s->ResvMax * 8) / 10) - add_bits;
-    if (over_bits > 0) add_bits += over_bits;
+    if (over_bits > 0) {
+        add_bits += over_bits;
+        if (g_trace) g_trace->add_branch |= 2;
+    }
     max_bits += add_bits;
+    if (g_trace) { g_trace->more_bits = more_bits; g_trace->add_bits = add_bits; if (max_bits > 4095) g_trace->add_branch |= 4; }
     if (max_bits > 4095) max_bits = 4095;
     return max_bits;
 }
@@ -1388,8 +1438,8 @@ static void ResvFrameEnd(mp3o_stream *s, int mean_bits)
     }
 }
 
-static void iteration_loop(mp3o_stream *s, double pe[2][2], double xr_org[2][2][576],
-                           double ratio_l[2][2][21], double ratio_s[2][2][12][3])
+static void iteration_loop_traced(mp3o_stream *s, double pe[2][2], double xr_org[2][2][576],
+                                  double ratio_l[2][2][21], double ratio_s[2][2][12][3], mp3o_loop_trace_t *trace)
 { /* src/loop.c:232-362 */
     double xr[2][2][576];
     xmin_t xm;
@@ -1404,9 +1454,19 @@ static void iteration_loop(mp3o_stream *s, double pe[2][2], double xr_org[2][2][
         for (ch = 0; ch < s->channels; ch++) {
             gr_info_t *g = &s->side.gr[gr][ch];
             gr_deco(g);
+            if (trace) {
+                g_trace = &trace[gr * s->channels + ch];
+                memset(g_trace, 0, sizeof(*g_trace));
+                g_trace->closest = HUGE_VAL;
+            }
             calc_xmin(s, xr[gr][ch], ratio_l[gr][ch], ratio_s[gr][ch], g, &xm);
             calc_scfsi(s, xr[gr][ch], &xm, ch, gr);
             max_bits = ResvMaxBits(s, pe[gr][ch], mean_bits);
+            if (g_trace) {
+                g_trace->max_bits = max_bits;
+                g_trace->resv_before = s->ResvSize;
+                if (gr == 1) for (i = 0; i < 4; i++) g_trace->scfsi_mask |= (int) s->side.scfsi[ch][i] << i;
+            }
             for (sfb = 0; sfb < 21; sfb++) s->scalefac_l[gr][ch][sfb] = 0;
             for (sfb = 0; sfb < 13; sfb++)
                 for (i = 0; i < 3; i++) s->scalefac_s[gr][ch][sfb][i] = 0;
@@ -1417,13 +1477,22 @@ static void iteration_loop(mp3o_stream *s, double pe[2][2], double xr_org[2][2][
             g->scalefac_scale = 0; g->quantizerStepSize = 0.0; g->count1table_select = 0;
             if (fabs(xr_max(xr[gr][ch], 0, 576)) != 0.0) {
                 g->quantizerStepSize = (double) quantanf_init(xr[gr][ch]);
+                if (g_trace) g_trace->q0 = (int) g->quantizerStepSize;
                 g->part2_3_length = (unsigned) outer_loop(s, xr[gr][ch], max_bits, &xm, gr, ch);
             }
+            if (g_trace) { g_trace->q_final = (int) g->quantizerStepSize; g_trace->part2_3_length = (int) g->part2_3_length; }
             s->ResvSize += (mean_bits / s->channels) - (int) g->part2_3_length; /* ResvAdjust */
             g->global_gain = (unsigned) r_nint(g->quantizerStepSize + 210.0);
             if (g->global_gain >= 256 && !s->ref_abort) s->ref_abort = MP3O_ABORT_GLOBAL_GAIN; /* assert, src/loop.c:358 */
+            g_trace = NULL;
         }
     ResvFrameEnd(s, mean_bits);
+}
+
+static void iteration_loop(mp3o_stream *s, double pe[2][2], double xr_org[2][2][576],
+                           double ratio_l[2][2][21], double ratio_s[2][2][12][3])
+{
+    iteration_loop_traced(s, pe, xr_org, ratio_l, ratio_s, NULL);
 }
 
 /* ------------------------------------------------------------------------- */
@@ -1785,6 +1854,102 @@ size_t mp3o_format_frames(int rate_hz, int channels, int kbps, int mode, int mod
     memcpy(*out, p, len);
     mp3o_close(s);
     return len;
+}
+
+/* Test entry (tests/test_loop_edges.py): iteration_loop() above on a chain of n_frames frames of GIVEN records, one stream. */
+int mp3o_iteration_loop(int rate_hz, int channels, int kbps, int crc, int n_frames, const double *xr_in, const void *psy_v,
+                        const int32_t *state_in, int trace_iter, int16_t *ix, int32_t *side, int32_t *state_out,
+                        mp3o_loop_trace_t *trace)
+{
+    enum { GR_WORDS = 15 + 39, FRAME_WORDS = 10 + 4 * GR_WORDS, STATE_WORDS = 1 + 4 + 84 + 84 + 4 + 12 + 1, PSY_BYTES = 8 * (1 + 21 + 36) + 8 };
+    static double xr[2][2][576], pe[2][2], ratio_l[2][2][21], ratio_s[2][2][12][3];
+    const unsigned char *psy = (const unsigned char *) psy_v;
+    mp3o_stream *s = mp3o_open(rate_hz, kbps, channels);
+    int f, gr, ch, i, w, k, died_in = 0;
+    if (!s) return -1;
+    mp3o_set_options(s, channels == 1 ? 3 : 0, crc, 0, 0, 0);
+    if (state_in) { /* the statics of src/loop.c:618-621 and src/reservoir.c:36, and the address1..3 the caller's gr_info keeps */
+        const int32_t *p = state_in + 1;
+        s->ResvSize = state_in[0];
+        memcpy(s->sc_en_tot, p, sizeof(s->sc_en_tot)); p += 4;
+        memcpy(s->sc_en, p, sizeof(s->sc_en)); p += 84;
+        memcpy(s->sc_xm, p, sizeof(s->sc_xm)); p += 84;
+        memcpy(s->sc_xrmax, p, sizeof(s->sc_xrmax)); p += 4;
+        for (gr = 0; gr < 2; gr++)
+            for (ch = 0; ch < 2; ch++) {
+                s->side.gr[gr][ch].address1 = (unsigned) *p++;
+                s->side.gr[gr][ch].address2 = (unsigned) *p++;
+                s->side.gr[gr][ch].address3 = (unsigned) *p++;
+            }
+        s->ref_abort = *p;
+    }
+    g_trace_iter = trace_iter;
+    memset(side, 0, (size_t) n_frames * FRAME_WORDS * 4);
+    for (f = 0; f < n_frames; f++) {
+        int32_t *fs = side + (size_t) f * FRAME_WORDS;
+        const int had = s->ref_abort;
+        memset(xr, 0, sizeof(xr)); memset(pe, 0, sizeof(pe)); memset(ratio_l, 0, sizeof(ratio_l)); memset(ratio_s, 0, sizeof(ratio_s));
+        for (gr = 0; gr < 2; gr++)
+            for (ch = 0; ch < channels; ch++) {
+                const size_t rec = (size_t) (2 * f + gr) * channels + ch;
+                const unsigned char *r = psy + rec * PSY_BYTES;
+                int32_t bt;
+                gr_info_t *g = &s->side.gr[gr][ch];
+                memcpy(xr[gr][ch], xr_in + rec * 576, sizeof(xr[0][0]));
+                memcpy(&pe[gr][ch], r, 8);
+                memcpy(ratio_l[gr][ch], r + 8, sizeof(ratio_l[0][0]));
+                memcpy(ratio_s[gr][ch], r + 8 * 22, sizeof(ratio_s[0][0]));
+                memcpy(&bt, r + 8 * 58, 4);
+                /* what L3psycho_anal's caller leaves in the granule (src/musicin.c; psy_granule above) */
+                g->block_type = (unsigned) bt;
+                g->window_switching_flag = bt != 0;
+                g->mixed_block_flag = 0;
+            }
+        s->side.main_data_begin = s->ResvSize / 8; /* (the formatter's, which the reservoir's size is by construction) */
+        iteration_loop_traced(s, pe, xr, ratio_l, ratio_s, trace ? trace + (size_t) f * 2 * channels : NULL);
+        if (s->ref_abort && !had) died_in = f;
+        fs[0] = s->side.main_data_begin;
+        fs[1] = s->side.resvDrain;
+        for (ch = 0; ch < channels; ch++)
+            for (i = 0; i < 4; i++) fs[2 + 4 * ch + i] = (int32_t) s->side.scfsi[ch][i];
+        for (gr = 0; gr < 2; gr++)
+            for (ch = 0; ch < channels; ch++) {
+                const gr_info_t *g = &s->side.gr[gr][ch];
+                int32_t *q = fs + 10 + (2 * gr + ch) * GR_WORDS;
+                int16_t *v = ix + ((size_t) (2 * f + gr) * channels + ch) * 576;
+                q[0] = (int32_t) g->part2_3_length; q[1] = (int32_t) g->big_values; q[2] = (int32_t) g->count1;
+                q[3] = (int32_t) g->global_gain; q[4] = (int32_t) g->scalefac_compress; q[5] = (int32_t) g->window_switching_flag;
+                q[6] = (int32_t) g->block_type; q[7] = (int32_t) g->table_select[0]; q[8] = (int32_t) g->table_select[1];
+                q[9] = (int32_t) g->table_select[2]; q[10] = (int32_t) g->region0_count; q[11] = (int32_t) g->region1_count;
+                q[12] = (int32_t) g->preflag; q[13] = (int32_t) g->count1table_select; q[14] = (int32_t) g->part2_length;
+                if (g->window_switching_flag && g->block_type == 2) {
+                    for (i = 0; i < 12; i++)
+                        for (w = 0; w < 3; w++) q[15 + 3 * i + w] = s->scalefac_s[gr][ch][i][w];
+                } else
+                    for (i = 0; i < 21; i++) q[15 + i] = s->scalefac_l[gr][ch][i];
+                for (k = 0; k < 576; k++) { /* the sign the formatter gives a value (src/l3bitstream.c:115-125) */
+                    const int m = s->l3_enc[gr][ch][k];
+                    v[k] = (int16_t) ((xr_in[((size_t) (2 * f + gr) * channels + ch) * 576 + k] < 0 && m > 0) ? -m : m);
+                }
+            }
+    }
+    {
+        int32_t *p = state_out + 1;
+        state_out[0] = s->ResvSize;
+        memcpy(p, s->sc_en_tot, sizeof(s->sc_en_tot)); p += 4;
+        memcpy(p, s->sc_en, sizeof(s->sc_en)); p += 84;
+        memcpy(p, s->sc_xm, sizeof(s->sc_xm)); p += 84;
+        memcpy(p, s->sc_xrmax, sizeof(s->sc_xrmax)); p += 4;
+        for (gr = 0; gr < 2; gr++)
+            for (ch = 0; ch < 2; ch++) {
+                *p++ = (int32_t) s->side.gr[gr][ch].address1;
+                *p++ = (int32_t) s->side.gr[gr][ch].address2;
+                *p++ = (int32_t) s->side.gr[gr][ch].address3;
+            }
+        *p = (state_in && state_in[STATE_WORDS - 1]) ? state_in[STATE_WORDS - 1] : (s->ref_abort ? (s->ref_abort | died_in << 8) : 0);
+    }
+    mp3o_close(s);
+    return 0;
 }
 
 mp3o_stream *mp3o_open(int rate_hz, int kbps, int channels)
