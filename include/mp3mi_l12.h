@@ -88,6 +88,21 @@ typedef struct mp3mi_l12_frame_seams {
 void mp3mi_l12_batch_debug_enable(mp3mi_l12_batch *b, int on);
 long mp3mi_l12_batch_debug_fetch(mp3mi_l12_batch *b, void *host_dst, size_t cap, int *first_frame, int *n_chunk_frames);
 
+/* Self-test hook: k12_alloc alone, as the batch launches it (csrc/l12_alloc_debug.cpp; k_l12.hip is the product's), on n_streams x
+ * n_frames frames of GIVEN subband samples sb[n_streams][n_frames][channels][parts][12][32] (parts 1 / 3: sb_sample of
+ * src/musicin.c:622-626, 662-666, before k_filter's sign change, which the hook applies) and signal-to-mask ratios
+ * ratio[n_streams][n_frames][passes][channels][32] (passes = layer: Layer II keeps the larger of its two).  One format per call --
+ * layer, rate_hz, channels, mode (MP3MI_MODE_*), crc, hdr_flags (bit 3 copyright, bit 2 original, bits 1-0 emphasis) -- and a
+ * bitrate per stream.  slot0 (0..17) is the phase of the first frame's first slot in k_filter's 18-slot granules.
+ * Out: per stream the frames' bytes one behind the other and the file's last byte, out_len[n_streams], and
+ * seams[n_streams][n_frames] records of mp3mi_l12_frame_seams.  MP3MI_ERR_ARG, and nothing is launched, outside the domain
+ * k12_alloc takes on trust (derived in csrc/l12_alloc_debug.cpp): a sample that is not finite or above 2.0 in magnitude, a ratio
+ * that is not finite, a format the batch would refuse, more than 4096 streams or 64 frames, out_stride below
+ * n_frames * (the longest frame's bytes; 38 at least for two-channel Layer I) + 1.  MP3MI_ERR_NO_DEVICE without a GPU. */
+int mp3mi_debug_l12_alloc(int layer, int rate_hz, int channels, int mode, int crc, int hdr_flags, int slot0, int n_streams,
+                          int n_frames, const int32_t *kbps, const double *sb, const float *ratio, uint8_t *out, size_t out_stride,
+                          uint32_t *out_len, void *seams);
+
 /* milliseconds inside the kernels of all encode calls since create (HIP events on the batch's stream), and the calls */
 int mp3mi_l12_batch_total_timing(mp3mi_l12_batch *b, double *all_kernels_ms, long *calls);
 /* the same per kernel, HIP events around every launch: [0] k_fft12, [1] k12_psy, [2] k_filter,

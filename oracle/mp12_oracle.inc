@@ -279,6 +279,24 @@ static void l12_transmission_pattern(unsigned scalar[2][3][32], unsigned scfsi[2
 /* ---------------------------------------------------------------------------------------------------------------- */
 /* bit allocation, src/encode.c:782-1172                                                                            */
 /* ---------------------------------------------------------------------------------------------------------------- */
+static mp3o_l12_alloc_trace_t *l12_trace; /* what the allocation reached, which no output shows (mp3o_l12_alloc_frames); NULL: none kept */
+
+static void l12_trace_step(int ad, int needed)
+{ /* one turn of *_a_bit_allocation's loop: the chosen band's step costs `needed` - what was spent before it of `ad` */
+    mp3o_l12_alloc_trace_t *t = l12_trace;
+    if (!t) return;
+    if (ad >= needed) {
+        t->steps++;
+        if (t->closed_no_room) t->granted_after_close++;
+        if (t->closed_no_room && ad == needed) t->exact_after_close++;
+        if (ad - needed < t->min_slack) t->min_slack = ad - needed;
+    } else {
+        if (t->closed_no_room && needed - ad < t->min_short_after_close) t->min_short_after_close = needed - ad;
+        t->closed_no_room++;
+        if (needed - ad < t->min_short) t->min_short = needed - ad;
+    }
+}
+
 static int l12_js_bound(int lay, int m_ext)
 { /* src/common.c:320-331 */
     static const int jsb_table[3][4] = {{4, 8, 12, 16}, {4, 8, 12, 16}, {0, 4, 8, 16}};
@@ -357,6 +375,7 @@ static void l1_a_bit_allocation(l12_stream *L, double perm_smr[2][32], unsigned 
             if (used[min_ch][min_sb]) { smpl_bits = 12; scale_bits = 0; }
             else { smpl_bits = 24; scale_bits = 6; }
             if (min_sb >= jsbound) scale_bits *= stereo;
+            l12_trace_step(ad, bspl + bscf + scale_bits + smpl_bits);
             if (ad >= bspl + bscf + scale_bits + smpl_bits) {
                 bspl += smpl_bits;
                 bscf += scale_bits;
@@ -414,6 +433,7 @@ static void l2_a_bit_allocation(l12_stream *L, double perm_smr[2][32], unsigned 
                     scale += 6 * L12_SFS_PER_SCFSI[scfsi[oth_ch][min_sb]];
                 }
             }
+            l12_trace_step(ad, bspl + bscf + bsel + seli + scale + increment);
             if (ad >= bspl + bscf + bsel + seli + scale + increment) {
                 ba = (int) ++bit_alloc[min_ch][min_sb];
                 bspl += increment;
@@ -444,6 +464,7 @@ static void l12_main_bit_allocation(l12_stream *L, double perm_smr[2][32], unsig
         L->mode_ext = 0;
         L->jsbound = L->sblimit;
         rq = (L->layer == 1) ? l1_bits_for_nonoise(L, perm_smr) : l2_bits_for_nonoise(L, perm_smr, scfsi);
+        if (l12_trace) l12_trace->rq[l12_trace->n_rq++] = rq;
         if (rq > *adb) {
             L->mode = 1;
             mode_ext = 4;
@@ -451,6 +472,7 @@ static void l12_main_bit_allocation(l12_stream *L, double perm_smr[2][32], unsig
                 --mode_ext;
                 L->jsbound = l12_js_bound(L->layer, mode_ext);
                 rq = (L->layer == 1) ? l1_bits_for_nonoise(L, perm_smr) : l2_bits_for_nonoise(L, perm_smr, scfsi);
+                if (l12_trace) l12_trace->rq[l12_trace->n_rq++] = rq;
             } while ((rq > *adb) && (mode_ext > 0));
             L->mode_ext = mode_ext;
         }
@@ -503,36 +525,49 @@ static unsigned l12_crc_calc(const l12_stream *L, unsigned bit_alloc[2][32], uns
 /* ---------------------------------------------------------------------------------------------------------------- */
 /* one frame, src/musicin.c:620-704                                                                                 */
 /* ---------------------------------------------------------------------------------------------------------------- */
+static void l12_encode_frame_tail(l12_stream *L, double ltmin[2][32], stage_dump_l12_t *d);
+
 static void l12_encode_frame(l12_stream *L, stage_dump_l12_t *d)
+{
+    mp3o_stream *B = L->base;
+    const int stereo = L->channels, nparts = (L->layer == 1) ? 1 : 3;
+    double ltmin[2][32];
+    float snr32[32];
+    const short *win_buf[2];
+    int i, j, k;
+    memset(ltmin, 0, sizeof(ltmin));
+    win_buf[0] = L->buffer[0]; win_buf[1] = L->buffer[1];
+    for (i = 0; i < nparts; i++)
+        for (j = 0; j < 12; j++)
+            for (k = 0; k < stereo; k++) {
+                filterbank_slot(B, win_buf[k], k, L->sb_sample[k][i][j]);
+                win_buf[k] += 32;
+            }
+    for (k = 0; k < stereo; k++) {
+        l12_psycho_anal(L, L->buffer[k], k, snr32);
+        for (i = 0; i < 32; i++) ltmin[k][i] = (double) snr32[i];
+    }
+    l12_encode_frame_tail(L, ltmin, d);
+}
+
+/* everything behind the filterbank and the model: from L->sb_sample and the signal-to-mask ratios to the frame's bits.  (The
+ * reference computes the scale factors before psycho_anal; neither reads what the other writes.) */
+static void l12_encode_frame_tail(l12_stream *L, double ltmin[2][32], stage_dump_l12_t *d)
 {
     double (*sb_sample)[3][12][32] = L->sb_sample, (*j_sample)[3][12][32] = L->j_sample;
     unsigned (*sbband)[3][12][32] = L->sbband;
     mp3o_stream *B = L->base;
     const int stereo = L->channels, nparts = (L->layer == 1) ? 1 : 3;
     unsigned scalar[2][3][32], j_scale[1][3][32], scfsi[2][32], bit_alloc[2][32], crc = 0;
-    double ltmin[2][32];
-    float snr32[32];
-    const short *win_buf[2];
     int adb = L->frame_bits, i, j, k, s, sblimit = L->sblimit, jsbound;
     memset(scalar, 0, sizeof(scalar)); memset(j_scale, 0, sizeof(j_scale)); memset(scfsi, 0, sizeof(scfsi));
-    memset(bit_alloc, 0, sizeof(bit_alloc)); memset(ltmin, 0, sizeof(ltmin));
-    win_buf[0] = L->buffer[0]; win_buf[1] = L->buffer[1];
-    for (i = 0; i < nparts; i++)
-        for (j = 0; j < 12; j++)
-            for (k = 0; k < stereo; k++) {
-                filterbank_slot(B, win_buf[k], k, sb_sample[k][i][j]);
-                win_buf[k] += 32;
-            }
+    memset(bit_alloc, 0, sizeof(bit_alloc));
     l12_scale_factor_calc(sb_sample, scalar, stereo, nparts, sblimit);
     if (L->actual_mode == 1) { /* I_ / II_combine_LR, src/encode.c:469-494 */
         for (i = 0; i < sblimit; ++i)
             for (j = 0; j < 12; ++j)
                 for (s = 0; s < nparts; ++s) j_sample[0][s][j][i] = .5 * (sb_sample[0][s][j][i] + sb_sample[1][s][j][i]);
         l12_scale_factor_calc(j_sample, j_scale, 1, nparts, sblimit);
-    }
-    for (k = 0; k < stereo; k++) {
-        l12_psycho_anal(L, L->buffer[k], k, snr32);
-        for (i = 0; i < 32; i++) ltmin[k][i] = (double) snr32[i];
     }
     if (L->layer == 2) l12_transmission_pattern(scalar, scfsi, stereo, sblimit);
     l12_main_bit_allocation(L, ltmin, scfsi, bit_alloc, &adb);
@@ -541,7 +576,7 @@ static void l12_encode_frame(l12_stream *L, stage_dump_l12_t *d)
     if (d) {
         memset(d, 0, sizeof(*d));
         memcpy(d->sb_sample, sb_sample, sizeof(L->sb_sample));
-        memcpy(d->ltmin, ltmin, sizeof(ltmin));
+        memcpy(d->ltmin, ltmin, sizeof(d->ltmin));
         for (k = 0; k < 2; k++)
             for (i = 0; i < 32; i++) {
                 for (s = 0; s < 3; s++) d->scalar[k][s][i] = (int32_t) scalar[k][s][i];
@@ -642,27 +677,17 @@ static void l12_encode_frame(l12_stream *L, stage_dump_l12_t *d)
 /* ---------------------------------------------------------------------------------------------------------------- */
 /* a whole stream                                                                                                   */
 /* ---------------------------------------------------------------------------------------------------------------- */
-size_t mp3o_encode_pcm_l12(int layer, int rate_hz, int kbps, int channels, const char *mode, const int16_t *pcm,
-                           size_t n_total, uint8_t **out, stage_dump_l12_t *dumps, int max_dumps)
-{ /* mode: NULL, or the driver's -m letter (s / d / j / m) followed by e / c / o for -e / -c / -o.
-     Returns 0 and *out = NULL for what the reference refuses. */
+/* a fresh stream as the driver sets it up (src/musicin.c:528-581, src/common.c:291-347); with_tables: the window, the FFT and the
+ * filterbank's matrix too (what is in front of the scale factors) */
+static l12_stream *l12_stream_new(int layer, int ri, int kbps, int bi, int channels, int m, const char *mode, int with_tables)
+{
     static const double s_freq[3] = {44.1, 48, 32};
     l12_stream *L;
     mp3o_stream *B;
-    size_t pos = 0, len, per_frame;
-    int ri, bi, i, j, frame = 0, m, whole_SpF, spf, br_per_ch, sfrq;
-    *out = NULL;
-    if (layer != 1 && layer != 2) return 0;
-    if (rate_hz == 44100) ri = 0; else if (rate_hz == 48000) ri = 1; else if (rate_hz == 32000) ri = 2; else return 0;
-    for (bi = 1; bi < 15; bi++)
-        if (L12_BITRATES[layer - 1][bi] == kbps) break;
-    if (bi == 15 || (channels != 1 && channels != 2)) return 0;
-    m = (channels == 1) ? 3 : 0;
-    if (mode && mode[0]) m = mode[0] == 'm' ? 3 : mode[0] == 'd' ? 2 : mode[0] == 'j' ? 1 : 0;
-    if ((channels == 1) != (m == 3)) return 0;
+    int i, whole_SpF, spf, br_per_ch, sfrq;
     L = (l12_stream *) calloc(1, sizeof(*L));
     B = (mp3o_stream *) calloc(1, sizeof(*B));
-    B->T = make_tables(ri);
+    B->T = with_tables ? make_tables(ri) : NULL;
     L->base = B;
     L->layer = layer; L->ri = ri; L->kbps = kbps; L->bitrate_index = bi; L->channels = channels;
     L->actual_mode = L->mode = m; L->mode_ext = 0;
@@ -693,7 +718,30 @@ size_t mp3o_encode_pcm_l12(int layer, int rate_hz, int kbps, int channels, const
         memcpy(L->alloc, T12_ALLOC[L->table], sizeof(L->alloc));
     }
     L->jsbound = (m == 1) ? l12_js_bound(layer, 0) : L->sblimit; /* hdr_to_frps, src/common.c:333-347 */
-    l12_psy_init(L);
+    if (with_tables) l12_psy_init(L);
+    return L;
+}
+
+size_t mp3o_encode_pcm_l12(int layer, int rate_hz, int kbps, int channels, const char *mode, const int16_t *pcm,
+                           size_t n_total, uint8_t **out, stage_dump_l12_t *dumps, int max_dumps)
+{ /* mode: NULL, or the driver's -m letter (s / d / j / m) followed by e / c / o for -e / -c / -o.
+     Returns 0 and *out = NULL for what the reference refuses. */
+    l12_stream *L;
+    mp3o_stream *B;
+    size_t pos = 0, len, per_frame;
+    int ri, bi, i, j, frame = 0, m, spf;
+    *out = NULL;
+    if (layer != 1 && layer != 2) return 0;
+    if (rate_hz == 44100) ri = 0; else if (rate_hz == 48000) ri = 1; else if (rate_hz == 32000) ri = 2; else return 0;
+    for (bi = 1; bi < 15; bi++)
+        if (L12_BITRATES[layer - 1][bi] == kbps) break;
+    if (bi == 15 || (channels != 1 && channels != 2)) return 0;
+    m = (channels == 1) ? 3 : 0;
+    if (mode && mode[0]) m = mode[0] == 'm' ? 3 : mode[0] == 'd' ? 2 : mode[0] == 'j' ? 1 : 0;
+    if ((channels == 1) != (m == 3)) return 0;
+    L = l12_stream_new(layer, ri, kbps, bi, channels, m, mode, 1);
+    B = L->base;
+    spf = (layer == 1) ? 384 : 1152;
     per_frame = (size_t) spf * (size_t) channels;
     while (pos < n_total) { /* get_audio / read_samples, src/encode.c:123-256 */
         size_t n = n_total - pos < per_frame ? n_total - pos : per_frame;
@@ -728,4 +776,73 @@ size_t mp3o_encode_pcm_l12(int layer, int rate_hz, int kbps, int channels, const
     free(B);
     free(L);
     return len;
+}
+
+/* ---------------------------------------------------------------------------------------------------------------- */
+/* the frame encoder alone, on given subband samples and ratios (mp3_oracle.h)                                      */
+/* ---------------------------------------------------------------------------------------------------------------- */
+void mp3o_l12_tables(double multiple[64], uint16_t alloc[4][32][16][4], int32_t sblimit[4], double snr[18], double qa[17], double qb[17])
+{
+    int i;
+    memcpy(multiple, T12_MULTIPLE, sizeof(T12_MULTIPLE));
+    memcpy(alloc, T12_ALLOC, sizeof(T12_ALLOC));
+    for (i = 0; i < 4; i++) sblimit[i] = T12_ALLOC_SBLIMIT[i];
+    memcpy(snr, L12_SNR, sizeof(L12_SNR));
+    memcpy(qa, L12_QA, sizeof(L12_QA));
+    memcpy(qb, L12_QB, sizeof(L12_QB));
+}
+
+int mp3o_l12_alloc_frames(int layer, int rate_hz, int channels, const char *mode, int n, const int32_t *kbps, const double *sb,
+                          const float *ratio, uint8_t *out, size_t out_stride, uint32_t *out_len, stage_dump_l12_t *dumps,
+                          mp3o_l12_alloc_trace_t *trace)
+{
+    const int nparts = layer == 1 ? 1 : 3, passes = layer == 1 ? 1 : 2;
+    int ri, m, c, k, i, t;
+    if ((layer != 1 && layer != 2) || (channels != 1 && channels != 2) || n < 0 || !kbps || !sb || !ratio || !out || !out_len) return -1;
+    if (rate_hz == 44100) ri = 0; else if (rate_hz == 48000) ri = 1; else if (rate_hz == 32000) ri = 2; else return -1;
+    m = (channels == 1) ? 3 : 0;
+    if (mode && mode[0]) m = mode[0] == 'm' ? 3 : mode[0] == 'd' ? 2 : mode[0] == 'j' ? 1 : 0;
+    if ((channels == 1) != (m == 3)) return -1;
+    for (c = 0; c < n; c++) {
+        int bi;
+        for (bi = 1; bi < 15; bi++)
+            if (L12_BITRATES[layer - 1][bi] == kbps[c]) break;
+        if (bi == 15) return -1;
+    }
+    for (c = 0; c < n; c++) {
+        l12_stream *L;
+        double ltmin[2][32];
+        const double *x = sb + (size_t) c * channels * nparts * 12 * 32;
+        const float *r = ratio + (size_t) c * passes * channels * 32;
+        size_t len;
+        int bi;
+        for (bi = 1; bi < 15; bi++)
+            if (L12_BITRATES[layer - 1][bi] == kbps[c]) break;
+        L = l12_stream_new(layer, ri, kbps[c], bi, channels, m, mode, 0);
+        memset(ltmin, 0, sizeof(ltmin));
+        for (k = 0; k < channels; k++) {
+            for (t = 0; t < nparts; t++) memcpy(L->sb_sample[k][t], x + ((size_t) k * nparts + t) * 12 * 32, sizeof(double) * 12 * 32);
+            for (i = 0; i < 32; i++) { /* src/psy.c:391-395: Layer II keeps the larger of its two passes */
+                const float a = r[(size_t) k * 32 + i], b = passes == 2 ? r[((size_t) channels + k) * 32 + i] : a;
+                ltmin[k][i] = (double) ((passes == 2 && !(a > b)) ? b : a);
+            }
+        }
+        if (trace) {
+            memset(&trace[c], 0, sizeof(trace[c]));
+            trace[c].min_slack = trace[c].min_short = trace[c].min_short_after_close = 0x7fffffff;
+            trace[c].frame_bits = L->frame_bits;
+        }
+        l12_trace = trace ? &trace[c] : NULL;
+        l12_encode_frame_tail(L, ltmin, dumps ? &dumps[c] : NULL);
+        l12_trace = NULL;
+        put_bits(L->base, 0, 0);
+        len = L->base->out_bits >> 3;
+        if (len > out_stride) { free(L->base->out); free(L->base); free(L); return -1; }
+        memcpy(out + (size_t) c * out_stride, L->base->out, len);
+        out_len[c] = (uint32_t) len;
+        free(L->base->out);
+        free(L->base);
+        free(L);
+    }
+    return 0;
 }
