@@ -74,6 +74,40 @@ int mp3mi_l12_batch_encode_next(mp3mi_l12_batch *b, const int16_t *pcm_dev, int 
 int mp3mi_l12_batch_flush(mp3mi_l12_batch *b, uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev);
 int mp3mi_l12_batch_reset(mp3mi_l12_batch *b);
 
+/* Continuous batching, as mp3mi_batch_encode_slots / mp3mi_batch_slot_frames of mp3mi.h: every stream index is a SLOT through
+ * which one stream after another passes, each beginning and ending in a call of its own while the other slots go on.  A frame
+ * is 384 (Layer I) or 1152 (Layer II) samples per channel; full = n_frames of them.
+ *   ctl_host       host, [n_streams] uint8: MP3MI_SLOT_START | MP3MI_SLOT_END (mp3mi.h)
+ *     START  the slot begins a new stream at this call's first sample, from silence before it; a stream still open in the slot
+ *            is abandoned
+ *     END    the call holds the stream's last n_samples_host[s] samples per channel, 0 .. full: the last partial frame is
+ *            zero-filled (src/encode.c:162-166), the slot delivers ceil(n / frame) frames and then the file's one byte past
+ *            the last frame (close_bit_stream_w), and is closed afterwards.  START | END is a one-call file; END with 0
+ *            samples (with START or on an open stream) delivers exactly that one byte
+ *     0      an open stream goes on, with a full call of samples; a closed slot stays closed
+ *   n_samples_host host, [n_streams] int32, or NULL: full for every open or starting slot, 0 for the others
+ *   pcm_dev        device, int16 [n_streams][full][channels]; the rows of closed slots are not looked at
+ *   out_dev, out_len_dev  device, [n_streams][out_stride] and [n_streams]: out_len_dev[s] is the bytes of slot s's file the call
+ *                  produced -- 0 for a closed slot, whose row is left alone whatever its PCM row holds
+ * The bytes a slot delivers from a stream's START call through its END call, concatenated, are byte for byte what
+ * mp3mi_l12_batch_encode gives for the same samples as one stream of a ragged whole-file call (bitrate: the slot's, from create).
+ * MP3MI_ERR_ARG, with nothing enqueued and the batch unchanged: ctl bits other than the two; END on a closed slot without
+ * START; a sample count that is not full for a continuing or starting slot, outside 0 .. full for an ending one, not 0 for a
+ * closed one; a NULL pointer other than n_samples_host; n_frames outside 1 .. max_frames; out_stride below
+ * mp3mi_l12_batch_out_stride(b, n_frames).  The two host arrays are copied before the call returns; calls may follow each
+ * other without a sync in between (the work is enqueued on the batch's stream, as ever).
+ *
+ * Alongside the other calls: mp3mi_l12_batch_encode_next starts every slot when none is open, and otherwise continues the open
+ * ones (closed slots stay closed, out_len 0); mp3mi_l12_batch_flush ends every open slot (out_len 0 for the closed ones);
+ * mp3mi_l12_batch_reset and mp3mi_l12_batch_encode close every slot.  A batch that is never given a per-slot call behaves in
+ * every respect as if these two functions did not exist -- mp3mi_l12_batch_flush then delivers the one byte for every stream,
+ * a fresh batch's included. */
+int mp3mi_l12_batch_encode_slots(mp3mi_l12_batch *b, const int16_t *pcm_dev, int n_frames, const uint8_t *ctl_host,
+                                 const int32_t *n_samples_host, uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev);
+/* frames_host[s] = frames encoded so far by the stream open in slot s, -1 if none is; returns the number of open slots.
+ * Host-side bookkeeping only: waits for nothing. */
+int mp3mi_l12_batch_slot_frames(const mp3mi_l12_batch *b, int64_t *frames_host);
+
 /* Two-tier decisions (mp3mi.h, MP3MI_TEST_PHASE_EXACT | _PSY_EXACT | _CW_EXACT): force the exact tier; bytes must not change */
 int mp3mi_l12_batch_set_test_flags(mp3mi_l12_batch *b, unsigned flags);
 

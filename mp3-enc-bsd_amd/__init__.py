@@ -128,6 +128,12 @@ def lib():
         L.mp3mi_l12_batch_out_stride.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.mp3mi_l12_batch_encode.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         L.mp3mi_l12_batch_sync.argtypes = [ctypes.c_void_p]
+        L.mp3mi_l12_batch_encode_next.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        L.mp3mi_l12_batch_flush.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        L.mp3mi_l12_batch_reset.argtypes = [ctypes.c_void_p]
+        L.mp3mi_l12_batch_encode_slots.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        L.mp3mi_l12_batch_slot_frames.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.mp3mi_l12_batch_total_timing.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]
         L.mp3mi_l12_batch_kernel_timing.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.mp3mi_version.restype = ctypes.c_char_p
@@ -428,6 +434,47 @@ class BatchL12:
         assert pcm.is_cuda and out.is_cuda and out_len.is_cuda and pcm.is_contiguous() and out.is_contiguous()
         self._check(self.L.mp3mi_l12_batch_encode(self.h, pcm.data_ptr(), n_samples.data_ptr() if n_samples is not None else None,
                                                   n_frames, out.data_ptr(), out.stride(0), out_len.data_ptr()), "mp3mi_l12_batch_encode")
+
+    def encode_next(self, pcm, n_frames, out, out_len):
+        """Streaming: the NEXT n_frames frames of every stream (pcm holds only these); out / out_len receive their bytes.
+        Concatenate them call after call, then flush()."""
+        assert pcm.is_cuda and out.is_cuda and out_len.is_cuda and pcm.is_contiguous() and out.is_contiguous()
+        self._check(self.L.mp3mi_l12_batch_encode_next(self.h, pcm.data_ptr(), n_frames, out.data_ptr(), out.stride(0), out_len.data_ptr()),
+                    "mp3mi_l12_batch_encode_next")
+
+    def flush(self, out, out_len):
+        """close_bit_stream_w: the file's one byte past the last frame of every open stream; ends the streams."""
+        self._check(self.L.mp3mi_l12_batch_flush(self.h, out.data_ptr(), out.stride(0), out_len.data_ptr()), "mp3mi_l12_batch_flush")
+
+    def reset(self):
+        self._check(self.L.mp3mi_l12_batch_reset(self.h), "mp3mi_l12_batch_reset")
+
+    def encode_slots(self, pcm, n_frames, out, out_len, start=None, end=None, n_samples=None):
+        """Continuous batching (mp3mi_l12_batch_encode_slots): every stream index is a slot in which one stream after another
+        begins (start[s] true: with this call's first sample, from silence) and ends (end[s] true: this call holds its last
+        n_samples[s] samples per channel).  start / end: boolean sequences of n_streams (None: all false); n_samples: an int
+        sequence (None: a full call for every open or starting slot, 0 for the others).  Tensors as for encode_next; out /
+        out_len receive per slot the bytes of its file this call produced (0 for a closed slot)."""
+        import numpy as np
+        assert pcm.is_cuda and out.is_cuda and out_len.is_cuda and pcm.is_contiguous() and out.is_contiguous()
+        S = self.n_streams
+        ctl = np.zeros(S, np.uint8)
+        if start is not None:
+            ctl |= np.asarray(start, dtype=bool).reshape(S).astype(np.uint8) * 1  # MP3MI_SLOT_START
+        if end is not None:
+            ctl |= np.asarray(end, dtype=bool).reshape(S).astype(np.uint8) * 2  # MP3MI_SLOT_END
+        ns = None if n_samples is None else np.ascontiguousarray(n_samples, dtype=np.int32).reshape(S)
+        self._check(self.L.mp3mi_l12_batch_encode_slots(self.h, pcm.data_ptr(), n_frames, ctl.ctypes.data, None if ns is None else ns.ctypes.data,
+                                                        out.data_ptr(), out.stride(0), out_len.data_ptr()), "mp3mi_l12_batch_encode_slots")
+
+    def slot_frames(self):
+        """numpy int64 [n_streams]: frames encoded so far by the stream open in each slot, -1 where none is (no device wait)"""
+        import numpy as np
+        f = np.zeros(self.n_streams, np.int64)
+        rc = self.L.mp3mi_l12_batch_slot_frames(self.h, f.ctypes.data)
+        if rc < 0:
+            raise Mp3miError("mp3mi_l12_batch_slot_frames failed with %d" % rc)
+        return f
 
     def sync(self):
         self._check(self.L.mp3mi_l12_batch_sync(self.h), "mp3mi_l12_batch_sync")

@@ -778,7 +778,7 @@ __global__ void __launch_bounds__(64 * W) k_fft12(const mp3mi_tables *__restrict
         const int qi = task % NP, s = task / NP;
         const size_t rec0 = ((size_t) s * NP + qi) * C;
         const long qr = (long) geo.f0 * geo.layer - geo.lb + qi; // the pass counted from the call's first, and from the stream's
-        const long q = geo.fabs0 * geo.layer + qr;
+        const long q = (geo.fabs_s ? (long) geo.fabs_s[s] : geo.fabs0) * geo.layer + qr; // (per-slot streaming: the slot's own stream)
         const long n_per_ch = geo.n_samples ? (long) geo.n_samples[s] : n_pitch;
         const int16_t *pcm = pcm_all + (size_t) s * (size_t) n_pitch * (size_t) C;
         const long t0 = (long) geo.spp * (qr + 1) - geo.span; // time of savebuf[0], from the call's first sample  (src/psy.c:258-262)

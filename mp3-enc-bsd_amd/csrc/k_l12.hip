@@ -152,6 +152,13 @@ __global__ void __launch_bounds__(64, 3) k12_psy(const mp3mi_tables_l12 *__restr
     const int run = (int) ((bid / (unsigned) C) % (unsigned) n_run);
     const int s = (int) (bid / (unsigned) (C * n_run));
     const int qa = qi0 + run * L12_PSY_RUN - warm, qb = qa + warm + L12_PSY_RUN < NP ? qa + warm + L12_PSY_RUN : NP;
+    // the chunk's pass 0 counted from the stream's first; per-slot streaming: the stream open in this slot has its own frame index
+    // (s is the same for the whole wavefront: one scalar load per run).  Only q < 0 and q >= 1 are asked below, so a stream's
+    // frames count as 2^20 at most and q is an int; the readfirstlane is there to have the load waited for HERE and not at q's
+    // first use inside the pass loop, where the same counter stands for the loop's LDS reads (with a 64-bit q taken straight from
+    // the load the kernel measured 0.3 - 0.6 % slower in an encode_next tick than before it had the load, this way 0.1 - 0.2 %)
+    const long fabs_first = geo.fabs_s ? (long) geo.fabs_s[s] : geo.fabs0;
+    const int q0 = __builtin_amdgcn_readfirstlane(((int) (fabs_first < (1L << 20) ? fabs_first : (1L << 20)) + geo.f0) * geo.layer - geo.lb);
     float h_ro[9], h_po[9], h_roo[9], h_poo[9]; // r, phi of the pass before ("old") and of the one before that ("oldest")
     {
         const float *r_o = erp + (((size_t) s * NP + qa - 1) * C + ch) * (3 * L12_ROW);
@@ -165,7 +172,7 @@ __global__ void __launch_bounds__(64, 3) k12_psy(const mp3mi_tables_l12 *__restr
     }
 #pragma unroll 1
     for (int qi = qa; qi < qb; qi++) {
-    const long q = (geo.fabs0 + geo.f0) * geo.layer - geo.lb + qi; // the pass counted from the stream's first
+    const int q = q0 + qi; // the pass counted from the stream's first (see q0)
     const size_t rec = ((size_t) s * NP + qi) * C + ch;
     const float *r_n = erp + rec * (3 * L12_ROW);               // this pass: energy, r, phi
     const float *r_o = erp + (rec - (size_t) C) * (3 * L12_ROW);     // (the second tier reads the passes before from memory)
@@ -466,8 +473,16 @@ __global__ void __launch_bounds__(64) k12_alloc(const mp3mi_tables_l12 *__restri
     const int fl = (int) (blockIdx.x % (unsigned) geo.nf), s = (int) (blockIdx.x / (unsigned) geo.nf);
     const long n = (long) geo.f0 + fl; // frame index in the stream
     const long n_frames_s = geo.n_samples ? ((long) geo.n_samples[s] + geo.spf - 1) / geo.spf : (long) geo.n_frames;
+    // the stream ends with the call -- the whole-file call, or the slot's END in a per-slot call --: the file's last byte follows
+    const bool ends = geo.slot_ctl ? (geo.slot_ctl[s] & MP3MI_SLOT_DEV_END) != 0 : geo.whole_file != 0;
     if (n >= n_frames_s) {
-        if (n_frames_s == 0 && n == 0 && lane == 0 && geo.whole_file) { out[(size_t) s * out_stride] = 0; out_len[s] = 1; }
+        // a stream without frames in the call: the wavefront of the call's first frame settles its length.  An ending one delivers
+        // the file's last byte alone; in a per-slot call a closed slot delivers nothing, whatever its PCM row holds (every slot of
+        // such a call gets a length: it has n_samples 0 or full but for the ENDs)
+        if (n_frames_s == 0 && n == 0 && lane == 0) {
+            if (ends) { out[(size_t) s * out_stride] = 0; out_len[s] = 1; }
+            else if (geo.slot_ctl) out_len[s] = 0;
+        }
         return;
     }
     const l12_stream_cfg cf = cfg[s];
@@ -895,8 +910,8 @@ __global__ void __launch_bounds__(64) k12_alloc(const mp3mi_tables_l12 *__restri
         uint8_t *o = out + (size_t) s * out_stride + (size_t) n * (size_t) frame_bytes;
         for (int i = lane; i < frame_bytes; i += 64) o[i] = (uint8_t) (L.img[i >> 2] >> (24 - 8 * (i & 3)));
         if (n == n_frames_s - 1 && lane == 0) {
-            if (geo.whole_file) o[frame_bytes] = 0;
-            out_len[s] = (uint32_t) (n_frames_s * frame_bytes + (geo.whole_file ? 1 : 0));
+            if (ends) o[frame_bytes] = 0;
+            out_len[s] = (uint32_t) (n_frames_s * frame_bytes + (ends ? 1 : 0));
         }
     }
 }
@@ -912,6 +927,9 @@ void mp3mi_launch_l12_alloc(const mp3mi_tables_l12 *T, const l12_geom &g, const 
 // ---- streaming: what a stream carries from call to call is PCM history only (l12_dev.h).  The last L12_PCM_HIST samples
 // before the next call's first one -- this call's tail, preceded by the old history's when the call was shorter --
 // for the FFT windows, and the last MP3MI_PCM_HIST of them in k_filter's layout.  Out of place: in and out are two buffers.
+// In a per-slot call it runs for every slot all the same: what it leaves in the row of a closed slot, or of one that ended on a
+// partial call, is stale, and harmless -- nothing computed from a closed slot's history is delivered, and k12_slot_begin zeroes the
+// row at the next START.
 __global__ void __launch_bounds__(256) k12_hist_save(l12_geom geo, const int16_t *__restrict__ pcm, const int16_t *__restrict__ hist_in,
                                                      int16_t *__restrict__ hist_out, const int16_t *__restrict__ fb_in, int16_t *__restrict__ fb_out)
 {
@@ -934,14 +952,40 @@ void mp3mi_launch_l12_hist_save(const l12_geom &g, const int16_t *pcm, const int
     hipLaunchKernelGGL(k12_hist_save, dim3((unsigned) g.n_streams), dim3(256), 0, st, g, pcm, hist_in, hist_out, fb_in, fb_out);
 }
 // close_bit_stream_w: the byte under construction is written too (src/common.c:843-868) -- frames end on byte boundaries, so it is 0
-__global__ void __launch_bounds__(64) k12_flush(int n_streams, uint8_t *__restrict__ out, size_t out_stride, uint32_t *__restrict__ out_len)
+// (per-slot streaming: only the slots with a stream open -- MP3MI_SLOT_DEV_ACTIVE -- have a file to close; the others deliver nothing)
+__global__ void __launch_bounds__(64) k12_flush(int n_streams, const uint8_t *__restrict__ slot_ctl, uint8_t *__restrict__ out, size_t out_stride,
+                                                uint32_t *__restrict__ out_len)
 {
     const int s = (int) (blockIdx.x * 64 + threadIdx.x);
-    if (s < n_streams) { out[(size_t) s * out_stride] = 0; out_len[s] = 1; }
+    if (s >= n_streams) return;
+    const bool open = !slot_ctl || (slot_ctl[s] & MP3MI_SLOT_DEV_ACTIVE);
+    if (open) out[(size_t) s * out_stride] = 0;
+    out_len[s] = open ? 1u : 0u;
 }
-void mp3mi_launch_l12_flush(int n_streams, uint8_t *out, size_t out_stride, uint32_t *out_len, hipStream_t st)
+void mp3mi_launch_l12_flush(int n_streams, const uint8_t *slot_ctl, uint8_t *out, size_t out_stride, uint32_t *out_len, hipStream_t st)
 {
-    hipLaunchKernelGGL(k12_flush, dim3((unsigned) ((n_streams + 63) / 64)), dim3(64), 0, st, n_streams, out, out_stride, out_len);
+    hipLaunchKernelGGL(k12_flush, dim3((unsigned) ((n_streams + 63) / 64)), dim3(64), 0, st, n_streams, slot_ctl, out, out_stride, out_len);
+}
+
+// ---- per-slot streaming (mp3mi_l12_batch_encode_slots): a stream that STARTs in a slot begins from silence -- the reference's
+// zero-filled buffers -- whatever the stream before it left there.  One workgroup per LISTED slot (the host lists the call's START
+// slots: no scan over all slots) zeroes the slot's rows of the two history buffers with 16-byte stores: a row is L12_PCM_HIST or
+// MP3MI_PCM_HIST samples per channel of 2 bytes, 3584 or 2112 bytes per channel -- multiples of 16, like the buffers' bases.
+static_assert((L12_PCM_HIST * sizeof(int16_t)) % 16 == 0 && (MP3MI_PCM_HIST * sizeof(int16_t)) % 16 == 0, "k12_slot_begin stores 16 bytes at a time");
+__global__ void __launch_bounds__(256) k12_slot_begin(const int32_t *__restrict__ list, int channels, int16_t *__restrict__ hist,
+                                                      int16_t *__restrict__ fb_hist)
+{
+    const size_t s = (size_t) list[blockIdx.x];
+    const uint4 zero = {0u, 0u, 0u, 0u};
+    const int n_h = (int) (L12_PCM_HIST * sizeof(int16_t) / 16) * channels, n_f = (int) (MP3MI_PCM_HIST * sizeof(int16_t) / 16) * channels;
+    uint4 *h = (uint4 *) (hist + s * L12_PCM_HIST * (size_t) channels), *f = (uint4 *) (fb_hist + s * MP3MI_PCM_HIST * (size_t) channels);
+    for (int i = (int) threadIdx.x; i < n_h; i += 256) h[i] = zero;
+    for (int i = (int) threadIdx.x; i < n_f; i += 256) f[i] = zero;
+}
+void mp3mi_launch_l12_slot_begin(const int32_t *list, int n_list, int channels, int16_t *hist, int16_t *fb_hist, hipStream_t st)
+{
+    if (n_list <= 0) return;
+    hipLaunchKernelGGL(k12_slot_begin, dim3((unsigned) n_list), dim3(256), 0, st, list, channels, hist, fb_hist);
 }
 
 ULP_CENSUS_ACCESSOR(mp3mi_debug_ulp_census_l12)

@@ -4,7 +4,8 @@
 //   k_fft12 -> k12_psy ;  k_filter ;  k12_alloc
 //
 // Frames are independent but for PCM history (l12_dev.h), so a chunk is just these four launches in stream order, and
-// chunks follow each other on the batch's one HIP stream.  No CPU fallback.
+// chunks follow each other on the batch's one HIP stream.  A per-slot call (mp3mi_l12_batch_encode_slots) puts its control block's
+// upload and k12_slot_begin ahead of them on the same stream.  No CPU fallback.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -46,6 +47,40 @@ struct mp3mi_l12_batch {
     int16_t *hist[2], *fb_hist[2];
     int hist_cur;
     long fabs0;              // frames every stream has been given by mp3mi_l12_batch_encode_next since the last reset
+    // per-slot streaming (mp3mi_l12_batch_encode_slots): a stream index is a SLOT through which one stream after another passes.
+    // While slots_on is false the slots are as fabs0 says (all open at fabs0 when it is > 0, else all closed) and every call runs
+    // as it always did; the first per-slot call sets slots_on, and the slots are as slot_frames_h says (l12_slots_settle hands back).
+    bool slots_on;
+    std::vector<int64_t> slot_frames_h; // frames encoded by the stream open in each slot, -1: no stream open there
+    // the control block of a per-slot call (l12_ctl_block), twice, taken in turn: calls are issued back to back, and an entry's
+    // fence is recorded behind the last kernel that reads its device copy -- the host waits for it before it writes the staging
+    // again (the per-slot call two before).  Created with the first per-slot call: a batch that never makes one holds none of it.
+    typedef upload_ring<uint8_t, 2> ctl_ring;
+    ctl_ring ctl;
+};
+
+// The control block of a per-slot call, one array per slot after the other: what the kernels read of it (l12_geom) and the list of
+// the slots the call STARTs (k12_slot_begin)
+struct l12_ctl_block {
+    int64_t *fabs;      // index of the call's first frame in the slot's stream
+    int32_t *n_samples; // valid samples per channel
+    int32_t *list;      // the START slots, n_start of them
+    uint8_t *ctl;       // MP3MI_SLOT_DEV_*
+};
+static size_t l12_ctl_bytes(int S) { return (size_t) S * (sizeof(int64_t) + 2 * sizeof(int32_t) + 1); }
+static l12_ctl_block l12_ctl_at(uint8_t *p, int S)
+{
+    l12_ctl_block c;
+    c.fabs = (int64_t *) p;
+    c.n_samples = (int32_t *) (c.fabs + S);
+    c.list = c.n_samples + S;
+    c.ctl = (uint8_t *) (c.list + S);
+    return c;
+}
+struct l12_slot_call { // a per-slot call: its control block on the device, and the ring entry it took
+    l12_ctl_block dev;
+    int n_start;
+    mp3mi_l12_batch::ctl_ring::entry *blk;
 };
 
 static size_t l12_per_frame_bytes(int layer, int channels, int spf)
@@ -82,6 +117,9 @@ extern "C" int mp3mi_l12_batch_create(mp3mi_l12_batch **out, int layer, int n_st
     b->ev0 = b->ev1 = 0; b->T3 = NULL; b->T = NULL; b->cfg = NULL;
     b->erp = b->snr = NULL; b->sbs = NULL; b->dbg = NULL; b->dbg_f0 = b->dbg_nf = 0;
     b->hist[0] = b->hist[1] = b->fb_hist[0] = b->fb_hist[1] = NULL; b->hist_cur = 0; b->fabs0 = 0;
+    b->slots_on = false;
+    b->slot_frames_h.assign((size_t) n_streams, -1);
+    memset((void *) &b->ctl, 0, sizeof(b->ctl));
     if (hipGetDevice(&b->device) != hipSuccess) { delete b; return MP3MI_ERR_HIP; }
     b->cfg_h.resize((size_t) n_streams);
     b->max_frame_bytes = 0;
@@ -158,6 +196,11 @@ extern "C" void mp3mi_l12_batch_destroy(mp3mi_l12_batch *b)
         (void) hipFree(b->T3); (void) hipFree(b->T); (void) hipFree(b->cfg); (void) hipFree(b->erp);
         (void) hipFree(b->snr); (void) hipFree(b->sbs); (void) hipFree(b->dbg);
         for (int i = 0; i < 2; i++) { (void) hipFree(b->hist[i]); (void) hipFree(b->fb_hist[i]); }
+        for (mp3mi_l12_batch::ctl_ring::entry &en : b->ctl.e) {
+            if (en.stage) (void) hipHostFree(en.stage);
+            (void) hipFree(en.dev);
+            en.free.destroy();
+        }
         if (b->ev0) (void) hipEventDestroy(b->ev0);
         if (b->ev1) (void) hipEventDestroy(b->ev1);
         for (hipEvent_t e : b->kev) (void) hipEventDestroy(e);
@@ -219,8 +262,62 @@ static int l12_close_timing(mp3mi_l12_batch *b)
     return MP3MI_OK;
 }
 
+// The PCM history of a streaming batch: allocated and zeroed with the first streaming call
+static int l12_hist_ensure(mp3mi_l12_batch *b)
+{
+    const size_t S = (size_t) b->n_streams, C = (size_t) b->channels;
+    for (int i = 0; i < 2; i++) {
+        if (b->hist[i] && b->fb_hist[i]) continue;
+        if (!b->hist[i]) CHK(hipMalloc((void **) &b->hist[i], sizeof(int16_t) * L12_PCM_HIST * C * S));
+        if (!b->fb_hist[i]) CHK(hipMalloc((void **) &b->fb_hist[i], sizeof(int16_t) * MP3MI_PCM_HIST * C * S));
+        CHK(hipMemsetAsync(b->hist[i], 0, sizeof(int16_t) * L12_PCM_HIST * C * S, b->stream));
+        CHK(hipMemsetAsync(b->fb_hist[i], 0, sizeof(int16_t) * MP3MI_PCM_HIST * C * S, b->stream));
+    }
+    return MP3MI_OK;
+}
+
+// ---- per-slot streaming: the bookkeeping (mp3mi_l12_batch::slots_on) ----
+// What every slot holds before a call: the frames of the stream open in it, -1 for none
+static void l12_slot_frames_now(const mp3mi_l12_batch *b, int64_t *f)
+{
+    for (int s = 0; s < b->n_streams; s++) f[s] = b->slots_on ? b->slot_frames_h[s] : (b->fabs0 > 0 ? (int64_t) b->fabs0 : -1);
+}
+// The per-slot bookkeeping is in force, with the slots as f says -- unless every slot is open at the same frame: then it hands over
+// to the whole-batch counter, and the next call runs exactly as if there had never been a per-slot call
+static void l12_slots_settle(mp3mi_l12_batch *b, const std::vector<int64_t> &f)
+{
+    b->slot_frames_h = f;
+    b->slots_on = true;
+    for (int s = 1; s < b->n_streams; s++)
+        if (f[(size_t) s] != f[0]) return;
+    if (f[0] > 0) {
+        b->slots_on = false;
+        b->fabs0 = (long) f[0];
+    }
+}
+// flush, reset and the whole-file call close every slot: the whole-batch counter again, at the start of new streams
+static void l12_slots_close(mp3mi_l12_batch *b)
+{
+    b->slots_on = false;
+    b->fabs0 = 0;
+}
+// The control block this call takes, its entry created with its first turn; the host waits for the per-slot call two before,
+// whose kernels read the device copy and whose upload read the staging it is about to write
+static int l12_ctl_take(mp3mi_l12_batch *b, mp3mi_l12_batch::ctl_ring::entry **blk)
+{
+    mp3mi_l12_batch::ctl_ring::entry &en = b->ctl.take();
+    const size_t bytes = l12_ctl_bytes(b->n_streams);
+    if (!en.stage) CHK(hipHostMalloc((void **) &en.stage, bytes, 0));
+    if (!en.dev) CHK(hipMalloc((void **) &en.dev, bytes));
+    if (!en.free.ev) CHK(en.free.create());
+    CHK(en.free.sync());
+    *blk = &en;
+    return MP3MI_OK;
+}
+
+// sc: the call is a per-slot one (l12_slots_impl), its control block written to the staging of sc->blk
 static int l12_encode_impl(mp3mi_l12_batch *b, const int16_t *pcm_dev, const int32_t *n_samples_dev, int n_frames,
-                           uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev, bool whole_file)
+                           uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev, bool whole_file, const l12_slot_call *sc = NULL)
 {
     if (!b || !pcm_dev || !out_dev || !out_len_dev || n_frames < 1 || n_frames > b->max_frames) return MP3MI_ERR_ARG;
     if (out_stride < mp3mi_l12_batch_out_stride(b, n_frames)) return MP3MI_ERR_ARG;
@@ -233,6 +330,12 @@ static int l12_encode_impl(mp3mi_l12_batch *b, const int16_t *pcm_dev, const int
     // equal chunks (as batch.cpp cuts a Layer III call): a short remainder -- 191 + 191 + 1 frames of the 383-frame bench call --
     // costs four full launches over all streams and recomputes the warm-up passes for one frame
     const int nchunks = (n_frames + b->chunk_frames - 1) / b->chunk_frames, cfr = (n_frames + nchunks - 1) / nchunks;
+    if (sc) {
+        // the control block goes up on the batch's one stream, ahead of its readers; the slots that START begin from silence
+        { const int rc = l12_hist_ensure(b); if (rc != MP3MI_OK) return rc; }
+        CHK(hipMemcpyAsync(sc->blk->dev, sc->blk->stage, l12_ctl_bytes(S), hipMemcpyHostToDevice, b->stream));
+        mp3mi_launch_l12_slot_begin(sc->dev.list, sc->n_start, C, b->hist[b->hist_cur], b->fb_hist[b->hist_cur], b->stream);
+    }
     int chunk = 0;
     for (int f0 = 0; f0 < n_frames; f0 += cfr, chunk++) {
         hipEvent_t *ke = &b->kev[(size_t) chunk * 5];
@@ -244,10 +347,15 @@ static int l12_encode_impl(mp3mi_l12_batch *b, const int16_t *pcm_dev, const int
         g.lb = b->lb; g.np = nf * layer + b->lb;
         g.spf = b->spf; g.spp = b->spp; g.span = b->span;
         g.actual_mode = b->mode; g.crc = b->crc; g.hdr_flags = b->hdr_flags; g.test_flags = (int) b->test_flags;
-        g.n_samples = n_samples_dev;
+        g.n_samples = sc ? sc->dev.n_samples : n_samples_dev;
         g.whole_file = whole_file ? 1 : 0;
-        g.fabs0 = whole_file ? 0 : b->fabs0;
+        g.fabs0 = (whole_file || sc) ? 0 : b->fabs0;
         g.hist = (!whole_file && b->fabs0 > 0) ? b->hist[b->hist_cur] : NULL; // (nothing precedes a stream's first call: zeros)
+        if (sc) { // every slot has its own position, and always a history: k12_slot_begin has zeroed the rows of the streams that begin
+            g.fabs_s = sc->dev.fabs;
+            g.slot_ctl = sc->dev.ctl;
+            g.hist = b->hist[b->hist_cur];
+        }
         // the filterbank slots of the chunk: frame f's slot u is slot (spf / 32) f + u of the stream, Layer I's two slots
         // EARLIER (get_audio holds 64 samples back, src/encode.c:224-247); k_filter computes whole 18-slot granules
         const long slots = b->spf / 32, first = slots * f0 - (layer == 1 ? 2 : 0), last = slots * (f0 + nf) - 1 - (layer == 1 ? 2 : 0);
@@ -258,8 +366,9 @@ static int l12_encode_impl(mp3mi_l12_batch *b, const int16_t *pcm_dev, const int
         mp3mi_geom fg = mp3mi_make_geom(S, C, b->rate_idx, n_frames, f0, nf);
         fg.g0 = g.g0; fg.n_gran = g.n_gran;
         fg.pcm_pitch = (long) n_frames * b->spf;
-        fg.n_samples = n_samples_dev;
+        fg.n_samples = g.n_samples;
         fg.fabs0 = g.fabs0;
+        fg.fabs_s = g.fabs_s;
         fg.hist = g.hist ? b->fb_hist[b->hist_cur] : NULL;
         CHK(hipEventRecord(ke[0], b->stream));
         mp3mi_launch_fft12(b->T3, g, pcm_dev, b->erp, b->stream);
@@ -276,22 +385,16 @@ static int l12_encode_impl(mp3mi_l12_batch *b, const int16_t *pcm_dev, const int
         l12_geom g;
         memset(&g, 0, sizeof(g));
         g.n_streams = S; g.channels = C; g.n_frames = n_frames; g.spf = b->spf;
-        for (int i = 0; i < 2; i++) {
-            if (!b->hist[i]) {
-                CHK(hipMalloc((void **) &b->hist[i], sizeof(int16_t) * L12_PCM_HIST * (size_t) C * (size_t) S));
-                CHK(hipMalloc((void **) &b->fb_hist[i], sizeof(int16_t) * MP3MI_PCM_HIST * (size_t) C * (size_t) S));
-                CHK(hipMemsetAsync(b->hist[i], 0, sizeof(int16_t) * L12_PCM_HIST * (size_t) C * (size_t) S, b->stream));
-                CHK(hipMemsetAsync(b->fb_hist[i], 0, sizeof(int16_t) * MP3MI_PCM_HIST * (size_t) C * (size_t) S, b->stream));
-            }
-        }
-        if (b->fabs0 == 0) { // a stream's first call: what precedes it is silence (the reference's zero-filled buffers)
+        { const int rc = l12_hist_ensure(b); if (rc != MP3MI_OK) return rc; }
+        if (!sc && b->fabs0 == 0) { // a stream's first call: what precedes it is silence (the reference's zero-filled buffers)
             CHK(hipMemsetAsync(b->hist[b->hist_cur], 0, sizeof(int16_t) * L12_PCM_HIST * (size_t) C * (size_t) S, b->stream));
             CHK(hipMemsetAsync(b->fb_hist[b->hist_cur], 0, sizeof(int16_t) * MP3MI_PCM_HIST * (size_t) C * (size_t) S, b->stream));
         }
         mp3mi_launch_l12_hist_save(g, pcm_dev, b->hist[b->hist_cur], b->hist[b->hist_cur ^ 1], b->fb_hist[b->hist_cur], b->fb_hist[b->hist_cur ^ 1], b->stream);
         b->hist_cur ^= 1;
-        b->fabs0 += n_frames;
-    } else b->fabs0 = 0;
+        if (sc) CHK(sc->blk->free.record(b->stream)); // behind the last reader of the control block
+        else b->fabs0 += n_frames;                    // (a per-slot call: l12_slots_impl keeps the slots' frames)
+    } else l12_slots_close(b);
     CHK(hipEventRecord(b->ev1, b->stream));
     b->kev_chunks = chunk;
     b->timing_open = true;
@@ -306,9 +409,92 @@ extern "C" int mp3mi_l12_batch_encode(mp3mi_l12_batch *b, const int16_t *pcm_dev
     return l12_encode_impl(b, pcm_dev, n_samples_dev, n_frames, out_dev, out_stride, out_len_dev, true);
 }
 
+// ---- per-slot streaming (mp3mi_l12_batch_encode_slots) ----
+// The rules of a per-slot call, slot by slot (f: l12_slot_frames_now)
+static bool l12_slots_rules_ok(const mp3mi_l12_batch *b, const int64_t *f, int n_frames, const uint8_t *ctl_host, const int32_t *n_samples_host)
+{
+    const int32_t full = (int32_t) n_frames * b->spf;
+    for (int s = 0; s < b->n_streams; s++) {
+        const int c = ctl_host[s];
+        if (c & ~(MP3MI_SLOT_START | MP3MI_SLOT_END)) return false;
+        const bool open = f[s] >= 0, start = c & MP3MI_SLOT_START, end = c & MP3MI_SLOT_END, part = open || start;
+        if (end && !part) return false;
+        const int32_t n = n_samples_host ? n_samples_host[s] : (part ? full : 0);
+        if (!part ? n != 0 : (!end ? n != full : (n < 0 || n > full))) return false;
+    }
+    return true;
+}
+
+static int l12_slots_impl(mp3mi_l12_batch *b, const int16_t *pcm_dev, int n_frames, const uint8_t *ctl_host, const int32_t *n_samples_host,
+                          uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev)
+{
+    if (!b || !pcm_dev || !ctl_host || !out_dev || !out_len_dev || n_frames < 1 || n_frames > b->max_frames) return MP3MI_ERR_ARG;
+    if (out_stride < mp3mi_l12_batch_out_stride(b, n_frames)) return MP3MI_ERR_ARG;
+    const int S = b->n_streams;
+    const int32_t full = (int32_t) n_frames * b->spf;
+    std::vector<int64_t> f((size_t) S);
+    l12_slot_frames_now(b, f.data());
+    // every rule first: a call that breaks one leaves the batch as it was
+    if (!l12_slots_rules_ok(b, f.data(), n_frames, ctl_host, n_samples_host)) return MP3MI_ERR_ARG;
+    ON_DEVICE(b);
+    l12_slot_call sc;
+    if (l12_ctl_take(b, &sc.blk) != MP3MI_OK) return MP3MI_ERR_HIP;
+    const l12_ctl_block st = l12_ctl_at(sc.blk->stage, S); // the staging copy: the caller's two arrays are copied here
+    sc.dev = l12_ctl_at(sc.blk->dev, S);
+    sc.n_start = 0;
+    for (int s = 0; s < S; s++) {
+        const int c = ctl_host[s];
+        const bool open = f[(size_t) s] >= 0, start = c & MP3MI_SLOT_START, part = open || start;
+        st.fabs[s] = (start || !open) ? 0 : f[(size_t) s];
+        st.n_samples[s] = n_samples_host ? n_samples_host[s] : (part ? full : 0);
+        st.ctl[s] = (uint8_t) ((start ? MP3MI_SLOT_DEV_START : 0) | (c & MP3MI_SLOT_END ? MP3MI_SLOT_DEV_END : 0) | (part ? MP3MI_SLOT_DEV_ACTIVE : 0));
+        st.list[s] = 0;
+        if (start) st.list[sc.n_start++] = s;
+    }
+    const int rc = l12_encode_impl(b, pcm_dev, NULL, n_frames, out_dev, out_stride, out_len_dev, false, &sc);
+    if (rc != MP3MI_OK) return rc;
+    b->ctl.next();
+    for (int s = 0; s < S; s++) {
+        const int c = ctl_host[s];
+        if (c & MP3MI_SLOT_START) f[(size_t) s] = 0;
+        if (c & MP3MI_SLOT_END) f[(size_t) s] = -1;
+        else if (f[(size_t) s] >= 0) f[(size_t) s] += n_frames;
+    }
+    l12_slots_settle(b, f);
+    return MP3MI_OK;
+}
+
+extern "C" int mp3mi_l12_batch_encode_slots(mp3mi_l12_batch *b, const int16_t *pcm_dev, int n_frames, const uint8_t *ctl_host,
+                                            const int32_t *n_samples_host, uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev)
+{
+    return l12_slots_impl(b, pcm_dev, n_frames, ctl_host, n_samples_host, out_dev, out_stride, out_len_dev);
+}
+
+extern "C" int mp3mi_l12_batch_slot_frames(const mp3mi_l12_batch *b, int64_t *frames_host)
+{
+    if (!b || !frames_host) return MP3MI_ERR_ARG;
+    l12_slot_frames_now(b, frames_host);
+    int n = 0;
+    for (int s = 0; s < b->n_streams; s++) n += frames_host[s] >= 0;
+    return n;
+}
+
 extern "C" int mp3mi_l12_batch_encode_next(mp3mi_l12_batch *b, const int16_t *pcm_dev, int n_frames, uint8_t *out_dev, size_t out_stride,
                                            uint32_t *out_len_dev)
 {
+    if (b && b->slots_on) {
+        // per-slot bookkeeping in force: with no stream open every slot starts (the whole-batch start); otherwise the open streams
+        // go on and the other slots stay closed
+        bool any = false;
+        for (int s = 0; s < b->n_streams && !any; s++) any = b->slot_frames_h[(size_t) s] >= 0;
+        if (any) {
+            std::vector<uint8_t> ctl((size_t) b->n_streams, 0);
+            return l12_slots_impl(b, pcm_dev, n_frames, ctl.data(), NULL, out_dev, out_stride, out_len_dev);
+        }
+        if (!pcm_dev || !out_dev || !out_len_dev || n_frames < 1 || n_frames > b->max_frames || out_stride < mp3mi_l12_batch_out_stride(b, n_frames))
+            return MP3MI_ERR_ARG; // (before the bookkeeping changes)
+        l12_slots_close(b);
+    }
     return l12_encode_impl(b, pcm_dev, NULL, n_frames, out_dev, out_stride, out_len_dev, false);
 }
 
@@ -316,8 +502,22 @@ extern "C" int mp3mi_l12_batch_flush(mp3mi_l12_batch *b, uint8_t *out_dev, size_
 {
     if (!b || !out_dev || !out_len_dev || out_stride < 1) return MP3MI_ERR_ARG;
     ON_DEVICE(b);
-    mp3mi_launch_l12_flush(b->n_streams, out_dev, out_stride, out_len_dev, b->stream);
-    b->fabs0 = 0;
+    const uint8_t *slot_ctl = NULL;
+    mp3mi_l12_batch::ctl_ring::entry *blk = NULL;
+    if (b->slots_on) { // some slots open, not all at the same frame (l12_slots_settle), or none: the open ones end, the others deliver nothing
+        const int S = b->n_streams;
+        if (l12_ctl_take(b, &blk) != MP3MI_OK) return MP3MI_ERR_HIP;
+        const l12_ctl_block st = l12_ctl_at(blk->stage, S), dev = l12_ctl_at(blk->dev, S);
+        for (int s = 0; s < S; s++) st.ctl[s] = b->slot_frames_h[(size_t) s] >= 0 ? MP3MI_SLOT_DEV_ACTIVE : 0;
+        CHK(hipMemcpyAsync(dev.ctl, st.ctl, (size_t) S, hipMemcpyHostToDevice, b->stream)); // (k12_flush reads nothing else of the block)
+        slot_ctl = dev.ctl;
+    }
+    mp3mi_launch_l12_flush(b->n_streams, slot_ctl, out_dev, out_stride, out_len_dev, b->stream);
+    if (blk) {
+        CHK(blk->free.record(b->stream));
+        b->ctl.next();
+    }
+    l12_slots_close(b);
     CHK(hipGetLastError());
     return MP3MI_OK;
 }
@@ -325,7 +525,7 @@ extern "C" int mp3mi_l12_batch_flush(mp3mi_l12_batch *b, uint8_t *out_dev, size_
 extern "C" int mp3mi_l12_batch_reset(mp3mi_l12_batch *b)
 {
     if (!b) return MP3MI_ERR_ARG;
-    b->fabs0 = 0;
+    l12_slots_close(b);
     return MP3MI_OK;
 }
 

@@ -67,6 +67,11 @@ struct l12_geom {
     const int16_t *hist;     /* device, [n_streams][L12_PCM_HIST][channels]: the samples before the call's first (zeros at the
                                 start of a stream), or NULL */
     int whole_file;          /* the call is the whole stream: the last frame's wavefront adds the file's last byte */
+    /* per-slot streaming (mp3mi_l12_batch_encode_slots): streams of one batch begin and end in different calls.  Both NULL in
+       every other call; in a per-slot call fabs0 is 0, n_samples and hist are always given */
+    const int64_t *fabs_s;   /* device, [n_streams]: index of the call's first frame in the stream open in each slot (0: the
+                                stream begins with the call, or the slot is closed) */
+    const uint8_t *slot_ctl; /* device, [n_streams]: MP3MI_SLOT_DEV_* of the call (mp3mi_host.h) */
 };
 
 /* per stream, device: what depends on the stream's bitrate */
@@ -89,7 +94,12 @@ void mp3mi_launch_l12_alloc(const mp3mi_tables_l12 *T, const l12_geom &g, const 
                             const float *snr, uint8_t *out, size_t out_stride, uint32_t *out_len, l12_frame_dbg *dbg, hipStream_t st);
 void mp3mi_launch_l12_hist_save(const l12_geom &g, const int16_t *pcm, const int16_t *hist_in, int16_t *hist_out, const int16_t *fb_in,
                                 int16_t *fb_out, hipStream_t st);
-void mp3mi_launch_l12_flush(int n_streams, uint8_t *out, size_t out_stride, uint32_t *out_len, hipStream_t st);
+/* slot_ctl: device, [n_streams] MP3MI_SLOT_DEV_* -- only the slots with MP3MI_SLOT_DEV_ACTIVE get the byte, the others length 0 --
+   or NULL: every stream */
+void mp3mi_launch_l12_flush(int n_streams, const uint8_t *slot_ctl, uint8_t *out, size_t out_stride, uint32_t *out_len, hipStream_t st);
+/* k12_slot_begin: the n_list slots of `list` (a call's MP3MI_SLOT_START slots) begin from silence: their rows of hist
+   ([n_streams][L12_PCM_HIST][channels]) and fb_hist ([n_streams][MP3MI_PCM_HIST][channels]) are zeroed */
+void mp3mi_launch_l12_slot_begin(const int32_t *list, int n_list, int channels, int16_t *hist, int16_t *fb_hist, hipStream_t st);
 extern "C" int mp3mi_build_tables_l12(mp3mi_tables_l12 *T, int rate_idx, int layer);
 #endif
 

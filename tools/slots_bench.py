@@ -27,7 +27,12 @@ streams - N of them are live in every tick:
   (p) slots_park          import N, export N, encode_slots per tick, issued back to back like the others
 The line then carries park_vs_continue and the bytes of a state record.
 
-usage: slots_bench.py [--calls 20] [--frames 32] [--streams 4096] [--reps 3] [--mixed-kbps] [--park N] [--host [--occupancy 1.0] [--map]]"""
+--layer 1|2: cases (a), (b), (c) on the Layer I / II batch (mp3mi_l12_batch_encode_next, mp3mi_l12_batch_encode_slots): Layer I at
+192 kbps in ticks of 12 frames, Layer II at 128 kbps in ticks of 4 (--frames sets another length); in (b) one slot STARTs a tick
+after the others, or the batch would hand every tick back to the whole-batch path (profiles/l12_slots_bench.jsonl).
+
+usage: slots_bench.py [--calls 20] [--frames 32] [--streams 4096] [--reps 3] [--mixed-kbps] [--park N] [--host [--occupancy 1.0] [--map]]
+       slots_bench.py --layer 1|2 [--calls 20] [--frames N] [--streams 4096] [--reps 3]"""
 import argparse
 import importlib
 import json
@@ -51,7 +56,12 @@ def main():
     ap.add_argument("--host", action="store_true", help="the per-slot cases on page-locked host buffers")
     ap.add_argument("--occupancy", type=float, default=1.0, help="--host: fraction of the slots that are live")
     ap.add_argument("--map", action="store_true", help="--host: a row map at occupancy 1.0 too (k_rows_in / k_rows_out run)")
+    ap.add_argument("--layer", type=int, default=3, choices=(1, 2, 3), help="1 | 2: the Layer I / II batch (mp3mi_l12_batch_encode_slots)")
     a = ap.parse_args()
+    if a.layer != 3:
+        if a.host or a.mixed_kbps or a.park:
+            ap.error("--layer 1|2 times the three resident cases only")
+        return l12_main(a)
     if a.host:
         if a.mixed_kbps or a.park:
             ap.error("--mixed-kbps and --park time the resident cases (without --host)")
@@ -143,6 +153,73 @@ def main():
                       "churn_vs_continue": round(res["slots_churn"] / res["slots_continue"], 4),
                       **({"park": N, "park_vs_continue": round(res["slots_park"] / res["slots_continue"], 4),
                           "state_bytes": b_state_bytes} if N else {}),
+                      "source_hash": mp3.lib().mp3mi_source_hash().decode()}))
+
+
+def l12_main(a):
+    """--layer 1|2: cases (a), (b), (c) on the Layer I / II batch; calls of --frames frames (default: 12 Layer I, 4 Layer II --
+    about 0.1 s of audio a tick), Layer I at 192 kbps, Layer II at 128"""
+    import torch
+    mp3 = importlib.import_module("mp3-enc-bsd_amd")
+    S, rate, ch, kbps = a.streams, 44100, 2, 192 if a.layer == 1 else 128
+    nf = a.frames if a.frames != 32 else (12 if a.layer == 1 else 4)
+    full = nf * mp3.L12_FRAME_SAMPLES[a.layer]
+    dev = torch.device("cuda:0")
+    pcm = torch.empty((S, full * ch), dtype=torch.int16, device=dev)
+    torch.cuda.synchronize()
+    mp3.synth_pcm_device(pcm, full, ch, rate)
+    b = mp3.BatchL12(a.layer, S, rate, ch, kbps, nf)
+    out = torch.zeros((S, b.out_stride(nf)), dtype=torch.uint8, device=dev)
+    out_len = torch.zeros(S, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    rng = np.random.default_rng(1)
+    every = np.ones(S, bool)
+
+    def run_next():
+        for _ in range(a.calls):
+            b.encode_next(pcm, nf, out, out_len)
+
+    def run_continue():
+        # (one slot STARTs a call later than the others: with every slot at the same frame the batch would hand the calls
+        # back to the whole-batch path, which is case (a))
+        first = every.copy()
+        first[S - 1] = False
+        b.encode_slots(pcm, nf, out, out_len, start=first)
+        b.encode_slots(pcm, nf, out, out_len, start=~first)
+        for _ in range(a.calls - 2):
+            b.encode_slots(pcm, nf, out, out_len)
+
+    def run_churn():
+        b.encode_slots(pcm, nf, out, out_len, start=every)
+        closed = np.zeros(S, bool)
+        for _ in range(a.calls - 1):
+            start = closed.copy()
+            end = np.zeros(S, bool)
+            end[rng.choice(np.flatnonzero(~closed), S // 32, replace=False)] = True
+            ns = np.full(S, full, np.int32)
+            ns[end] = rng.integers(0, full + 1, int(end.sum()))
+            b.encode_slots(pcm, nf, out, out_len, start=start, end=end, n_samples=ns)
+            closed = end
+
+    res = {}
+    for name, fn in (("encode_next", run_next), ("slots_continue", run_continue), ("slots_churn", run_churn)):
+        best = None
+        for r in range(a.reps + 1):  # the first run warms up
+            b.reset()
+            b.sync()
+            t0 = time.perf_counter()
+            fn()
+            b.flush(out, out_len)
+            b.sync()
+            ms = (time.perf_counter() - t0) * 1e3 / a.calls
+            if r > 0:
+                best = ms if best is None else min(best, ms)
+        res[name] = round(best, 3)
+    b.close()
+    print(json.dumps({"tool": "slots_bench --layer", "layer": a.layer, "streams": S, "frames_per_call": nf, "calls": a.calls, "rate": rate,
+                      "channels": ch, "kbps": kbps, "ms_per_call": res,
+                      "continue_vs_next": round(res["slots_continue"] / res["encode_next"], 4),
+                      "churn_vs_continue": round(res["slots_churn"] / res["slots_continue"], 4),
                       "source_hash": mp3.lib().mp3mi_source_hash().decode()}))
 
 
