@@ -372,6 +372,7 @@ static int batch_build(mp3mi_batch *b, int n_streams, int rate_hz, int channels,
     if (cf < 1) cf = 1;
     if (cf > max_frames) cf = max_frames;
     if (opt.chunk_frames > 0 && opt.chunk_frames < cf) cf = opt.chunk_frames;
+    if ((size_t) n_streams * 2 * (size_t) cf * (size_t) channels > MP3MI_CW_MAX_REC) return MP3MI_ERR_ARG; // (k_cw's 32-bit item index; such a chunk's buffers would be a terabyte)
     b->chunk_frames = (int) cf;
 
     std::vector<char> Th_store(sizeof(mp3mi_tables)); // host copy of the tables, released on every path

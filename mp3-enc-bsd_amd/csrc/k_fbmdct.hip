@@ -131,17 +131,49 @@ __global__ void __launch_bounds__(64, 3) k_filter(const mp3mi_tables *__restrict
     // where the slots of this wavefront go: lane >> 4 picks the slot of a group of four, the walk below adds four
     const int sg = FILT_SLOTS * blk + (lane >> 4);
     const int gi = sg / 18, q = sg - 18 * gi;
+    // s[sub] = y[16] + sum_j filt[j] (y[j] + y[32-j]) + sum_j filt[16+j] (y[33+j] - y[63-j])   (src/encode.c:398-408),
+    // four subbands at a time: filt[i][j] is cos((2i+1) n pi/64) rounded to 1e-9, n = 16-j (j < 16) or j+1, and rows
+    // g, 15-g, 16+g and 31-g repeat each other up to sign -- bit for bit: every table build checks it and refuses a
+    // table where they do not (mp3mi_filt_mirror_check, tables_host.cpp):
+    //   filt[31-g][j] == (-1)^n filt[g][j],  filt[16+g][j] == (-1)^n filt[15-g][j],  n even: filt[15-g][j] == (-1)^(n/2) filt[g][j].
+    // A product by the negated coefficient is the negated product and a + (-p) == a - p, so pa = filt[g][j] u[1+j] (and,
+    // for odd n, pb = filt[15-g][j] u[1+j]) serves all four sums: 47 multiplies instead of 124, and every sum still
+    // takes its 31 terms in j order.  The signs depend on j alone: constants of the unrolled loop.  Subbands g and 15-g
+    // go to the tile of the lower half at once, 16+g and 31-g wait in registers for the upper half's turn (the g loop is
+    // unrolled so that they are registers: 36 KB of code instead of 24; a rolled loop over pairs was no faster than
+    // the plain one, EXPERIMENTS.md, round 10).
+    double hold[16];
+#pragma unroll
+    for (int g = 0; g < 8; g++) {
+        const double *fa = T->filt[g], *fb = T->filt[15 - g];
+        double s0 = u[0], s1 = u[0], s2 = u[0], s3 = u[0]; // subbands g, 15-g, 16+g, 31-g
+#pragma unroll
+        for (int j = 0; j < 31; j++) {
+            const int n = j < 16 ? 16 - j : j + 1;
+            const double pa = fa[j] * u[1 + j];
+            s0 = s0 + pa;
+            if (n & 1) {
+                const double pb = fb[j] * u[1 + j];
+                s1 = s1 + pb;
+                s2 = s2 - pb;
+                s3 = s3 - pa;
+            } else {
+                if (n & 2) { s1 = s1 - pa; s2 = s2 - pa; }
+                else { s1 = s1 + pa; s2 = s2 + pa; }
+                s3 = s3 + pa;
+            }
+        }
+        L.tr[lane][g] = s0;
+        L.tr[lane][15 - g] = s1;
+        hold[g] = s2;
+        hold[15 - g] = s3;
+        __asm__ volatile("" ::: "memory"); // (likewise: one group's coefficients at a time)
+    }
 #pragma unroll 1
     for (int half = 0; half < 2; half++) {
-        // s[sub] = y[16] + sum_j filt[j] (y[j] + y[32-j]) + sum_j filt[16+j] (y[33+j] - y[63-j])   (src/encode.c:398-408)
-#pragma unroll 1
-        for (int sb = 0; sb < 16; sb++) {
-            const double *f = T->filt[16 * half + sb];
-            double si = u[0];
+        if (half) {
 #pragma unroll
-            for (int j = 0; j < 31; j++) si = si + f[j] * u[1 + j];
-            L.tr[lane][sb] = si;
-            __asm__ volatile("" ::: "memory"); // (likewise: one row of coefficients at a time)
+            for (int sb = 0; sb < 16; sb++) L.tr[lane][sb] = hold[sb];
         }
         __syncthreads();
         // element lane + 64 m of [slot][16] is slot 4 m + (lane >> 4): the walk adds four slots a step; a slot's parity

@@ -662,9 +662,9 @@ MP3MI_DEVFN void cw_bin(float re, float im, bool exact, float *energy, float *ph
     *phi = ph;
 }
 
-// Phases and the unpredictability measure from the raw FFT bins of one (granule, channel) record by one wavefront:
-// lanes 0..49 the unpredictability of lines 6+4n..9+4n from the three short FFTs (src/l3psy.c:531-549),
-// lanes 50..55 magnitude and phase of long lines 0..5 (src/l3psy.c:497-503).  Kept out of k_fft so that
+// Phases and the unpredictability measure from the raw FFT bins of a (granule, channel) record, a lane per value:
+// 50 values, the unpredictability of lines 6+4n..9+4n from the three short FFTs (src/l3psy.c:531-549), and
+// magnitude and phase of long lines 0..5 (src/l3psy.c:497-503).  Kept out of k_fft so that
 // this double-precision chain runs at full occupancy instead of next to 150 KB of LDS.
 //
 // The sines and cosines: c_w only ever reaches a bit through cb[b] += c_w * energy, a sum that is rounded to FLOAT at
@@ -673,7 +673,36 @@ MP3MI_DEVFN void cw_bin(float re, float im, bool exact, float *energy, float *ph
 // every step that the float it rounds to cannot depend on that; the blocks of records where it could are repeated
 // with FASTSC = false, the correctly rounded dm_sincos (k_cw_fix, then k_part again).
 template <bool FASTSC>
-MP3MI_DEVFN void cw_record(const float *__restrict__ bins, double *__restrict__ cw_mid, float *__restrict__ hist6, size_t rec, int force_exact)
+MP3MI_DEVFN double cw_value(const float (&e)[3], const float (&ph)[3])
+{
+    const double r_prime = 2.0 * __builtin_sqrt((double) e[0]) - __builtin_sqrt((double) e[2]);
+    const double phi_prime = 2.0 * (double) ph[0] - (double) ph[2];
+    const double r2 = __builtin_sqrt((double) e[1]);
+    const double phi2 = (double) ph[1];
+    double s2, c2, sp, cp;
+    if (FASTSC) {
+        dm_sincos_fast(phi2, &s2, &c2);
+        dm_sincos_fast(phi_prime, &sp, &cp);
+    } else {
+        dm_sincos(phi2, &s2, &c2);
+        dm_sincos(phi_prime, &sp, &cp);
+    }
+    const double t1 = r2 * c2 - r_prime * cp;
+    const double t2 = r2 * s2 - r_prime * sp;
+    const double t3 = r2 + __builtin_fabs(r_prime);
+    double cw = 0.0;
+    if (t3 != 0.0) cw = __builtin_sqrt(t1 * t1 + t2 * t2) / t3;
+    // Predicted and actual line bit for bit alike (digital silence: every energy at its floor, every phase 0; a
+    // stationary bin): the reference subtracts a product from itself, whatever its libm returns for the sine --
+    // its c_w is +0 exactly, as ours is.  -0.0 tells k_part that this zero is not a first-tier estimate (it adds
+    // like +0.0 there): without it every record of a silent stream would go through the second tier.
+    if (r2 == r_prime && phi2 == phi_prime) cw = -0.0;
+    return cw;
+}
+
+// the second tier (k_cw_fix): one listed record by one wavefront, lanes 0..49 its 50 values again with the correctly
+// rounded sines and cosines (the long lines are the same in both tiers: k_cw has written them)
+MP3MI_DEVFN void cw_record_exact(const float *__restrict__ bins, double *__restrict__ cw_mid, size_t rec, int force_exact)
 {
     const int lane = wave_lane();
     const float *b = bins + rec * MP3MI_FFT_BINS;
@@ -681,53 +710,31 @@ MP3MI_DEVFN void cw_record(const float *__restrict__ bins, double *__restrict__ 
     if (lane < 50) {
 #pragma unroll
         for (int sb = 0; sb < 3; sb++) { re[sb] = b[(sb * 50 + lane) * 2]; im[sb] = b[(sb * 50 + lane) * 2 + 1]; }
-    } else if (lane < 56) {
-        re[0] = b[300 + lane - 50];
-        im[0] = b[306 + lane - 50];
     }
     float e[3], ph[3];
     bool unsafe = force_exact != 0;
     if (!unsafe) {
 #pragma unroll
-        for (int sb = 0; sb < 3; sb++) cw_bin<false>(re[sb], im[sb], lane == 50 && sb == 0, &e[sb], &ph[sb], &unsafe);
+        for (int sb = 0; sb < 3; sb++) cw_bin<false>(re[sb], im[sb], false, &e[sb], &ph[sb], &unsafe);
     }
     if (wave_any(unsafe)) { // rare: some phase too close to a float midpoint for the first tier
 #pragma unroll
-        for (int sb = 0; sb < 3; sb++) cw_bin<true>(re[sb], im[sb], lane == 50 && sb == 0, &e[sb], &ph[sb], &unsafe);
+        for (int sb = 0; sb < 3; sb++) cw_bin<true>(re[sb], im[sb], false, &e[sb], &ph[sb], &unsafe);
     }
-    if (lane < 50) {
-        const double r_prime = 2.0 * __builtin_sqrt((double) e[0]) - __builtin_sqrt((double) e[2]);
-        const double phi_prime = 2.0 * (double) ph[0] - (double) ph[2];
-        const double r2 = __builtin_sqrt((double) e[1]);
-        const double phi2 = (double) ph[1];
-        double s2, c2, sp, cp;
-        if (FASTSC) {
-            dm_sincos_fast(phi2, &s2, &c2);
-            dm_sincos_fast(phi_prime, &sp, &cp);
-        } else {
-            dm_sincos(phi2, &s2, &c2);
-            dm_sincos(phi_prime, &sp, &cp);
-        }
-        const double t1 = r2 * c2 - r_prime * cp;
-        const double t2 = r2 * s2 - r_prime * sp;
-        const double t3 = r2 + __builtin_fabs(r_prime);
-        double cw = 0.0;
-        if (t3 != 0.0) cw = __builtin_sqrt(t1 * t1 + t2 * t2) / t3;
-        // Predicted and actual line bit for bit alike (digital silence: every energy at its floor, every phase 0; a
-        // stationary bin): the reference subtracts a product from itself, whatever its libm returns for the sine --
-        // its c_w is +0 exactly, as ours is.  -0.0 tells k_part that this zero is not a first-tier estimate (it adds
-        // like +0.0 there): without it every record of a silent stream would go through the second tier.
-        if (r2 == r_prime && phi2 == phi_prime) cw = -0.0;
-        cw_mid[rec * 50 + lane] = cw;
-    } else if (lane < 56 && FASTSC) { // (the same in both tiers: written once)
-        hist6[rec * 12 + lane - 50] = (float) __builtin_sqrt((double) e[0]); // r, src/l3psy.c:500
-        hist6[rec * 12 + 6 + lane - 50] = ph[0];
-    }
+    if (lane < 50) cw_mid[rec * 50 + lane] = cw_value<false>(e, ph);
 }
 
-// first tier: one wavefront per record.  exact_sc (MP3MI_CW_EXACT=1, tests): the second tier for every record.
+// first tier.  A value depends on nothing but its own bins, so the work of a launch is laid across the wavefronts
+// without regard to record boundaries: items 0 .. 50 n_rec - 1 are the unpredictability values -- item t is line t % 50
+// of record t / 50 --, items 50 n_rec .. 56 n_rec - 1 the long lines -- line k % 6 of record k / 6 --; a wavefront takes
+// 64 consecutive items.  (A wavefront per record kept 50 of its 64 lanes busy, and its idle lanes, whose stand-in bin
+// is real, sent every wavefront through the correctly rounded atan2 beside the plain one.)  The item -> address
+// arithmetic is 32-bit: 56 n_rec + 64 < 2^32 for the n_rec <= MP3MI_CW_MAX_REC that batch creation admits (mp3mi_host.h).
+// A wavefront of long lines computes one bin per lane, not three.  The retry below now spans lanes of two records: harmless for the reason it
+// is within one -- a lane that was safe gets the same float from the correctly rounded atan2.
+// exact_sc (MP3MI_CW_EXACT=1, tests): the second tier's sines and cosines for every value.
 __global__ void __launch_bounds__(64) k_cw(const float *__restrict__ bins, double *__restrict__ cw_mid, float *__restrict__ hist6,
-                                          int force_exact, int exact_sc)
+                                          unsigned n_rec, int force_exact, int exact_sc)
 {
 #if !defined(MP3MI_EMU)
     // beside k_loop (batch.cpp) this kernel gets what that one leaves: with the highest wave priority it is through in its
@@ -736,16 +743,56 @@ __global__ void __launch_bounds__(64) k_cw(const float *__restrict__ bins, doubl
     __builtin_amdgcn_s_setprio(3);
 #endif
 
-    cw_record<true>(bins, cw_mid, hist6, blockIdx.x, force_exact);
-    if (exact_sc) cw_record<false>(bins, cw_mid, hist6, blockIdx.x, force_exact);
+    const unsigned n_up = 50u * n_rec, n_item = 56u * n_rec;
+    const unsigned t0 = 64u * (unsigned) blockIdx.x, t = t0 + (unsigned) wave_lane();
+    const bool up = t < n_up, lg = !up && t < n_item;
+    const int nb = t0 >= n_up ? 1 : 3; // bins per lane: the same for the whole wavefront
+    unsigned rec = 0, l = 0;
+    float re[3] = {1.0f, 1.0f, 1.0f}, im[3] = {0.0f, 0.0f, 0.0f}; // (a lane past the last item, and the second and third bin of a long line)
+    if (up) {
+        rec = t / 50u;
+        l = t - 50u * rec;
+        const float *b = bins + (size_t) rec * MP3MI_FFT_BINS + 2u * l;
+#pragma unroll
+        for (int sb = 0; sb < 3; sb++) { re[sb] = b[sb * 100]; im[sb] = b[sb * 100 + 1]; }
+    } else if (lg) {
+        const unsigned k = t - n_up;
+        rec = k / 6u;
+        l = k - 6u * rec;
+        const float *b = bins + (size_t) rec * MP3MI_FFT_BINS + 300u + l;
+        re[0] = b[0];
+        im[0] = b[6];
+    }
+    const bool real0 = lg && l == 0; // long line 0 is real and has no floor (cw_bin)
+    float e[3] = {1.0f, 1.0f, 1.0f}, ph[3] = {0.0f, 0.0f, 0.0f};
+    bool unsafe = force_exact != 0;
+    if (!unsafe) {
+#pragma unroll
+        for (int sb = 0; sb < 3; sb++)
+            if (sb < nb) cw_bin<false>(re[sb], im[sb], real0 && sb == 0, &e[sb], &ph[sb], &unsafe);
+    }
+    if (wave_any(unsafe)) { // rare: some phase too close to a float midpoint for the first tier
+#pragma unroll
+        for (int sb = 0; sb < 3; sb++)
+            if (sb < nb) cw_bin<true>(re[sb], im[sb], real0 && sb == 0, &e[sb], &ph[sb], &unsafe);
+    }
+    if (up) {
+        double *o = cw_mid + (size_t) rec * 50 + l;
+        *o = cw_value<true>(e, ph);
+        if (exact_sc) *o = cw_value<false>(e, ph);
+    } else if (lg) {
+        float *h = hist6 + (size_t) rec * 12 + l;
+        h[0] = (float) __builtin_sqrt((double) e[0]); // r, src/l3psy.c:500
+        h[6] = ph[0];
+    }
 }
 
 // second tier: the records k_part listed, a wavefront each (a fixed grid walks the list)
-__global__ void __launch_bounds__(64) k_cw_fix(const float *__restrict__ bins, double *__restrict__ cw_mid, float *__restrict__ hist6,
+__global__ void __launch_bounds__(64) k_cw_fix(const float *__restrict__ bins, double *__restrict__ cw_mid,
                                               int force_exact, const mp3mi_cw_fixlist *__restrict__ fix)
 {
     const unsigned n_fix = fix->count < fix->cap ? fix->count : fix->cap;
-    for (unsigned i = blockIdx.x; i < n_fix; i += gridDim.x) cw_record<false>(bins, cw_mid, hist6, fix->list[i], force_exact);
+    for (unsigned i = blockIdx.x; i < n_fix; i += gridDim.x) cw_record_exact(bins, cw_mid, fix->list[i], force_exact);
 }
 
 __global__ void __launch_bounds__(64) k_cw_fix_reset(mp3mi_cw_fixlist *fix, unsigned cap)
@@ -877,7 +924,10 @@ void mp3mi_launch_fft(const mp3mi_tables *T, const mp3mi_geom &g, const int16_t 
         hipLaunchKernelGGL((k_fft<1, W, true>), dim3((unsigned) grid), dim3(64 * W), 0, st, T, g, pcm, energy_l, energy_s, bins);
         hipLaunchKernelGGL((k_fft<1, W, false>), dim3((unsigned) grid), dim3(64 * W), 0, st, T, g, pcm, energy_l, energy_s, bins);
     }
-    if (which & 2) hipLaunchKernelGGL(k_cw, dim3((unsigned) (n_task * g.channels)), dim3(64), 0, st, bins, cw_mid, hist6, (g.test_flags >> 1) & 1, (g.test_flags >> 4) & 1);
+    if (which & 2) {
+        const unsigned n_rec = (unsigned) n_task * (unsigned) g.channels; // (<= MP3MI_CW_MAX_REC: batch creation)
+        hipLaunchKernelGGL(k_cw, dim3((n_rec * 56u + 63u) / 64u), dim3(64), 0, st, bins, cw_mid, hist6, n_rec, (g.test_flags >> 1) & 1, (g.test_flags >> 4) & 1);
+    }
 }
 
 // the second tier of the unpredictability for the records k_part listed (mp3mi_launch_psy)
@@ -887,7 +937,7 @@ void mp3mi_launch_cw_fix_reset(mp3mi_cw_fixlist *fix, unsigned cap, hipStream_t 
 }
 void mp3mi_launch_cw_fix(const mp3mi_geom &g, const float *bins, double *cw_mid, float *hist6, const mp3mi_cw_fixlist *fix, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_cw_fix, dim3(2048), dim3(64), 0, st, bins, cw_mid, hist6, (g.test_flags >> 1) & 1, fix);
+    hipLaunchKernelGGL(k_cw_fix, dim3(2048), dim3(64), 0, st, bins, cw_mid, (g.test_flags >> 1) & 1, fix); // (hist6: the long lines are k_cw's)
 }
 
 ULP_CENSUS_ACCESSOR(mp3mi_debug_ulp_census_fft)

@@ -254,7 +254,7 @@ __global__ void __launch_bounds__(64) k_part(const mp3mi_tables *__restrict__ T,
         const double t2 = (double) rn * sn - r_prime * sp;
         const double t3 = (double) rn + __builtin_fabs(r_prime);
         double cw = (t3 != 0.0) ? __builtin_sqrt(t1 * t1 + t2 * t2) / t3 : 0.0;
-        if ((double) rn == r_prime && (double) pn == phi_prime) cw = -0.0; // an exact zero in the reference too (k_fft.hip, cw_record)
+        if ((double) rn == r_prime && (double) pn == phi_prime) cw = -0.0; // an exact zero in the reference too (k_fft.hip, cw_value)
         part_line<false>(T, W, Lt, j, er[j], cw, eb_all, cb_all, &amb PART_CENSUS_PASS); // (correctly rounded sines: nothing to check)
     }
     // lines 6..511 in blocks of 32 = one 128-byte line of the energy row; the unpredictability of lines

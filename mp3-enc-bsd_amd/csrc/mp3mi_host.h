@@ -13,6 +13,9 @@ extern "C" {
 int mp3mi_build_tables(mp3mi_tables *T, int rate_idx);
 /* hashes of the table members as this host builds them (test / pin generation; tables_host.cpp) */
 int mp3mi_tables_digest(int rate_idx, uint64_t *hashes, const char **names, int cap);
+/* the mirror identities of the 32 x 32 matrixing coefficients that k_filter's shared products rest on, bit for bit
+ * (tables_host.cpp; every table build runs it, and mp3mi_build_tables reports a violation as -8 like a damaged blob): 0, or -14 */
+int mp3mi_filt_mirror_check(const double *filt);
 
 #ifdef __cplusplus
 }
@@ -75,6 +78,9 @@ static inline mp3mi_geom mp3mi_make_geom(int n_streams, int channels, int rate_i
     return g;
 }
 
+/* records (granule, channel) of one launch at most: k_cw numbers 56 items a record in 32 bits (k_fft.hip); batch
+ * creation refuses a chunk beyond it -- its per-chunk buffers would take more than a terabyte */
+#define MP3MI_CW_MAX_REC ((size_t) 1 << 26)
 void mp3mi_launch_fft(const mp3mi_tables *T, const mp3mi_geom &g, const int16_t *pcm,
                       float *energy_l, float *energy_s, float *bins, double *cw_mid, float *hist6, hipStream_t st, int which = 3);
 /* records whose unpredictability needs its second tier (k_part lists them, k_cw_fix and k_part's second run work

@@ -108,6 +108,33 @@ static int tb_get(uint32_t id, int rate, void *dst, size_t bytes)
 #define LIBM_TABLE(id, rate, dst, bytes, ...) do { if (tb_get((id), (rate), (dst), (bytes))) return -7; } while (0)
 #endif
 
+/* The matrixing coefficients filt[i][j] = cos((2i+1) n pi/64) rounded to 1e-9, n = 16-j (j < 16) or j+1 (j >= 16):
+ * rows g, 15-g, 16+g and 31-g (g = 0..7) repeat each other up to sign, and k_filter multiplies once for the four of
+ * them.  That holds for the cosine; whether it holds for the 32 x 32 doubles in hand, bit for bit, is checked here
+ * (as integers: a zero of the wrong sign is a violation too).  0, or -14 with the first violation on stderr. */
+extern "C" int mp3mi_filt_mirror_check(const double *filt)
+{
+    auto bits = [&](int i, int j, bool neg) {
+        uint64_t b;
+        memcpy(&b, &filt[32 * i + j], 8);
+        return neg ? b ^ 0x8000000000000000ull : b;
+    };
+    for (int g = 0; g < 8; g++)
+        for (int j = 0; j < 31; j++) {
+            const int n = j < 16 ? 16 - j : j + 1;
+            const bool odd = n & 1;
+            int bad = -1;
+            if (bits(31 - g, j, false) != bits(g, j, odd)) bad = 31 - g;
+            else if (bits(16 + g, j, false) != bits(15 - g, j, odd)) bad = 16 + g;
+            else if (!odd && bits(15 - g, j, false) != bits(g, j, (n >> 1) & 1)) bad = 15 - g;
+            if (bad >= 0) {
+                fprintf(stderr, "mp3mi: matrixing coefficient filt[%d][%d] does not mirror its group's (g = %d): k_filter cannot share its products\n", bad, j, g);
+                return -14;
+            }
+        }
+    return 0;
+}
+
 static const int SFB_L[3][23] = {
     {0,4,8,12,16,20,24,30,36,44,52,62,74,90,110,134,162,196,238,288,342,418,576},
     {0,4,8,12,16,20,24,30,36,42,50,60,72,88,106,128,156,190,230,276,330,384,576},
@@ -957,6 +984,9 @@ static int build_tables_unpinned(mp3mi_tables *T, int rate_idx)
                    for (int j = 0; j < 15; j++) T->filt[i][16 + j] = row[33 + j];
                    T->filt[i][31] = 0.0;
                });
+    /* k_filter computes the products of four mirrored rows once (k_fbmdct.hip): built or read from the blob, a table
+       that does not mirror never reaches it */
+    if (mp3mi_filt_mirror_check(&T->filt[0][0]) != 0) return -14;
 
     double (*win)[36] = T->mdct_win;
     LIBM_TABLE(TB_MDCT_WIN, -1, T->mdct_win, sizeof(T->mdct_win),
@@ -1182,7 +1212,7 @@ extern "C" int mp3mi_build_tables(mp3mi_tables *T, int rate_idx)
 {
     std::lock_guard<std::mutex> lock(g_tables_mutex);
     const int rc = build_tables_unpinned(T, rate_idx);
-    if (rc == -7) return -8; /* the blob lacks an entry or is damaged: reported as MP3MI_ERR_TABLES */
+    if (rc == -7 || rc == -14) return -8; /* the blob lacks an entry, is damaged, or holds matrixing coefficients that do not mirror: reported as MP3MI_ERR_TABLES */
     if (rc != 0) return rc;
     if (MP3MI_TABLE_PINS_N != MP3MI_N_TABLE_MEMBERS) {
         fprintf(stderr, "mp3mi: tables_pins.h lists %d members, mp3mi_tables has %d -- regenerate it (tools/gen_table_pins.py)\n",
