@@ -148,15 +148,11 @@ struct mp3mi_batch {
     uint8_t *carry;          // [S][MP3MI_CARRY_BYTES]: file bytes formatted but not final yet
     int32_t *carry_len;      // [S]
     carried_region carried[N_CARRIED];
-    // streaming (encode_next / flush), the whole-batch bookkeeping
-    long frames_done;        // frames of every stream encoded since the last reset
+    // streaming: where the streams are -- the whole-batch counter of encode_next / flush (book.frames_all: frames of every stream
+    // encoded since the last reset) and the slots of mp3mi_batch_encode_slots (host_util.h)
+    slot_book book;
     bool fresh;              // reset since the last encode (or never encoded): state buffers are zero
     int debug, last_nf;
-    // per-slot streaming (mp3mi_batch_encode_slots): a stream index is a SLOT through which one stream after another passes.
-    // While slots_on is false the slots are as frames_done says (all open at frames_done when it is > 0, else all closed) and
-    // every call runs the whole-batch path above; a per-slot call sets slots_on, and the slots are as slot_frames_h says.
-    bool slots_on;
-    std::vector<int64_t> slot_frames_h; // frames encoded by the stream open in each slot, -1: no stream open there
     // the control block of a per-slot call (ctl_layout), twice, taken in turn by the per-slot calls: an entry's fence is recorded
     // behind the last reader of its device copy, and the host waits for it before it writes the staging again (the per-slot call
     // two before: ctl_take)
@@ -240,23 +236,17 @@ template <typename E> static hipError_t ring_entry_create(mp3mi_batch *b, E &en,
     return e;
 }
 
-static const int BITRATES[15] = {0, 32, 40, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256, 320}; // src/common.c:124
-
 // What a bitrate means for a stream of sampling-frequency code ri: its index in the header and the frame's size, slots per frame
 // never padded (src/musicin.c:562-581).  False for anything but an MPEG-1 Layer III bitrate (src/common.c:118-125, 460-481) --
 // the check of mp3mi_batch_create_ex and of a per-slot call's kbps_host alike.
 static bool rate_of_kbps(int ri, int k, int *bitrate_index, int *bits_per_frame)
 {
-    int bi;
-    for (bi = 1; bi < 15; bi++)
-        if (BITRATES[bi] == k) break;
-    if (bi == 15 || ri < 0 || ri > 2) return false;
+    const int bi = bitrate_index_of(3, k);
+    if (!bi || ri < 0 || ri > 2) return false;
     *bitrate_index = bi;
     *bits_per_frame = frame_bits(1152, ri, k, 8);
     return true;
 }
-
-static int rate_idx_of(int rate_hz) { return rate_hz == 44100 ? 0 : rate_hz == 48000 ? 1 : rate_hz == 32000 ? 2 : -1; }
 
 #if !defined(MP3MI_SOURCE_HASH)
 #define MP3MI_SOURCE_HASH "unknown"
@@ -377,11 +367,7 @@ static int batch_build(mp3mi_batch *b, int n_streams, int rate_hz, int channels,
 
     std::vector<char> Th_store(sizeof(mp3mi_tables)); // host copy of the tables, released on every path
     mp3mi_tables *Th = (mp3mi_tables *) Th_store.data();
-    {
-        const int trc = mp3mi_build_tables(Th, ri);
-        if (trc == -8) return MP3MI_ERR_TABLES; // the host's libm does not reproduce the pinned tables (tables_host.cpp)
-        if (trc != 0) return MP3MI_ERR_ARG;
-    }
+    { const int trc = tables_rc(mp3mi_build_tables(Th, ri)); if (trc != MP3MI_OK) return trc; }
     const size_t S = (size_t) n_streams, ngc = S * 2 * (size_t) cf * (size_t) channels;
     {
         int least = 0, greatest = 0;
@@ -474,7 +460,7 @@ static int batch_build(mp3mi_batch *b, int n_streams, int rate_hz, int channels,
     // slot that never had a stream must hold a valid -- fresh -- encoder state for that)
     for (const carried_region &r : b->carried)
         if (r.zero) CHK(hipMemset(r.base, 0, r.bytes * S));
-    b->slot_frames_h.assign(S, -1);
+    b->book.init(n_streams);
     b->ctl_at.init(S);
     for (mp3mi_batch::ctl_ring::entry &en : b->ctl.e) CHK(ring_entry_create(b, en, b->ctl_at.bytes));
     CHK(hipEventCreateWithFlags(&b->ev_ctl_up, hipEventDisableTiming));
@@ -508,7 +494,7 @@ extern "C" int mp3mi_batch_create_ex(mp3mi_batch **out, int n_streams, int rate_
             return MP3MI_ERR_ARG;
     }
     // argument errors first: they are the caller's, whatever the machine
-    if (rate_hz != 44100 && rate_hz != 48000 && rate_hz != 32000) return MP3MI_ERR_ARG; // src/l3psy.c:170-176 exits on anything else
+    if (rate_idx_of(rate_hz) < 0) return MP3MI_ERR_ARG; // src/l3psy.c:170-176 exits on anything else
     if (n_streams <= 0 || max_frames <= 0 || (channels != 1 && channels != 2)) return MP3MI_ERR_ARG;
     for (int s = 0; s < n_streams; s++) {
         int bi, bits;
@@ -669,9 +655,8 @@ static int reset_impl(mp3mi_batch *b)
     CHK(b->ev_done.wait_on(b->stream)); // the previous call's kernels may still be running on the loop stream
     for (const carried_region &r : b->carried) // (all on the front stream, the loop stream's regions too: behind ev_done)
         if (r.zero) CHK(hipMemsetAsync(r.base, 0, r.bytes * (size_t) b->n_streams, b->stream));
-    b->frames_done = 0;
+    b->book.close();
     b->fresh = true;
-    b->slots_on = false;
     return MP3MI_OK;
 }
 
@@ -698,28 +683,6 @@ extern "C" int mp3mi_batch_encode_ragged(mp3mi_batch *b, const int16_t *pcm_dev,
 }
 
 // ---- per-slot streaming (mp3mi_batch_encode_slots) ----
-// What every slot holds before a call: the frames of the stream open in it, -1 for none (mp3mi_batch::slots_on)
-static void slot_frames_now(const mp3mi_batch *b, int64_t *f)
-{
-    for (int s = 0; s < b->n_streams; s++) f[s] = b->slots_on ? b->slot_frames_h[s] : (b->frames_done > 0 ? (int64_t) b->frames_done : -1);
-}
-
-// The per-slot bookkeeping is in force, with the slots as f says -- unless every slot is open at the same frame: then it hands over to
-// the whole-batch one, and the next call runs exactly as if there had never been a per-slot call (a batch whose streams all
-// began together)
-static void slots_settle(mp3mi_batch *b, const std::vector<int64_t> &f)
-{
-    b->slot_frames_h = f;
-    b->slots_on = true;
-    const int64_t f0 = b->slot_frames_h[0];
-    for (int s = 1; s < b->n_streams; s++)
-        if (b->slot_frames_h[s] != f0) return;
-    if (f0 > 0) {
-        b->slots_on = false;
-        b->frames_done = f0;
-    }
-}
-
 // Writes the staging copy of the control block this per-slot call takes (waits for the per-slot call two before, whose kernels
 // read the device copy of the same parity and whose upload read this staging)
 static int ctl_take(mp3mi_batch *b, mp3mi_batch::ctl_ring::entry **blk)
@@ -729,21 +692,16 @@ static int ctl_take(mp3mi_batch *b, mp3mi_batch::ctl_ring::entry **blk)
     return MP3MI_OK;
 }
 
-// The rules of a per-slot call, slot by slot (f: slot_frames_now)
+// The rules of a per-slot call (f: slot_book::now): the book's, which all three layers share, then Layer III's own of the bitrate -- a
+// STARTing stream's (0: the slot's create-time one) is a Layer III bitrate that fits the rows; any other slot's is 0, or what the
+// open stream has
 static bool slots_rules_ok(const mp3mi_batch *b, const int64_t *f, int n_frames, const uint8_t *ctl_host, const int32_t *n_samples_host,
                            const int32_t *kbps_host)
 {
-    const int32_t full = (int32_t) n_frames * 1152;
-    for (int s = 0; s < b->n_streams; s++) {
-        const int c = ctl_host[s];
-        if (c & ~(MP3MI_SLOT_START | MP3MI_SLOT_END)) return false;
-        const bool open = f[s] >= 0, start = c & MP3MI_SLOT_START, end = c & MP3MI_SLOT_END, part = open || start;
-        if (end && !part) return false;
-        const int32_t n = n_samples_host ? n_samples_host[s] : (part ? full : 0);
-        if (!part ? n != 0 : (!end ? n != full : (n < 0 || n > full))) return false;
-        // the bitrate: a STARTing stream's own (0: the slot's create-time one), a Layer III bitrate that fits the rows; else 0, or
-        // what the open stream has
-        const int32_t k = kbps_host ? kbps_host[s] : 0;
+    if (!b->book.rules_ok(f, n_frames, 1152, ctl_host, n_samples_host)) return false;
+    for (int s = 0; kbps_host && s < b->n_streams; s++) {
+        const bool open = f[s] >= 0, start = ctl_host[s] & MP3MI_SLOT_START;
+        const int32_t k = kbps_host[s];
         int bi, bits;
         if (start ? (k != 0 && (k > b->ceil_kbps || !rate_of_kbps(b->rate_idx, k, &bi, &bits))) : (k != 0 && !(open && k == b->slot_kbps_h[s])))
             return false;
@@ -758,9 +716,8 @@ static int slots_impl(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, cons
     if (!b || !pcm_dev || !ctl_host || !out_dev || !out_len_dev || n_frames <= 0 || n_frames > b->max_frames) return MP3MI_ERR_ARG;
     if (out_stride < min_out_stride(b, n_frames, true)) return MP3MI_ERR_ARG;
     const int S = b->n_streams;
-    const int32_t full = (int32_t) n_frames * 1152;
     std::vector<int64_t> f((size_t) S);
-    slot_frames_now(b, f.data());
+    b->book.now(f.data());
     // every rule first: a call that breaks one leaves the batch as it was
     if (!slots_rules_ok(b, f.data(), n_frames, ctl_host, n_samples_host, kbps_host)) return MP3MI_ERR_ARG;
     ON_DEVICE(b);
@@ -774,26 +731,20 @@ static int slots_impl(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, cons
     }
     std::vector<int32_t> kb(b->slot_kbps_h);
     bool other_rate = false; // a stream STARTs at another bitrate than its slot was created with
-    sc.n_start = 0;
+    sc.n_start = b->book.fill(f.data(), n_frames, 1152, ctl_host, n_samples_host, st.fabs, st.n_samples, st.ctl, st.list);
+    for (int i = 0; i < sc.n_start; i++) { // the bitrates of the streams that START, in the order of the list
+        const int s = st.list[i];
+        kb[s] = (kbps_host && kbps_host[s]) ? kbps_host[s] : b->kbps_h[s];
+        int bi = 0, bits = 0;
+        (void) rate_of_kbps(b->rate_idx, kb[s], &bi, &bits); // (checked: slots_rules_ok, create)
+        st.rate_bits[i] = bits;
+        st.rate_index[i] = bi;
+        other_rate |= kb[s] != b->kbps_h[s];
+    }
     sc.any_continue = false;
     for (int s = 0; s < S; s++) {
-        const int c = ctl_host[s];
-        const bool open = f[s] >= 0, start = c & MP3MI_SLOT_START, part = open || start;
-        st.fabs[s] = (start || !open) ? 0 : f[s];
-        st.n_samples[s] = n_samples_host ? n_samples_host[s] : (part ? full : 0);
-        st.ctl[s] = (uint8_t) ((c & MP3MI_SLOT_START ? MP3MI_SLOT_DEV_START : 0) | (c & MP3MI_SLOT_END ? MP3MI_SLOT_DEV_END : 0) |
-                            (part ? MP3MI_SLOT_DEV_ACTIVE : 0));
-        if (start) {
-            kb[s] = (kbps_host && kbps_host[s]) ? kbps_host[s] : b->kbps_h[s];
-            int bi = 0, bits = 0;
-            (void) rate_of_kbps(b->rate_idx, kb[s], &bi, &bits); // (checked: slots_rules_ok, create)
-            st.rate_bits[sc.n_start] = bits;
-            st.rate_index[sc.n_start] = bi;
-            other_rate |= kb[s] != b->kbps_h[s];
-            st.list[sc.n_start++] = s;
-        } else if (open)
-            sc.any_continue = true;
-        if (c & MP3MI_SLOT_END) kb[s] = b->kbps_h[s]; // the stream takes its bitrate with it
+        if (f[s] >= 0 && !(ctl_host[s] & MP3MI_SLOT_START)) sc.any_continue = true;
+        if (ctl_host[s] & MP3MI_SLOT_END) kb[s] = b->kbps_h[s]; // the stream takes its bitrate with it
     }
     // the START slots' bitrates go into the live arrays (encode_impl) once any slot of the batch may hold another than its
     // create-time one -- a START with kbps 0, or without kbps_host, then brings its slot back; a batch that never saw another
@@ -804,13 +755,8 @@ static int slots_impl(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, cons
     b->ctl.next();
     b->slot_kbps_h.swap(kb);
     b->rate_dirty |= other_rate;
-    for (int s = 0; s < S; s++) {
-        const int c = ctl_host[s];
-        if (c & MP3MI_SLOT_START) f[s] = 0;
-        if (c & MP3MI_SLOT_END) f[s] = -1;
-        else if (f[s] >= 0) f[s] += n_frames;
-    }
-    slots_settle(b, f);
+    b->book.advance(f.data(), ctl_host, n_frames);
+    b->book.settle(f.data());
     return MP3MI_OK;
 }
 
@@ -837,28 +783,23 @@ extern "C" int mp3mi_batch_slot_kbps(const mp3mi_batch *b, int32_t *kbps_host)
 extern "C" int mp3mi_batch_slot_frames(const mp3mi_batch *b, int64_t *frames_host)
 {
     if (!b || !frames_host) return MP3MI_ERR_ARG;
-    slot_frames_now(b, frames_host);
-    int n = 0;
-    for (int s = 0; s < b->n_streams; s++) n += frames_host[s] >= 0;
-    return n;
+    b->book.now(frames_host);
+    return b->book.count_open();
 }
 
 extern "C" int mp3mi_batch_encode_next(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, uint8_t *out_dev,
                                        size_t out_stride, uint32_t *out_len_dev)
 {
-    if (b && b->slots_on) {
+    if (b && b->book.on) {
         // per-slot bookkeeping in force: with no stream open every slot starts (the whole-batch start: state cleared for all);
         // otherwise the open streams go on and the other slots stay closed
-        bool any = false;
-        for (int s = 0; s < b->n_streams && !any; s++) any = b->slot_frames_h[s] >= 0;
-        if (any) {
+        if (b->book.any_open()) {
             std::vector<uint8_t> ctl((size_t) b->n_streams, 0);
             return slots_impl(b, pcm_dev, n_frames, ctl.data(), NULL, NULL, out_dev, out_stride, out_len_dev);
         }
         if (!pcm_dev || !out_dev || !out_len_dev || n_frames <= 0 || n_frames > b->max_frames || out_stride < min_out_stride(b, n_frames, true))
             return MP3MI_ERR_ARG; // (before the bookkeeping changes)
-        b->slots_on = false;
-        b->frames_done = 0;
+        b->book.close();
         b->fresh = false;
     }
     return encode_impl(b, pcm_dev, NULL, n_frames, out_dev, out_stride, out_len_dev, false);
@@ -901,12 +842,10 @@ extern "C" int mp3mi_batch_flush(mp3mi_batch *b, uint8_t *out_dev, size_t out_st
     ON_DEVICE(b);
     hold_release(b);
     const int S = b->n_streams;
-    call_shape cs = {0, NULL, b->frames_done, NULL, NULL, false};
+    call_shape cs = {0, NULL, b->book.frames_all, NULL, NULL, false};
     mp3mi_batch::ctl_ring::entry *blk = NULL;
-    if (b->slots_on) { // some slots open, not all at the same frame (slots_settle), or none: end the open ones
-        int n_open = 0;
-        for (int s = 0; s < S; s++) n_open += b->slot_frames_h[s] >= 0;
-        if (n_open == 0) { // nothing to end; the ended streams' status stays in their slots
+    if (b->book.on) { // some slots open, not all at the same frame (slot_book::settle), or none: end the open ones
+        if (!b->book.any_open()) { // nothing to end; the ended streams' status stays in their slots -- and the book stays on
             CHK(hipMemsetAsync(out_len_dev, 0, sizeof(uint32_t) * (size_t) S, b->lstream));
             return MP3MI_OK;
         }
@@ -914,8 +853,8 @@ extern "C" int mp3mi_batch_flush(mp3mi_batch *b, uint8_t *out_dev, size_t out_st
         memset(blk->stage, 0, b->ctl_at.base_bytes); // (k_stream_tail reads fabs_s and ctl only)
         const ctl_block st = b->ctl_at.at(blk->stage), dev = b->ctl_at.at(blk->dev);
         for (int s = 0; s < S; s++) {
-            const bool open = b->slot_frames_h[s] >= 0;
-            st.fabs[s] = open ? b->slot_frames_h[s] : 0;
+            const bool open = b->book.at(s) >= 0;
+            st.fabs[s] = open ? b->book.at(s) : 0;
             st.ctl[s] = open ? MP3MI_SLOT_DEV_ACTIVE : 0;
         }
         CHK(hipMemcpyAsync(blk->dev, blk->stage, b->ctl_at.base_bytes, hipMemcpyHostToDevice, b->lstream));
@@ -1037,7 +976,7 @@ extern "C" int mp3mi_batch_slots_export(mp3mi_batch *b, int n, const int32_t *sl
     const size_t state_bytes = park_tables(b, &front, &loop);
     if (!park_args_ok(b, n, slots_host, state_dev, state_stride, tickets_host, state_bytes)) return MP3MI_ERR_ARG;
     std::vector<int64_t> f((size_t) b->n_streams);
-    slot_frames_now(b, f.data());
+    b->book.now(f.data());
     for (int i = 0; i < n; i++)
         if (f[slots_host[i]] < 0) return MP3MI_ERR_ARG; // no stream open there
     ON_DEVICE(b);
@@ -1059,14 +998,14 @@ extern "C" int mp3mi_batch_slots_export(mp3mi_batch *b, int n, const int32_t *sl
     const int rc = park_run(b, n, slots_host, front, loop, state_dev, state_stride, 1);
     if (rc != MP3MI_OK) return rc;
     if (close) {
-        // (the whole-batch bookkeeping cannot say "all but these": the per-slot one takes over; slots_settle hands back as ever)
+        // (the whole-batch bookkeeping cannot say "all but these": the per-slot one takes over; slot_book::settle hands back as ever)
         for (int i = 0; i < n; i++) {
             const int32_t s = slots_host[i];
             f[s] = -1;
             b->slot_kbps_h[s] = b->kbps_h[s]; // the stream takes its bitrate with it
         }
     }
-    slots_settle(b, f);
+    b->book.settle(f.data());
     return MP3MI_OK;
 }
 
@@ -1078,7 +1017,7 @@ extern "C" int mp3mi_batch_slots_import(mp3mi_batch *b, int n, const int32_t *sl
     const size_t state_bytes = park_tables(b, &front, &loop);
     if (!park_args_ok(b, n, slots_host, state_dev, state_stride, tickets_host, state_bytes)) return MP3MI_ERR_ARG;
     std::vector<int64_t> f((size_t) b->n_streams);
-    slot_frames_now(b, f.data());
+    b->book.now(f.data());
     bool other_rate = false; // a stream arrives at another bitrate than its slot was created with
     for (int i = 0; i < n; i++) {
         const int32_t s = slots_host[i];
@@ -1105,9 +1044,9 @@ extern "C" int mp3mi_batch_slots_import(mp3mi_batch *b, int n, const int32_t *sl
     }
     b->rate_dirty |= other_rate;
     // the per-slot bookkeeping from here on, also on a batch nothing has run on yet: no later call takes the "first call clears
-    // every stream's state" branch of encode_impl over the resumed streams (slots_settle hands back only with every slot open)
+    // every stream's state" branch of encode_impl over the resumed streams (slot_book::settle hands back only with every slot open)
     b->fresh = false;
-    slots_settle(b, f);
+    b->book.settle(f.data());
     return MP3MI_OK;
 }
 
@@ -1131,18 +1070,18 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
     // wavefronts, serial, nothing beside them -- runs out: back-to-back calls lose no pipeline fill.
     // a whole-file call starts every stream afresh; a streaming call continues (the first one after create / reset /
     // flush / a whole-file call starts afresh too)
-    if (whole_file || (!sc && b->frames_done == 0 && !b->fresh)) {
+    if (whole_file || (!sc && b->book.frames_all == 0 && !b->fresh)) {
         for (const carried_region &r : b->carried) // (each region on the stream that owns it)
             if (r.zero) CHK(hipMemsetAsync(r.base, 0, r.bytes * (size_t) S, r.loop ? b->lstream : b->stream));
         // streams that per-slot calls began at bitrates of their own end here.  (The host mirror is reset with the copy's enqueue, not
         // with the call's success: a HIP error further down leaves a call half enqueued, like any MP3MI_ERR_HIP of this function,
         // and no entry point recovers a batch from that, so the mirror is not rolled back.)
         if (rates_restore(b) != MP3MI_OK) return MP3MI_ERR_HIP;
-        b->frames_done = 0;
+        b->book.frames_all = 0;
     }
     // (a per-slot call: every slot has its own frame index, in the control block; k_loop counts the frame of a status from the
     // call's first, and k_stream_tail places it in the stream)
-    const long fabs0 = sc ? 0 : b->frames_done;
+    const long fabs0 = sc ? 0 : b->book.frames_all;
     if (sc) n_samples_dev = sc->dev.n_samples;
     const bool kept = b->status_kept;
     b->fresh = false;
@@ -1437,8 +1376,8 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
     }
     if (sc) CHK(sc->blk->free.record(b->lstream)); // (lstream has joined the front stream: every reader of this copy of the control block is ahead of this)
     b->slot_base = (b->slot_base + nchunks) & 1;
-    b->frames_done = (whole_file || sc) ? 0 : fabs0 + n_frames; // a whole-file call leaves finished streams behind
-    if (whole_file) b->slots_on = false;
+    if (whole_file) b->book.close(); // a whole-file call leaves finished streams behind
+    else b->book.frames_all = sc ? 0 : fabs0 + n_frames; // (a per-slot call: slots_impl keeps the slots' frames)
     CHK(hipEventRecord(ts.ev1, b->lstream));
     ts.pending = true;
     b->call_no++;
@@ -1675,7 +1614,7 @@ extern "C" int mp3mi_batch_encode_slots_kbps_host_async(mp3mi_batch *b, const in
     if (n_rows < 1 || n_rows > S || (!row_slot_host && n_rows != S)) return MP3MI_ERR_ARG;
     if (out_stride < mp3mi_batch_out_stride(b, n_frames)) return MP3MI_ERR_ARG;
     std::vector<int64_t> f((size_t) S);
-    slot_frames_now(b, f.data());
+    b->book.now(f.data());
     std::vector<uint8_t> ctl_s;
     std::vector<int32_t> ns_s, kbps_s;
     const uint8_t *ctl = ctl_host;
@@ -1765,38 +1704,24 @@ static int encode_host_impl(int n_streams, int rate_hz, int channels, const int 
     int rc = mp3mi_batch_create(&b, n_streams, rate_hz, channels, kbps, kbps_all, n_frames);
     if (rc != MP3MI_OK) return rc;
     if (hdr >= 0) rc = mp3mi_batch_set_header(b, (hdr >> 3) & 1, (hdr >> 2) & 1, hdr & 3);
-    const size_t pcm_bytes = (size_t) n_streams * (size_t) n_frames * 1152 * (size_t) channels * sizeof(int16_t);
-    int16_t *pcm_d = NULL;
-    uint8_t *out_d = NULL;
-    uint32_t *len_d = NULL;
-    int32_t *ns_d = NULL;
     if (rc == MP3MI_OK && !n_samples) { // whole streams: the overlapped host path (pageable buffers here: staged by the runtime)
         rc = mp3mi_batch_encode_host_async(b, pcm, n_frames, out, out_stride, out_len);
         if (rc == MP3MI_OK) rc = mp3mi_batch_sync(b); // (MP3MI_ERR_REFERENCE_ABORT: done, the outputs are delivered -- mp3mi.h)
-        mp3mi_batch_destroy(b);
-        return rc;
-    }
-    if (rc == MP3MI_OK) rc = MP3MI_ERR_HIP;
-    if (rc == MP3MI_ERR_HIP && hipMalloc((void **) &pcm_d, pcm_bytes) == hipSuccess &&
-        hipMalloc((void **) &out_d, out_stride * n_streams) == hipSuccess &&
-        hipMalloc((void **) &len_d, sizeof(uint32_t) * n_streams) == hipSuccess &&
-        hipMalloc((void **) &ns_d, sizeof(int32_t) * n_streams) == hipSuccess &&
-        hipMemcpy(pcm_d, pcm, pcm_bytes, hipMemcpyHostToDevice) == hipSuccess &&
-        (!n_samples || hipMemcpy(ns_d, n_samples, sizeof(int32_t) * n_streams, hipMemcpyHostToDevice) == hipSuccess)) {
-        rc = n_samples ? mp3mi_batch_encode_ragged(b, pcm_d, ns_d, n_frames, out_d, out_stride, len_d)
-                       : mp3mi_batch_encode(b, pcm_d, n_frames, out_d, out_stride, len_d);
+    } else if (rc == MP3MI_OK) { // a ragged batch: device copies of the call's buffers, freed before the batch goes
+        const size_t S = (size_t) n_streams;
+        hook_bufs D;
+        int16_t *pcm_d = D.copy_of(pcm, S * (size_t) n_frames * 1152 * (size_t) channels);
+        uint8_t *out_d = D.raw<uint8_t>(out_stride * S);
+        uint32_t *len_d = D.raw<uint32_t>(S);
+        int32_t *ns_d = D.copy_of(n_samples, S);
+        rc = D.rc();
+        if (rc == MP3MI_OK) rc = mp3mi_batch_encode_ragged(b, pcm_d, ns_d, n_frames, out_d, out_stride, len_d);
         if (rc == MP3MI_OK) rc = mp3mi_batch_sync(b);
         // MP3MI_ERR_REFERENCE_ABORT means "done, and some stream is an input the reference dies on": that stream's out_len is
         // 0 and every other stream's output is valid (mp3mi.h), so the results are delivered and the code is kept
-        if ((rc == MP3MI_OK || rc == MP3MI_ERR_REFERENCE_ABORT) &&
-            (hipMemcpy(out, out_d, out_stride * n_streams, hipMemcpyDeviceToHost) != hipSuccess ||
-             hipMemcpy(out_len, len_d, sizeof(uint32_t) * n_streams, hipMemcpyDeviceToHost) != hipSuccess))
+        if ((rc == MP3MI_OK || rc == MP3MI_ERR_REFERENCE_ABORT) && !(D.fetch(out, out_d, out_stride * S) && D.fetch(out_len, len_d, S)))
             rc = MP3MI_ERR_HIP;
     }
-    if (pcm_d) hipFree(pcm_d);
-    if (out_d) hipFree(out_d);
-    if (len_d) hipFree(len_d);
-    if (ns_d) hipFree(ns_d);
     mp3mi_batch_destroy(b);
     return rc;
 }

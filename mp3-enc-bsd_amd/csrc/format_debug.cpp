@@ -11,7 +11,6 @@
 #include "host_util.h"
 #include "mp3mi.h"
 
-static const int FD_BITRATES[15] = {0, 32, 40, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256, 320}; // src/common.c:124
 static const int FD_SLEN1[16] = {0, 0, 0, 0, 3, 1, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4};                      // src/l3bitstream.c:171-172
 static const int FD_SLEN2[16] = {0, 1, 2, 3, 0, 1, 2, 3, 1, 2, 3, 1, 2, 3, 2, 3};
 static const int FD_IMAGE_BITS = 640 * 32; // fmt_lds.words (k_format.hip)
@@ -113,23 +112,17 @@ extern "C" int mp3mi_debug_format_frames(int rate_hz, int channels, int kbps, in
 {
     if (!have_device()) return MP3MI_ERR_NO_DEVICE;
     const mp3mi_frame_side *side = (const mp3mi_frame_side *) side_v;
-    const int ri = rate_hz == 44100 ? 0 : (rate_hz == 48000 ? 1 : (rate_hz == 32000 ? 2 : -1));
-    int bi = 1;
-    while (bi < 15 && FD_BITRATES[bi] != kbps) bi++;
-    if (ri < 0 || bi == 15 || (channels != 1 && channels != 2) || hdr_mode < 0 || hdr_mode > 3 || (channels == 1) != (hdr_mode == 3) ||
+    const int ri = rate_idx_of(rate_hz), bi = bitrate_index_of(3, kbps);
+    if (ri < 0 || bi == 0 || (channels != 1 && channels != 2) || hdr_mode < 0 || hdr_mode > 3 || (channels == 1) != (hdr_mode == 3) ||
         (hdr_flags & ~63) || (crc & ~1) || n_streams <= 0 || n_frames < 0 || !n_frames_s || !out_len || !status ||
         (n_frames > 0 && (!ix || !side || !out)))
         return MP3MI_ERR_ARG;
     const int frame_bytes = frame_bits(1152, ri, kbps, 8) / 8;
     const int si_bytes = 4 + 2 * crc + (channels == 2 ? 32 : 17), slot = frame_bytes - si_bytes;
     if (slot <= 0 || out_stride < (size_t) n_frames * frame_bytes + 1) return MP3MI_ERR_ARG;
-    mp3mi_tables *Th = (mp3mi_tables *) malloc(sizeof(mp3mi_tables));
-    if (!Th) return MP3MI_ERR_NOMEM;
-    const int trc = mp3mi_build_tables(Th, ri);
-    if (trc != 0) {
-        free(Th);
-        return trc == -8 ? MP3MI_ERR_TABLES : MP3MI_ERR_ARG;
-    }
+    host_mem<mp3mi_tables> Th(1);
+    const int trc = tables_into(Th, ri);
+    if (trc != MP3MI_OK) return trc;
     const int C = channels;
     bool legal = true;
     for (int s = 0; legal && s < n_streams; s++) {
@@ -143,58 +136,45 @@ extern "C" int mp3mi_debug_format_frames(int rate_hz, int channels, int kbps, in
                 for (int ch = 0; legal && ch < C; ch++) {
                     for (int b = 0; b < 4; b++) legal = legal && !(sd->scfsi[ch][b] & ~1);
                     const int16_t *q = ix + (((size_t) s * 2 * n_frames + (2 * f + gr)) * C + ch) * 576;
-                    legal = legal && fd_check_granule(Th, &sd->gr[gr][ch], sd->scfsi[ch], gr, q);
+                    legal = legal && fd_check_granule(Th.p, &sd->gr[gr][ch], sd->scfsi[ch], gr, q);
                     bits += sd->gr[gr][ch].part2_3_length;
                 }
             legal = legal && bits % 8 == 0 && bits <= FD_IMAGE_BITS && bits / 8 <= mdb + slot; // (data never passes its own slot's end)
             mdb += slot - bits / 8;
         }
     }
-    if (!legal) {
-        free(Th);
-        return MP3MI_ERR_ARG;
+    if (!legal) return MP3MI_ERR_ARG;
+    const size_t S = (size_t) n_streams, nf = (size_t) n_frames, n_ix = S * nf * 2 * C * 576;
+    host_mem<int32_t> par(4 * S); // bits_per_frame, bitrate_index, n_samples, status: [4][S]
+    if (!par.p) return MP3MI_ERR_NOMEM;
+    for (size_t s = 0; s < S; s++) {
+        par.p[s] = 8 * frame_bytes;
+        par.p[S + s] = bi;
+        par.p[2 * S + s] = n_frames_s[s] * 1152;
     }
-    const size_t S = (size_t) n_streams, nf = (size_t) n_frames;
-    mp3mi_tables *dT = NULL;
-    int16_t *dix = NULL;
-    mp3mi_frame_side *dside = NULL;
-    int32_t *dpar = NULL; // bits_per_frame, bitrate_index, n_samples, status: [4][S]
-    uint8_t *dout = NULL;
-    uint32_t *dlen = NULL;
-    int32_t *par = (int32_t *) calloc(4 * S, sizeof(int32_t));
-    int rc = par ? MP3MI_ERR_HIP : MP3MI_ERR_NOMEM;
-    for (size_t s = 0; par && s < S; s++) {
-        par[s] = 8 * frame_bytes;
-        par[S + s] = bi;
-        par[2 * S + s] = n_frames_s[s] * 1152;
+    hook_bufs D;
+    const mp3mi_tables *dT = D.copy_of(Th.p, 1);
+    int32_t *dpar = D.copy_of(par.p, 4 * S);
+    uint8_t *dout = D.zeros<uint8_t>(S * out_stride);
+    uint32_t *dlen = D.zeros<uint32_t>(S);
+    // (a sample and a record more than the frames hold, not initialised; a chain of no frames uploads nothing)
+    int16_t *dix = D.raw<int16_t>(n_ix + 1);
+    mp3mi_frame_side *dside = D.raw<mp3mi_frame_side>(S * nf + 1);
+    if (nf) {
+        D.put(dix, ix, n_ix);
+        D.put(dside, side, S * nf);
     }
-    if (par && hipMalloc((void **) &dT, sizeof(mp3mi_tables)) == hipSuccess && hipMalloc((void **) &dix, (S * nf * 2 * C * 576 + 1) * 2) == hipSuccess &&
-        hipMalloc((void **) &dside, (S * nf + 1) * sizeof(mp3mi_frame_side)) == hipSuccess && hipMalloc((void **) &dpar, 4 * S * 4) == hipSuccess &&
-        hipMalloc((void **) &dout, S * out_stride) == hipSuccess && hipMalloc((void **) &dlen, S * 4) == hipSuccess &&
-        hipMemcpy(dT, Th, sizeof(mp3mi_tables), hipMemcpyHostToDevice) == hipSuccess &&
-        hipMemcpy(dpar, par, 4 * S * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemset(dout, 0, S * out_stride) == hipSuccess &&
-        hipMemset(dlen, 0, S * 4) == hipSuccess &&
-        (nf == 0 || (hipMemcpy(dix, ix, S * nf * 2 * C * 576 * 2, hipMemcpyHostToDevice) == hipSuccess &&
-                     hipMemcpy(dside, side, S * nf * sizeof(mp3mi_frame_side), hipMemcpyHostToDevice) == hipSuccess))) {
-        // the whole-file geometry of a batch call (batch.cpp); a stream of no frames has no file body
-        mp3mi_geom g = mp3mi_make_geom(n_streams, C, ri, n_frames, 0, n_frames > 0 ? n_frames : 1);
-        g.hdr_mode = hdr_mode;
-        g.hdr_flags = hdr_flags;
-        g.crc = crc;
-        g.n_samples = dpar + 2 * S;
-        mp3mi_launch_format(dT, g, dix, dside, dpar, dpar + S, dout, out_stride, dlen, dpar + 3 * S, 1, (unsigned *) NULL, 0);
-        if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(out_len, dlen, S * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-            hipMemcpy(status, dpar + 3 * S, S * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-            (nf == 0 || hipMemcpy(out, dout, S * out_stride, hipMemcpyDeviceToHost) == hipSuccess))
-            rc = MP3MI_OK;
-    }
-    if (dT) hipFree(dT);
-    if (dix) hipFree(dix);
-    if (dside) hipFree(dside);
-    if (dpar) hipFree(dpar);
-    if (dout) hipFree(dout);
-    if (dlen) hipFree(dlen);
-    free(par);
-    free(Th);
-    return rc;
+    if (!D.ok) return D.rc();
+    // the whole-file geometry of a batch call (batch.cpp); a stream of no frames has no file body
+    mp3mi_geom g = mp3mi_make_geom(n_streams, C, ri, n_frames, 0, n_frames > 0 ? n_frames : 1);
+    g.hdr_mode = hdr_mode;
+    g.hdr_flags = hdr_flags;
+    g.crc = crc;
+    g.n_samples = dpar + 2 * S;
+    mp3mi_launch_format(dT, g, dix, dside, dpar, dpar + S, dout, out_stride, dlen, dpar + 3 * S, 1, (unsigned *) NULL, 0);
+    D.sync();
+    D.fetch(out_len, dlen, S);
+    D.fetch(status, dpar + 3 * S, S);
+    if (nf) D.fetch(out, dout, S * out_stride);
+    return D.rc();
 }

@@ -1658,6 +1658,7 @@ void mp3mi_launch_hold_release(unsigned *flag, unsigned ticket, hipStream_t st)
 ULP_CENSUS_ACCESSOR(mp3mi_debug_ulp_census_loop)
 
 #else // MP3MI_LOOP_PASS_ONLY
+#include "host_util.h" // (the hooks' host side; in this region only: k_loop's own translation unit never sees it)
 // ---- self-test hook: one quantise+count pass of k_loop on given granules (include/mp3mi.h, mp3mi_debug_quantize_count) ----
 // A wavefront per granule runs what a pass of loop_stream runs, with these functions, in this order: loop_power34, a rescale
 // plan, loop_all_zero, loop_quantize (first tier and rare tier as in the product) and loop_count_bits.  The two rescale blocks
@@ -1808,9 +1809,8 @@ __global__ void __launch_bounds__(64) k_debug_quantize_count(const mp3mi_tables 
 extern "C" int mp3mi_debug_quantize_count(int rate_hz, int n_gran, const double *xr, const int32_t *gran, int16_t *ix,
                                           double *xr_out, int32_t *fields)
 {
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return MP3MI_ERR_NO_DEVICE;
-    const int ri = rate_hz == 44100 ? 0 : (rate_hz == 48000 ? 1 : (rate_hz == 32000 ? 2 : -1));
+    if (!have_device()) return MP3MI_ERR_NO_DEVICE;
+    const int ri = rate_idx_of(rate_hz);
     if (ri < 0 || n_gran < 0 || (n_gran > 0 && (!xr || !gran || !ix || !xr_out || !fields))) return MP3MI_ERR_ARG;
     for (int i = 0; i < n_gran; i++) {
         const int32_t *p = gran + 4 * i;
@@ -1819,40 +1819,24 @@ extern "C" int mp3mi_debug_quantize_count(int rate_hz, int n_gran, const double 
             return MP3MI_ERR_ARG;
     }
     if (n_gran == 0) return MP3MI_OK;
-    mp3mi_tables *Th = (mp3mi_tables *) malloc(sizeof(mp3mi_tables));
-    if (!Th) return MP3MI_ERR_NOMEM;
-    const int trc = mp3mi_build_tables(Th, ri);
-    if (trc != 0) {
-        free(Th);
-        return trc == -8 ? MP3MI_ERR_TABLES : MP3MI_ERR_ARG;
-    }
+    host_mem<mp3mi_tables> Th(1);
+    const int trc = tables_into(Th, ri);
+    if (trc != MP3MI_OK) return trc;
     const size_t n = (size_t) n_gran;
-    mp3mi_tables *dT = NULL;
-    double *dxr = NULL, *dxo = NULL;
-    loop_qc_gran *dg = NULL;
-    int16_t *dix = NULL;
-    int32_t *df = NULL;
-    int rc = MP3MI_ERR_HIP;
-    if (hipMalloc((void **) &dT, sizeof(mp3mi_tables)) == hipSuccess && hipMalloc((void **) &dxr, n * 576 * 8) == hipSuccess &&
-        hipMalloc((void **) &dxo, n * 576 * 8) == hipSuccess && hipMalloc((void **) &dg, n * sizeof(loop_qc_gran)) == hipSuccess &&
-        hipMalloc((void **) &dix, n * 576 * 2) == hipSuccess && hipMalloc((void **) &df, n * MP3MI_QC_FIELDS * 4) == hipSuccess &&
-        hipMemcpy(dT, Th, sizeof(mp3mi_tables), hipMemcpyHostToDevice) == hipSuccess &&
-        hipMemcpy(dxr, xr, n * 576 * 8, hipMemcpyHostToDevice) == hipSuccess &&
-        hipMemcpy(dg, gran, n * sizeof(loop_qc_gran), hipMemcpyHostToDevice) == hipSuccess) {
-        hipLaunchKernelGGL(k_debug_quantize_count, dim3((unsigned) n), dim3(64), 0, 0, dT, dxr, dg, dix, dxo, df);
-        if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(ix, dix, n * 576 * 2, hipMemcpyDeviceToHost) == hipSuccess &&
-            hipMemcpy(xr_out, dxo, n * 576 * 8, hipMemcpyDeviceToHost) == hipSuccess &&
-            hipMemcpy(fields, df, n * MP3MI_QC_FIELDS * 4, hipMemcpyDeviceToHost) == hipSuccess)
-            rc = MP3MI_OK;
-    }
-    if (dT) hipFree(dT);
-    if (dxr) hipFree(dxr);
-    if (dxo) hipFree(dxo);
-    if (dg) hipFree(dg);
-    if (dix) hipFree(dix);
-    if (df) hipFree(df);
-    free(Th);
-    return rc;
+    hook_bufs D;
+    const mp3mi_tables *dT = D.copy_of(Th.p, 1);
+    const double *dxr = D.copy_of(xr, n * 576);
+    double *dxo = D.raw<double>(n * 576);
+    const loop_qc_gran *dg = D.copy_of((const loop_qc_gran *) gran, n);
+    int16_t *dix = D.raw<int16_t>(n * 576);
+    int32_t *df = D.raw<int32_t>(n * MP3MI_QC_FIELDS);
+    if (!D.ok) return D.rc();
+    hipLaunchKernelGGL(k_debug_quantize_count, dim3((unsigned) n), dim3(64), 0, 0, dT, dxr, dg, dix, dxo, df);
+    D.sync();
+    D.fetch(ix, dix, n * 576);
+    D.fetch(xr_out, dxo, n * 576);
+    D.fetch(fields, df, n * MP3MI_QC_FIELDS);
+    return D.rc();
 }
 
 // ---- self-test hook: the peak lines k_mdct's tail would record for given granules, and the cells they are the peaks of ----
@@ -1870,17 +1854,13 @@ __global__ void __launch_bounds__(64) k_debug_peak_lines(const mp3mi_tables *__r
 
 extern "C" int mp3mi_debug_peak_lines(int rate_hz, int n_gran, const double *xr, uint16_t *peak, int32_t *cell_first)
 {
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return MP3MI_ERR_NO_DEVICE;
-    const int ri = rate_hz == 44100 ? 0 : (rate_hz == 48000 ? 1 : (rate_hz == 32000 ? 2 : -1));
+    if (!have_device()) return MP3MI_ERR_NO_DEVICE;
+    const int ri = rate_idx_of(rate_hz);
     if (ri < 0 || n_gran < 0 || !cell_first || (n_gran > 0 && (!xr || !peak))) return MP3MI_ERR_ARG;
-    mp3mi_tables *Th = (mp3mi_tables *) malloc(sizeof(mp3mi_tables));
-    if (!Th) return MP3MI_ERR_NOMEM;
-    const int trc = mp3mi_build_tables(Th, ri);
-    if (trc != 0) {
-        free(Th);
-        return trc == -8 ? MP3MI_ERR_TABLES : MP3MI_ERR_ARG;
-    }
+    host_mem<mp3mi_tables> Th_h(1);
+    const int trc = tables_into(Th_h, ri);
+    if (trc != MP3MI_OK) return trc;
+    const mp3mi_tables *Th = Th_h.p;
     for (int c = 0; c <= MP3MI_PEAK_CELLS; c++) { // (the cells as the kernels cut them; entry MP3MI_PEAK_CELLS closes the last cell)
         int first = 576, lines = 0, cells = 0;
         for (int b = 0; b < 22; b++) {
@@ -1891,21 +1871,15 @@ extern "C" int mp3mi_debug_peak_lines(int rate_hz, int n_gran, const double *xr,
         cell_first[c] = first;
     }
     const size_t n = (size_t) n_gran;
-    mp3mi_tables *dT = NULL;
-    double *dxr = NULL;
-    uint16_t *dpk = NULL;
-    int rc = n ? MP3MI_ERR_HIP : MP3MI_OK;
-    if (n && hipMalloc((void **) &dT, sizeof(mp3mi_tables)) == hipSuccess && hipMalloc((void **) &dxr, n * 576 * 8) == hipSuccess &&
-        hipMalloc((void **) &dpk, n * MP3MI_PEAK_CELLS * 2) == hipSuccess &&
-        hipMemcpy(dT, Th, sizeof(mp3mi_tables), hipMemcpyHostToDevice) == hipSuccess &&
-        hipMemcpy(dxr, xr, n * 576 * 8, hipMemcpyHostToDevice) == hipSuccess) {
-        hipLaunchKernelGGL(k_debug_peak_lines, dim3((unsigned) n), dim3(64), 0, 0, dT, dxr, dpk);
-        if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(peak, dpk, n * MP3MI_PEAK_CELLS * 2, hipMemcpyDeviceToHost) == hipSuccess) rc = MP3MI_OK;
-    }
-    if (dT) hipFree(dT);
-    if (dxr) hipFree(dxr);
-    if (dpk) hipFree(dpk);
-    free(Th);
-    return rc;
+    if (n == 0) return MP3MI_OK;
+    hook_bufs D;
+    const mp3mi_tables *dT = D.copy_of(Th, 1);
+    const double *dxr = D.copy_of(xr, n * 576);
+    uint16_t *dpk = D.raw<uint16_t>(n * MP3MI_PEAK_CELLS);
+    if (!D.ok) return D.rc();
+    hipLaunchKernelGGL(k_debug_peak_lines, dim3((unsigned) n), dim3(64), 0, 0, dT, dxr, dpk);
+    D.sync();
+    D.fetch(peak, dpk, n * MP3MI_PEAK_CELLS);
+    return D.rc();
 }
 #endif // MP3MI_LOOP_PASS_ONLY

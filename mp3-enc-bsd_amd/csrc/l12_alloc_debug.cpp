@@ -29,13 +29,9 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include "host_util.h"
-#include "l12_dev.h"
+#include "l12_host.h"
 #include "mp3mi_l12.h"
 
-static const int LA_BITRATES[2][15] = { /* src/common.c:122-123 */
-    {0, 32, 64, 96, 128, 160, 192, 224, 256, 288, 320, 352, 384, 416, 448},
-    {0, 32, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256, 320, 384}};
 static const double LA_SAMPLE_MAX = 2.0; // multiple[0]
 
 extern "C" int mp3mi_debug_l12_alloc(int layer, int rate_hz, int channels, int mode, int crc, int hdr_flags, int slot0, int n_streams,
@@ -44,42 +40,27 @@ extern "C" int mp3mi_debug_l12_alloc(int layer, int rate_hz, int channels, int m
 {
     static_assert(sizeof(mp3mi_l12_frame_seams) == sizeof(l12_frame_dbg), "seam record of mp3mi_l12.h and l12_dev.h");
     if (!have_device()) return MP3MI_ERR_NO_DEVICE;
-    const int ri = rate_hz == 44100 ? 0 : (rate_hz == 48000 ? 1 : (rate_hz == 32000 ? 2 : -1));
+    const int ri = rate_idx_of(rate_hz);
     if ((layer != 1 && layer != 2) || ri < 0 || (channels != 1 && channels != 2) || mode < 0 || mode > 3 ||
         (channels == 1) != (mode == MP3MI_MODE_MONO) || (crc & ~1) || (hdr_flags & ~15) || slot0 < 0 || slot0 > 17 || n_streams <= 0 ||
         n_streams > 4096 || n_frames <= 0 || n_frames > 64 || !kbps || !sb || !ratio || !out || !out_len || !seams)
         return MP3MI_ERR_ARG;
     const size_t S = (size_t) n_streams, nf = (size_t) n_frames, C = (size_t) channels;
-    const int parts = layer == 1 ? 1 : 3, nslot = 12 * parts, spf = 32 * nslot, lb = layer == 1 ? 3 : 2;
+    const int parts = layer == 1 ? 1 : 3, nslot = 12 * parts, spf = l12_samples_per_frame(layer), lb = layer == 1 ? 3 : 2;
     const size_t n_sb = S * nf * C * (size_t) parts * 12 * 32, n_ratio = S * nf * (size_t) layer * C * 32;
     for (size_t i = 0; i < n_sb; i++)
         if (!(fabs(sb[i]) <= LA_SAMPLE_MAX)) return MP3MI_ERR_ARG; // (also catches NaN and the infinities)
     for (size_t i = 0; i < n_ratio; i++)
         if (!(fabsf(ratio[i]) <= 3.402823466e38f)) return MP3MI_ERR_ARG;
-    l12_stream_cfg *cfg_h = (l12_stream_cfg *) calloc(S, sizeof(l12_stream_cfg));
-    if (!cfg_h) return MP3MI_ERR_NOMEM;
-    int max_frame_bytes = 0;
-    for (size_t s = 0; s < S; s++) { // as mp3mi_l12_batch_create sets a stream up
-        int bi = 1;
-        while (bi < 15 && LA_BITRATES[layer - 1][bi] != kbps[s]) bi++;
-        if (bi == 15) { free(cfg_h); return MP3MI_ERR_ARG; }
-        l12_stream_cfg &c = cfg_h[s];
-        c.bitrate_index = bi;
-        c.frame_bits = frame_bits(spf, ri, kbps[s], layer == 1 ? 32 : 8);
-        if (layer == 2) { // pick_table, src/common.c:291-318
-            const int br_per_ch = kbps[s] / channels, sfrq = rate_hz / 1000;
-            if ((sfrq == 48 && br_per_ch >= 56) || (br_per_ch >= 56 && br_per_ch <= 80)) c.table = 0;
-            else if (sfrq != 48 && br_per_ch >= 96) c.table = 1;
-            else if (sfrq != 32 && br_per_ch <= 48) c.table = 2;
-            else c.table = 3;
-            static const int SBL[4] = {27, 30, 8, 12};
-            c.sblimit = SBL[c.table];
-        } else { c.table = 0; c.sblimit = 32; }
-        int fb = c.frame_bits / 8;
-        if (layer == 1 && channels == 2 && fb < 38) fb = 38; // (the frame that outgrows its slot, k_l12.hip)
+    host_mem<l12_stream_cfg> cfg_h(S);
+    if (!cfg_h.p) return MP3MI_ERR_NOMEM;
+    size_t max_frame_bytes = 0;
+    for (size_t s = 0; s < S; s++) { // as mp3mi_l12_batch_create sets a stream up: the same two functions
+        if (!l12_stream_cfg_of(layer, rate_hz, ri, channels, kbps[s], &cfg_h.p[s])) return MP3MI_ERR_ARG;
+        const size_t fb = l12_row_frame_bytes(layer, channels, cfg_h.p[s].frame_bits);
         if (fb > max_frame_bytes) max_frame_bytes = fb;
     }
-    if (out_stride < nf * (size_t) max_frame_bytes + 1) { free(cfg_h); return MP3MI_ERR_ARG; }
+    if (out_stride < nf * max_frame_bytes + 1) return MP3MI_ERR_ARG;
 
     l12_geom g;
     memset(&g, 0, sizeof(g));
@@ -93,67 +74,42 @@ extern "C" int mp3mi_debug_l12_alloc(int layer, int rate_hz, int channels, int m
     g.whole_file = 1; // (the last frame's wavefront adds the file's last byte)
 
     const size_t n_sbs = S * G1 * C * 576, n_snr = S * (size_t) g.np * C * 32;
-    double *sbs_h = (double *) calloc(n_sbs, sizeof(double));
-    float *snr_h = (float *) calloc(n_snr, sizeof(float));
-    mp3mi_tables_l12 *Th = (mp3mi_tables_l12 *) malloc(sizeof(mp3mi_tables_l12));
-    int rc = MP3MI_ERR_NOMEM;
-    mp3mi_tables_l12 *dT = NULL;
-    l12_stream_cfg *dcfg = NULL;
-    double *dsbs = NULL;
-    float *dsnr = NULL;
-    uint8_t *dout = NULL;
-    uint32_t *dlen = NULL;
-    l12_frame_dbg *ddbg = NULL;
-    if (sbs_h && snr_h && Th) {
-        const int trc = mp3mi_build_tables_l12(Th, ri, layer);
-        rc = trc == 0 ? MP3MI_OK : (trc == -8 ? MP3MI_ERR_TABLES : MP3MI_ERR_ARG);
-        for (size_t s = 0; rc == MP3MI_OK && s < S; s++)
-            if (layer == 2 && cfg_h[s].sblimit != Th->sblimit[cfg_h[s].table]) rc = MP3MI_ERR_TABLES;
-    }
-    if (rc == MP3MI_OK) {
-        // k_filter's layout: [stream][granule][channel][slot of 18][subband], odd slots of odd subbands negated (src/mdct.c:57-60)
-        for (size_t s = 0; s < S; s++)
-            for (size_t f = 0; f < nf; f++)
-                for (size_t ch = 0; ch < C; ch++)
-                    for (int u = 0; u < nslot; u++) {
-                        const size_t sg = (size_t) slot0 + f * (size_t) nslot + (size_t) u, gi = sg / 18, qq = sg % 18;
-                        const double *src = sb + ((((s * nf + f) * C + ch) * (size_t) parts + (size_t) (u / 12)) * 12 + (size_t) (u % 12)) * 32;
-                        double *dst = sbs_h + ((s * G1 + gi) * C + ch) * 576 + qq * 32;
-                        for (int i = 0; i < 32; i++) dst[i] = ((i & 1) && (qq & 1)) ? -src[i] : src[i];
-                    }
-        // k12_psy's records: [stream][pass][channel][32], the chunk's passes behind the lb recomputed ones
-        for (size_t s = 0; s < S; s++)
-            for (size_t q = 0; q < nf * (size_t) layer; q++)
-                memcpy(snr_h + ((s * (size_t) g.np + (size_t) lb + q) * C) * 32, ratio + ((s * nf * (size_t) layer + q) * C) * 32, C * 32 * sizeof(float));
-        rc = MP3MI_ERR_HIP;
-        if (hipMalloc((void **) &dT, sizeof(mp3mi_tables_l12)) == hipSuccess && hipMalloc((void **) &dcfg, S * sizeof(l12_stream_cfg)) == hipSuccess &&
-            hipMalloc((void **) &dsbs, n_sbs * sizeof(double)) == hipSuccess && hipMalloc((void **) &dsnr, n_snr * sizeof(float)) == hipSuccess &&
-            hipMalloc((void **) &dout, S * out_stride) == hipSuccess && hipMalloc((void **) &dlen, S * sizeof(uint32_t)) == hipSuccess &&
-            hipMalloc((void **) &ddbg, S * nf * sizeof(l12_frame_dbg)) == hipSuccess &&
-            hipMemcpy(dT, Th, sizeof(mp3mi_tables_l12), hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(dcfg, cfg_h, S * sizeof(l12_stream_cfg), hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(dsbs, sbs_h, n_sbs * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(dsnr, snr_h, n_snr * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemset(dout, 0, S * out_stride) == hipSuccess && hipMemset(dlen, 0, S * sizeof(uint32_t)) == hipSuccess &&
-            hipMemset(ddbg, 0, S * nf * sizeof(l12_frame_dbg)) == hipSuccess) {
-            mp3mi_launch_l12_alloc(dT, g, dcfg, dsbs, dsnr, dout, out_stride, dlen, ddbg, 0);
-            if (hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
-                hipMemcpy(out, dout, S * out_stride, hipMemcpyDeviceToHost) == hipSuccess &&
-                hipMemcpy(out_len, dlen, S * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess &&
-                hipMemcpy(seams, ddbg, S * nf * sizeof(l12_frame_dbg), hipMemcpyDeviceToHost) == hipSuccess)
-                rc = MP3MI_OK;
-        }
-    }
-    if (dT) hipFree(dT);
-    if (dcfg) hipFree(dcfg);
-    if (dsbs) hipFree(dsbs);
-    if (dsnr) hipFree(dsnr);
-    if (dout) hipFree(dout);
-    if (dlen) hipFree(dlen);
-    if (ddbg) hipFree(ddbg);
-    free(Th);
-    free(snr_h);
-    free(sbs_h);
-    free(cfg_h);
-    return rc;
+    host_mem<double> sbs_h(n_sbs);
+    host_mem<float> snr_h(n_snr);
+    host_mem<mp3mi_tables_l12> Th(1);
+    if (!sbs_h.p || !snr_h.p || !Th.p) return MP3MI_ERR_NOMEM;
+    int rc = tables_rc(mp3mi_build_tables_l12(Th.p, ri, layer));
+    for (size_t s = 0; rc == MP3MI_OK && s < S; s++)
+        if (layer == 2 && cfg_h.p[s].sblimit != Th.p->sblimit[cfg_h.p[s].table]) rc = MP3MI_ERR_TABLES;
+    if (rc != MP3MI_OK) return rc;
+    // k_filter's layout: [stream][granule][channel][slot of 18][subband], odd slots of odd subbands negated (src/mdct.c:57-60)
+    for (size_t s = 0; s < S; s++)
+        for (size_t f = 0; f < nf; f++)
+            for (size_t ch = 0; ch < C; ch++)
+                for (int u = 0; u < nslot; u++) {
+                    const size_t sg = (size_t) slot0 + f * (size_t) nslot + (size_t) u, gi = sg / 18, qq = sg % 18;
+                    const double *src = sb + ((((s * nf + f) * C + ch) * (size_t) parts + (size_t) (u / 12)) * 12 + (size_t) (u % 12)) * 32;
+                    double *dst = sbs_h.p + ((s * G1 + gi) * C + ch) * 576 + qq * 32;
+                    for (int i = 0; i < 32; i++) dst[i] = ((i & 1) && (qq & 1)) ? -src[i] : src[i];
+                }
+    // k12_psy's records: [stream][pass][channel][32], the chunk's passes behind the lb recomputed ones
+    for (size_t s = 0; s < S; s++)
+        for (size_t q = 0; q < nf * (size_t) layer; q++)
+            memcpy(snr_h.p + ((s * (size_t) g.np + (size_t) lb + q) * C) * 32, ratio + ((s * nf * (size_t) layer + q) * C) * 32, C * 32 * sizeof(float));
+    hook_bufs D;
+    const mp3mi_tables_l12 *dT = D.copy_of(Th.p, 1);
+    const l12_stream_cfg *dcfg = D.copy_of(cfg_h.p, S);
+    const double *dsbs = D.copy_of(sbs_h.p, n_sbs);
+    const float *dsnr = D.copy_of(snr_h.p, n_snr);
+    uint8_t *dout = D.zeros<uint8_t>(S * out_stride);
+    uint32_t *dlen = D.zeros<uint32_t>(S);
+    l12_frame_dbg *ddbg = D.zeros<l12_frame_dbg>(S * nf);
+    if (!D.ok) return D.rc();
+    mp3mi_launch_l12_alloc(dT, g, dcfg, dsbs, dsnr, dout, out_stride, dlen, ddbg, 0);
+    D.ok = hipGetLastError() == hipSuccess;
+    D.sync();
+    D.fetch(out, dout, S * out_stride);
+    D.fetch(out_len, dlen, S);
+    D.fetch((l12_frame_dbg *) seams, ddbg, S * nf);
+    return D.rc();
 }

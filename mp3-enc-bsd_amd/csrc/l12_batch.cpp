@@ -10,13 +10,8 @@
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
-#include "host_util.h"
-#include "l12_dev.h"
+#include "l12_host.h"
 #include "mp3mi_l12.h"
-
-static const int L12_BITRATES[2][15] = { /* src/common.c:122-123 */
-    {0, 32, 64, 96, 128, 160, 192, 224, 256, 288, 320, 352, 384, 416, 448},
-    {0, 32, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256, 320, 384}};
 
 struct mp3mi_l12_batch {
     int device;
@@ -25,7 +20,7 @@ struct mp3mi_l12_batch {
     int mode, crc, hdr_flags;
     unsigned test_flags;
     int debug;
-    int max_frame_bytes;
+    int max_frame_bytes;     // of the longest frame in an output row (l12_row_frame_bytes)
     std::vector<l12_stream_cfg> cfg_h;
     hipStream_t stream;
     hipEvent_t ev0, ev1;
@@ -46,12 +41,9 @@ struct mp3mi_l12_batch {
     // streaming: PCM history of the streams in progress, two copies taken in turn (k12_hist_save is out of place)
     int16_t *hist[2], *fb_hist[2];
     int hist_cur;
-    long fabs0;              // frames every stream has been given by mp3mi_l12_batch_encode_next since the last reset
-    // per-slot streaming (mp3mi_l12_batch_encode_slots): a stream index is a SLOT through which one stream after another passes.
-    // While slots_on is false the slots are as fabs0 says (all open at fabs0 when it is > 0, else all closed) and every call runs
-    // as it always did; the first per-slot call sets slots_on, and the slots are as slot_frames_h says (l12_slots_settle hands back).
-    bool slots_on;
-    std::vector<int64_t> slot_frames_h; // frames encoded by the stream open in each slot, -1: no stream open there
+    // where the streams are: the whole-batch counter of mp3mi_l12_batch_encode_next (book.frames_all: frames every stream has been
+    // given since the last reset) and the slots of mp3mi_l12_batch_encode_slots (host_util.h)
+    slot_book book;
     // the control block of a per-slot call (l12_ctl_block), twice, taken in turn: calls are issued back to back, and an entry's
     // fence is recorded behind the last kernel that reads its device copy -- the host waits for it before it writes the staging
     // again (the per-slot call two before).  Created with the first per-slot call: a batch that never makes one holds none of it.
@@ -95,11 +87,8 @@ extern "C" int mp3mi_l12_batch_create(mp3mi_l12_batch **out, int layer, int n_st
     if (!out) return MP3MI_ERR_ARG;
     *out = NULL;
     if ((layer != 1 && layer != 2) || n_streams < 1 || max_frames < 1 || (channels != 1 && channels != 2)) return MP3MI_ERR_ARG;
-    int ri;
-    if (rate_hz == 44100) ri = 0;
-    else if (rate_hz == 48000) ri = 1;
-    else if (rate_hz == 32000) ri = 2;
-    else return MP3MI_ERR_ARG; // (MPEG-2 LSF rates: psycho_anal exits on them, src/psy.c:131-136)
+    const int ri = rate_idx_of(rate_hz);
+    if (ri < 0) return MP3MI_ERR_ARG;
     if (!have_device()) {
         fprintf(stderr, "mp3mi: no usable HIP device -- this library has no CPU fallback\n");
         return MP3MI_ERR_NO_DEVICE;
@@ -108,7 +97,7 @@ extern "C" int mp3mi_l12_batch_create(mp3mi_l12_batch **out, int layer, int n_st
     memset((void *) &b->stream, 0, sizeof(b->stream));
     b->layer = layer; b->n_streams = n_streams; b->rate_idx = ri; b->rate_hz = rate_hz; b->channels = channels;
     b->max_frames = max_frames;
-    b->spf = layer == 1 ? 384 : 1152; b->spp = layer == 1 ? 384 : 576; b->span = layer == 1 ? 1024 : 1056;
+    b->spf = l12_samples_per_frame(layer); b->spp = layer == 1 ? 384 : 576; b->span = layer == 1 ? 1024 : 1056;
     b->lb = layer == 1 ? 3 : 2;
     b->mode = channels == 1 ? MP3MI_MODE_MONO : MP3MI_MODE_STEREO;
     b->crc = 0; b->hdr_flags = 0; b->test_flags = 0; b->debug = 0;
@@ -116,32 +105,17 @@ extern "C" int mp3mi_l12_batch_create(mp3mi_l12_batch **out, int layer, int n_st
     for (int i = 0; i < 4; i++) { b->kernel_ms[i] = 0.0; b->kernel_launches[i] = 0; }
     b->ev0 = b->ev1 = 0; b->T3 = NULL; b->T = NULL; b->cfg = NULL;
     b->erp = b->snr = NULL; b->sbs = NULL; b->dbg = NULL; b->dbg_f0 = b->dbg_nf = 0;
-    b->hist[0] = b->hist[1] = b->fb_hist[0] = b->fb_hist[1] = NULL; b->hist_cur = 0; b->fabs0 = 0;
-    b->slots_on = false;
-    b->slot_frames_h.assign((size_t) n_streams, -1);
+    b->hist[0] = b->hist[1] = b->fb_hist[0] = b->fb_hist[1] = NULL; b->hist_cur = 0;
+    b->book.init(n_streams);
     memset((void *) &b->ctl, 0, sizeof(b->ctl));
     if (hipGetDevice(&b->device) != hipSuccess) { delete b; return MP3MI_ERR_HIP; }
     b->cfg_h.resize((size_t) n_streams);
     b->max_frame_bytes = 0;
     for (int s = 0; s < n_streams; s++) {
-        const int k = kbps ? kbps[s] : kbps_all;
-        int bi;
-        for (bi = 1; bi < 15; bi++)
-            if (L12_BITRATES[layer - 1][bi] == k) break;
-        if (bi == 15) { delete b; return MP3MI_ERR_ARG; }
         l12_stream_cfg &c = b->cfg_h[(size_t) s];
-        c.bitrate_index = bi;
-        c.frame_bits = frame_bits(b->spf, ri, k, layer == 1 ? 32 : 8);
-        if (layer == 2) { // pick_table, src/common.c:291-318
-            const int br_per_ch = k / channels, sfrq = rate_hz / 1000; // (int) s_freq: 44, 48, 32
-            if ((sfrq == 48 && br_per_ch >= 56) || (br_per_ch >= 56 && br_per_ch <= 80)) c.table = 0;
-            else if (sfrq != 48 && br_per_ch >= 96) c.table = 1;
-            else if (sfrq != 32 && br_per_ch <= 48) c.table = 2;
-            else c.table = 3;
-            static const int SBL[4] = {27, 30, 8, 12};
-            c.sblimit = SBL[c.table];
-        } else { c.table = 0; c.sblimit = 32; }
-        if (c.frame_bits / 8 > b->max_frame_bytes) b->max_frame_bytes = c.frame_bits / 8;
+        if (!l12_stream_cfg_of(layer, rate_hz, ri, channels, kbps ? kbps[s] : kbps_all, &c)) { delete b; return MP3MI_ERR_ARG; }
+        const int fb = (int) l12_row_frame_bytes(layer, channels, c.frame_bits);
+        if (fb > b->max_frame_bytes) b->max_frame_bytes = fb;
     }
     const size_t budget = (size_t) (scratch_mb ? scratch_mb : 32768u) << 20;
     // per stream the chunk's buffers also hold the lb warm-up passes and three extra filterbank granules, whatever its length
@@ -157,12 +131,9 @@ extern "C" int mp3mi_l12_batch_create(mp3mi_l12_batch **out, int layer, int n_st
         std::vector<char> t3_store(sizeof(mp3mi_tables)), t12_store(sizeof(mp3mi_tables_l12));
         mp3mi_tables *T3h = (mp3mi_tables *) t3_store.data();
         mp3mi_tables_l12 *T12h = (mp3mi_tables_l12 *) t12_store.data();
-        int trc = mp3mi_build_tables(T3h, ri);
-        if (trc == -8) return MP3MI_ERR_TABLES;
-        if (trc != 0) return MP3MI_ERR_ARG;
-        trc = mp3mi_build_tables_l12(T12h, ri, layer);
-        if (trc == -8) return MP3MI_ERR_TABLES;
-        if (trc != 0) return MP3MI_ERR_ARG;
+        int trc = tables_rc(mp3mi_build_tables(T3h, ri));
+        if (trc == MP3MI_OK) trc = tables_rc(mp3mi_build_tables_l12(T12h, ri, layer));
+        if (trc != MP3MI_OK) return trc;
         for (int s = 0; s < n_streams; s++)
             if (layer == 2 && b->cfg_h[(size_t) s].sblimit != T12h->sblimit[b->cfg_h[(size_t) s].table]) return MP3MI_ERR_TABLES;
         CHK(hipStreamCreate(&b->stream));
@@ -237,10 +208,7 @@ extern "C" int mp3mi_l12_batch_set_test_flags(mp3mi_l12_batch *b, unsigned flags
 extern "C" size_t mp3mi_l12_batch_out_stride(const mp3mi_l12_batch *b, int n_frames)
 {
     if (!b || n_frames < 0) return 0;
-    // (two-channel Layer I below its fields' size: the reference's frames outgrow their slots, k_l12.hip)
-    size_t fb = (size_t) b->max_frame_bytes;
-    if (b->layer == 1 && b->channels == 2 && fb < 38) fb = 38;
-    return ((size_t) n_frames * fb + 1 + 255) / 256 * 256;
+    return ((size_t) n_frames * (size_t) b->max_frame_bytes + 1 + 255) / 256 * 256;
 }
 extern "C" void mp3mi_l12_batch_debug_enable(mp3mi_l12_batch *b, int on) { if (b) b->debug = on != 0; }
 
@@ -276,31 +244,6 @@ static int l12_hist_ensure(mp3mi_l12_batch *b)
     return MP3MI_OK;
 }
 
-// ---- per-slot streaming: the bookkeeping (mp3mi_l12_batch::slots_on) ----
-// What every slot holds before a call: the frames of the stream open in it, -1 for none
-static void l12_slot_frames_now(const mp3mi_l12_batch *b, int64_t *f)
-{
-    for (int s = 0; s < b->n_streams; s++) f[s] = b->slots_on ? b->slot_frames_h[s] : (b->fabs0 > 0 ? (int64_t) b->fabs0 : -1);
-}
-// The per-slot bookkeeping is in force, with the slots as f says -- unless every slot is open at the same frame: then it hands over
-// to the whole-batch counter, and the next call runs exactly as if there had never been a per-slot call
-static void l12_slots_settle(mp3mi_l12_batch *b, const std::vector<int64_t> &f)
-{
-    b->slot_frames_h = f;
-    b->slots_on = true;
-    for (int s = 1; s < b->n_streams; s++)
-        if (f[(size_t) s] != f[0]) return;
-    if (f[0] > 0) {
-        b->slots_on = false;
-        b->fabs0 = (long) f[0];
-    }
-}
-// flush, reset and the whole-file call close every slot: the whole-batch counter again, at the start of new streams
-static void l12_slots_close(mp3mi_l12_batch *b)
-{
-    b->slots_on = false;
-    b->fabs0 = 0;
-}
 // The control block this call takes, its entry created with its first turn; the host waits for the per-slot call two before,
 // whose kernels read the device copy and whose upload read the staging it is about to write
 static int l12_ctl_take(mp3mi_l12_batch *b, mp3mi_l12_batch::ctl_ring::entry **blk)
@@ -349,8 +292,8 @@ static int l12_encode_impl(mp3mi_l12_batch *b, const int16_t *pcm_dev, const int
         g.actual_mode = b->mode; g.crc = b->crc; g.hdr_flags = b->hdr_flags; g.test_flags = (int) b->test_flags;
         g.n_samples = sc ? sc->dev.n_samples : n_samples_dev;
         g.whole_file = whole_file ? 1 : 0;
-        g.fabs0 = (whole_file || sc) ? 0 : b->fabs0;
-        g.hist = (!whole_file && b->fabs0 > 0) ? b->hist[b->hist_cur] : NULL; // (nothing precedes a stream's first call: zeros)
+        g.fabs0 = (whole_file || sc) ? 0 : b->book.frames_all;
+        g.hist = (!whole_file && b->book.frames_all > 0) ? b->hist[b->hist_cur] : NULL; // (nothing precedes a stream's first call: zeros)
         if (sc) { // every slot has its own position, and always a history: k12_slot_begin has zeroed the rows of the streams that begin
             g.fabs_s = sc->dev.fabs;
             g.slot_ctl = sc->dev.ctl;
@@ -386,15 +329,15 @@ static int l12_encode_impl(mp3mi_l12_batch *b, const int16_t *pcm_dev, const int
         memset(&g, 0, sizeof(g));
         g.n_streams = S; g.channels = C; g.n_frames = n_frames; g.spf = b->spf;
         { const int rc = l12_hist_ensure(b); if (rc != MP3MI_OK) return rc; }
-        if (!sc && b->fabs0 == 0) { // a stream's first call: what precedes it is silence (the reference's zero-filled buffers)
+        if (!sc && b->book.frames_all == 0) { // a stream's first call: what precedes it is silence (the reference's zero-filled buffers)
             CHK(hipMemsetAsync(b->hist[b->hist_cur], 0, sizeof(int16_t) * L12_PCM_HIST * (size_t) C * (size_t) S, b->stream));
             CHK(hipMemsetAsync(b->fb_hist[b->hist_cur], 0, sizeof(int16_t) * MP3MI_PCM_HIST * (size_t) C * (size_t) S, b->stream));
         }
         mp3mi_launch_l12_hist_save(g, pcm_dev, b->hist[b->hist_cur], b->hist[b->hist_cur ^ 1], b->fb_hist[b->hist_cur], b->fb_hist[b->hist_cur ^ 1], b->stream);
         b->hist_cur ^= 1;
         if (sc) CHK(sc->blk->free.record(b->stream)); // behind the last reader of the control block
-        else b->fabs0 += n_frames;                    // (a per-slot call: l12_slots_impl keeps the slots' frames)
-    } else l12_slots_close(b);
+        else b->book.frames_all += n_frames;          // (a per-slot call: l12_slots_impl keeps the slots' frames)
+    } else b->book.close();
     CHK(hipEventRecord(b->ev1, b->stream));
     b->kev_chunks = chunk;
     b->timing_open = true;
@@ -410,57 +353,27 @@ extern "C" int mp3mi_l12_batch_encode(mp3mi_l12_batch *b, const int16_t *pcm_dev
 }
 
 // ---- per-slot streaming (mp3mi_l12_batch_encode_slots) ----
-// The rules of a per-slot call, slot by slot (f: l12_slot_frames_now)
-static bool l12_slots_rules_ok(const mp3mi_l12_batch *b, const int64_t *f, int n_frames, const uint8_t *ctl_host, const int32_t *n_samples_host)
-{
-    const int32_t full = (int32_t) n_frames * b->spf;
-    for (int s = 0; s < b->n_streams; s++) {
-        const int c = ctl_host[s];
-        if (c & ~(MP3MI_SLOT_START | MP3MI_SLOT_END)) return false;
-        const bool open = f[s] >= 0, start = c & MP3MI_SLOT_START, end = c & MP3MI_SLOT_END, part = open || start;
-        if (end && !part) return false;
-        const int32_t n = n_samples_host ? n_samples_host[s] : (part ? full : 0);
-        if (!part ? n != 0 : (!end ? n != full : (n < 0 || n > full))) return false;
-    }
-    return true;
-}
-
 static int l12_slots_impl(mp3mi_l12_batch *b, const int16_t *pcm_dev, int n_frames, const uint8_t *ctl_host, const int32_t *n_samples_host,
                           uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev)
 {
     if (!b || !pcm_dev || !ctl_host || !out_dev || !out_len_dev || n_frames < 1 || n_frames > b->max_frames) return MP3MI_ERR_ARG;
     if (out_stride < mp3mi_l12_batch_out_stride(b, n_frames)) return MP3MI_ERR_ARG;
     const int S = b->n_streams;
-    const int32_t full = (int32_t) n_frames * b->spf;
     std::vector<int64_t> f((size_t) S);
-    l12_slot_frames_now(b, f.data());
+    b->book.now(f.data());
     // every rule first: a call that breaks one leaves the batch as it was
-    if (!l12_slots_rules_ok(b, f.data(), n_frames, ctl_host, n_samples_host)) return MP3MI_ERR_ARG;
+    if (!b->book.rules_ok(f.data(), n_frames, b->spf, ctl_host, n_samples_host)) return MP3MI_ERR_ARG;
     ON_DEVICE(b);
     l12_slot_call sc;
     if (l12_ctl_take(b, &sc.blk) != MP3MI_OK) return MP3MI_ERR_HIP;
     const l12_ctl_block st = l12_ctl_at(sc.blk->stage, S); // the staging copy: the caller's two arrays are copied here
     sc.dev = l12_ctl_at(sc.blk->dev, S);
-    sc.n_start = 0;
-    for (int s = 0; s < S; s++) {
-        const int c = ctl_host[s];
-        const bool open = f[(size_t) s] >= 0, start = c & MP3MI_SLOT_START, part = open || start;
-        st.fabs[s] = (start || !open) ? 0 : f[(size_t) s];
-        st.n_samples[s] = n_samples_host ? n_samples_host[s] : (part ? full : 0);
-        st.ctl[s] = (uint8_t) ((start ? MP3MI_SLOT_DEV_START : 0) | (c & MP3MI_SLOT_END ? MP3MI_SLOT_DEV_END : 0) | (part ? MP3MI_SLOT_DEV_ACTIVE : 0));
-        st.list[s] = 0;
-        if (start) st.list[sc.n_start++] = s;
-    }
+    sc.n_start = b->book.fill(f.data(), n_frames, b->spf, ctl_host, n_samples_host, st.fabs, st.n_samples, st.ctl, st.list);
     const int rc = l12_encode_impl(b, pcm_dev, NULL, n_frames, out_dev, out_stride, out_len_dev, false, &sc);
     if (rc != MP3MI_OK) return rc;
     b->ctl.next();
-    for (int s = 0; s < S; s++) {
-        const int c = ctl_host[s];
-        if (c & MP3MI_SLOT_START) f[(size_t) s] = 0;
-        if (c & MP3MI_SLOT_END) f[(size_t) s] = -1;
-        else if (f[(size_t) s] >= 0) f[(size_t) s] += n_frames;
-    }
-    l12_slots_settle(b, f);
+    b->book.advance(f.data(), ctl_host, n_frames);
+    b->book.settle(f.data());
     return MP3MI_OK;
 }
 
@@ -473,27 +386,23 @@ extern "C" int mp3mi_l12_batch_encode_slots(mp3mi_l12_batch *b, const int16_t *p
 extern "C" int mp3mi_l12_batch_slot_frames(const mp3mi_l12_batch *b, int64_t *frames_host)
 {
     if (!b || !frames_host) return MP3MI_ERR_ARG;
-    l12_slot_frames_now(b, frames_host);
-    int n = 0;
-    for (int s = 0; s < b->n_streams; s++) n += frames_host[s] >= 0;
-    return n;
+    b->book.now(frames_host);
+    return b->book.count_open();
 }
 
 extern "C" int mp3mi_l12_batch_encode_next(mp3mi_l12_batch *b, const int16_t *pcm_dev, int n_frames, uint8_t *out_dev, size_t out_stride,
                                            uint32_t *out_len_dev)
 {
-    if (b && b->slots_on) {
+    if (b && b->book.on) {
         // per-slot bookkeeping in force: with no stream open every slot starts (the whole-batch start); otherwise the open streams
         // go on and the other slots stay closed
-        bool any = false;
-        for (int s = 0; s < b->n_streams && !any; s++) any = b->slot_frames_h[(size_t) s] >= 0;
-        if (any) {
+        if (b->book.any_open()) {
             std::vector<uint8_t> ctl((size_t) b->n_streams, 0);
             return l12_slots_impl(b, pcm_dev, n_frames, ctl.data(), NULL, out_dev, out_stride, out_len_dev);
         }
         if (!pcm_dev || !out_dev || !out_len_dev || n_frames < 1 || n_frames > b->max_frames || out_stride < mp3mi_l12_batch_out_stride(b, n_frames))
             return MP3MI_ERR_ARG; // (before the bookkeeping changes)
-        l12_slots_close(b);
+        b->book.close();
     }
     return l12_encode_impl(b, pcm_dev, NULL, n_frames, out_dev, out_stride, out_len_dev, false);
 }
@@ -504,11 +413,11 @@ extern "C" int mp3mi_l12_batch_flush(mp3mi_l12_batch *b, uint8_t *out_dev, size_
     ON_DEVICE(b);
     const uint8_t *slot_ctl = NULL;
     mp3mi_l12_batch::ctl_ring::entry *blk = NULL;
-    if (b->slots_on) { // some slots open, not all at the same frame (l12_slots_settle), or none: the open ones end, the others deliver nothing
+    if (b->book.on) { // some slots open, not all at the same frame (slot_book::settle), or none: the open ones end, the others deliver nothing
         const int S = b->n_streams;
         if (l12_ctl_take(b, &blk) != MP3MI_OK) return MP3MI_ERR_HIP;
         const l12_ctl_block st = l12_ctl_at(blk->stage, S), dev = l12_ctl_at(blk->dev, S);
-        for (int s = 0; s < S; s++) st.ctl[s] = b->slot_frames_h[(size_t) s] >= 0 ? MP3MI_SLOT_DEV_ACTIVE : 0;
+        for (int s = 0; s < S; s++) st.ctl[s] = b->book.at(s) >= 0 ? MP3MI_SLOT_DEV_ACTIVE : 0;
         CHK(hipMemcpyAsync(dev.ctl, st.ctl, (size_t) S, hipMemcpyHostToDevice, b->stream)); // (k12_flush reads nothing else of the block)
         slot_ctl = dev.ctl;
     }
@@ -517,7 +426,7 @@ extern "C" int mp3mi_l12_batch_flush(mp3mi_l12_batch *b, uint8_t *out_dev, size_
         CHK(blk->free.record(b->stream));
         b->ctl.next();
     }
-    l12_slots_close(b);
+    b->book.close();
     CHK(hipGetLastError());
     return MP3MI_OK;
 }
@@ -525,7 +434,7 @@ extern "C" int mp3mi_l12_batch_flush(mp3mi_l12_batch *b, uint8_t *out_dev, size_
 extern "C" int mp3mi_l12_batch_reset(mp3mi_l12_batch *b)
 {
     if (!b) return MP3MI_ERR_ARG;
-    l12_slots_close(b);
+    b->book.close();
     return MP3MI_OK;
 }
 
@@ -583,25 +492,18 @@ extern "C" int mp3mi_l12_encode_host(int layer, int n_streams, int rate_hz, int 
     if (mode >= 0) rc = mp3mi_l12_batch_set_mode(b, mode);
     if (rc == MP3MI_OK) rc = mp3mi_l12_batch_set_error_protection(b, error_protection);
     if (rc != MP3MI_OK || out_stride < mp3mi_l12_batch_out_stride(b, n_frames)) { mp3mi_l12_batch_destroy(b); return MP3MI_ERR_ARG; }
-    const size_t spf = layer == 1 ? 384 : 1152;
-    const size_t pcm_bytes = (size_t) n_streams * (size_t) n_frames * spf * (size_t) channels * sizeof(int16_t);
-    int16_t *pcm_d = NULL;
-    uint8_t *out_d = NULL;
-    uint32_t *len_d = NULL;
-    int32_t *ns_d = NULL;
-    rc = MP3MI_ERR_HIP;
-    if (hipMalloc((void **) &pcm_d, pcm_bytes) == hipSuccess && hipMalloc((void **) &out_d, out_stride * (size_t) n_streams) == hipSuccess &&
-        hipMalloc((void **) &len_d, sizeof(uint32_t) * (size_t) n_streams) == hipSuccess &&
-        hipMalloc((void **) &ns_d, sizeof(int32_t) * (size_t) n_streams) == hipSuccess &&
-        hipMemcpy(pcm_d, pcm, pcm_bytes, hipMemcpyHostToDevice) == hipSuccess &&
-        (!n_samples || hipMemcpy(ns_d, n_samples, sizeof(int32_t) * (size_t) n_streams, hipMemcpyHostToDevice) == hipSuccess)) {
-        rc = mp3mi_l12_batch_encode(b, pcm_d, n_samples ? ns_d : NULL, n_frames, out_d, out_stride, len_d);
+    const size_t S = (size_t) n_streams;
+    {
+        hook_bufs D; // (the call's device copies: freed before the batch goes)
+        int16_t *pcm_d = D.copy_of(pcm, S * (size_t) n_frames * (size_t) l12_samples_per_frame(layer) * (size_t) channels);
+        uint8_t *out_d = D.raw<uint8_t>(out_stride * S);
+        uint32_t *len_d = D.raw<uint32_t>(S);
+        int32_t *ns_d = n_samples ? D.copy_of(n_samples, S) : D.raw<int32_t>(S);
+        rc = D.rc();
+        if (rc == MP3MI_OK) rc = mp3mi_l12_batch_encode(b, pcm_d, n_samples ? ns_d : NULL, n_frames, out_d, out_stride, len_d);
         if (rc == MP3MI_OK) rc = mp3mi_l12_batch_sync(b);
-        if (rc == MP3MI_OK && (hipMemcpy(out, out_d, out_stride * (size_t) n_streams, hipMemcpyDeviceToHost) != hipSuccess ||
-                               hipMemcpy(out_len, len_d, sizeof(uint32_t) * (size_t) n_streams, hipMemcpyDeviceToHost) != hipSuccess))
-            rc = MP3MI_ERR_HIP;
+        if (rc == MP3MI_OK && !(D.fetch(out, out_d, out_stride * S) && D.fetch(out_len, len_d, S))) rc = MP3MI_ERR_HIP;
     }
-    (void) hipFree(pcm_d); (void) hipFree(out_d); (void) hipFree(len_d); (void) hipFree(ns_d);
     mp3mi_l12_batch_destroy(b);
     return rc;
 }

@@ -38,7 +38,6 @@ size_t mp3mi_loop_state_size(void);
 void mp3mi_launch_prep_tail(const mp3mi_tables *T, const mp3mi_geom &g, const double *xr, const mp3mi_psy_out *psy, mp3mi_loop_prep *prep,
                             mp3mi_prep_fixlist *fix, hipStream_t st);
 
-static const int LD_BITRATES[15] = {0, 32, 40, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256, 320}; // src/common.c:124
 static const double LD_XR_MAX = 0x1p64, LD_XR_MIN = 0x1p-500;
 static const double LD_PE_MAX = 1e8;     // (int) (pe * 3.1 - mean_bits) stays an int (src/reservoir.c:117)
 static const double LD_RATIO_MAX = 1e30; // xmin = ratio * energy / width, doubled 16 times and pre-emphasised (* 8), stays finite: 2^100 * 2^138 * 2^19
@@ -87,19 +86,18 @@ extern "C" int mp3mi_debug_iteration_loop(int rate_hz, int channels, int crc, in
     if (!have_device()) return MP3MI_ERR_NO_DEVICE;
     const mp3mi_psy_out *psy = (const mp3mi_psy_out *) psy_v;
     const ld_loop_state *st_in = (const ld_loop_state *) state_in;
-    const int ri = rate_hz == 44100 ? 0 : (rate_hz == 48000 ? 1 : (rate_hz == 32000 ? 2 : -1));
+    const int ri = rate_idx_of(rate_hz);
     if (sizeof(ld_loop_state) != mp3mi_loop_state_size()) return MP3MI_ERR_HIP; // (internal: the layouts went apart)
     if (ri < 0 || (channels != 1 && channels != 2) || (crc & ~1) || n_streams <= 0 || n_streams > 4096 || n_frames <= 0 || n_frames > 64 ||
         !kbps || !xr || !psy || !ix || !side || !state_out || !n_listed)
         return MP3MI_ERR_ARG;
     const size_t S = (size_t) n_streams, nf = (size_t) n_frames, C = (size_t) channels, n_rec = S * 2 * nf * C;
-    int32_t *bits = (int32_t *) calloc(S, sizeof(int32_t));
+    host_mem<int32_t> bits_h(S);
+    int32_t *bits = bits_h.p;
     if (!bits) return MP3MI_ERR_NOMEM;
     bool legal = true;
     for (size_t s = 0; legal && s < S; s++) {
-        int bi = 1;
-        while (bi < 15 && LD_BITRATES[bi] != kbps[s]) bi++;
-        if (bi == 15) { legal = false; break; }
+        if (!bitrate_index_of(3, kbps[s])) { legal = false; break; }
         bits[s] = frame_bits(1152, ri, kbps[s], 8);
         legal = (bits[s] - (32 + 16 * crc + (channels == 1 ? 136 : 256))) / 2 / channels > 0;
         if (st_in) { // src/reservoir.c:45-93: the reservoir's size is the back pointer's bytes, within what the frame length leaves
@@ -121,72 +119,33 @@ extern "C" int mp3mi_debug_iteration_loop(int rate_hz, int channels, int crc, in
         for (int b = 0; legal && b < 36; b++) legal = (&p.ratio_s[0][0])[b] >= 0.0 && (&p.ratio_s[0][0])[b] <= LD_RATIO_MAX;
         legal = legal && ld_granule_ok(xr + r * 576);
     }
-    if (!legal) {
-        free(bits);
-        return MP3MI_ERR_ARG;
-    }
-    mp3mi_tables *Th = (mp3mi_tables *) malloc(sizeof(mp3mi_tables));
-    if (!Th) {
-        free(bits);
-        return MP3MI_ERR_NOMEM;
-    }
-    const int trc = mp3mi_build_tables(Th, ri);
-    if (trc != 0) {
-        free(Th);
-        free(bits);
-        return trc == -8 ? MP3MI_ERR_TABLES : MP3MI_ERR_ARG;
-    }
-    mp3mi_tables *dT = NULL;
-    double *dxr = NULL;
-    mp3mi_psy_out *dpsy = NULL;
-    mp3mi_loop_prep *dprep = NULL;
-    mp3mi_prep_fixlist *dfix = NULL;
-    int32_t *dbits = NULL;
-    ld_loop_state *dstate = NULL;
-    int16_t *dix = NULL;
-    mp3mi_frame_side *dside = NULL;
-    int rc = MP3MI_ERR_HIP;
+    if (!legal) return MP3MI_ERR_ARG;
+    host_mem<mp3mi_tables> Th(1);
+    const int trc = tables_into(Th, ri);
+    if (trc != MP3MI_OK) return trc;
+    hook_bufs D;
+    const mp3mi_tables *dT = D.copy_of(Th.p, 1);
     // (a record more than the launch has behind the spectrum, the records and the quantised values, as format_debug.cpp leaves one)
-    if (hipMalloc((void **) &dT, sizeof(mp3mi_tables)) == hipSuccess && hipMalloc((void **) &dxr, (n_rec + 1) * 576 * 8) == hipSuccess &&
-        hipMalloc((void **) &dpsy, (n_rec + 1) * sizeof(mp3mi_psy_out)) == hipSuccess &&
-        hipMalloc((void **) &dprep, (n_rec + 1) * sizeof(mp3mi_loop_prep)) == hipSuccess &&
-        hipMalloc((void **) &dfix, mp3mi_prep_fixlist_bytes(n_rec + 1)) == hipSuccess && hipMalloc((void **) &dbits, S * 4) == hipSuccess &&
-        hipMalloc((void **) &dstate, S * sizeof(ld_loop_state)) == hipSuccess && hipMalloc((void **) &dix, (n_rec + 1) * 576 * 2) == hipSuccess &&
-        hipMalloc((void **) &dside, (S * nf + 1) * sizeof(mp3mi_frame_side)) == hipSuccess &&
-        hipMemcpy(dT, Th, sizeof(mp3mi_tables), hipMemcpyHostToDevice) == hipSuccess &&
-        hipMemset(dxr, 0, (n_rec + 1) * 576 * 8) == hipSuccess && hipMemcpy(dxr, xr, n_rec * 576 * 8, hipMemcpyHostToDevice) == hipSuccess &&
-        hipMemset(dpsy, 0, (n_rec + 1) * sizeof(mp3mi_psy_out)) == hipSuccess &&
-        hipMemcpy(dpsy, psy, n_rec * sizeof(mp3mi_psy_out), hipMemcpyHostToDevice) == hipSuccess &&
-        hipMemset(dprep, 0, (n_rec + 1) * sizeof(mp3mi_loop_prep)) == hipSuccess &&
-        hipMemset(dfix, 0, mp3mi_prep_fixlist_bytes(n_rec + 1)) == hipSuccess &&
-        hipMemcpy(dbits, bits, S * 4, hipMemcpyHostToDevice) == hipSuccess &&
-        (st_in ? hipMemcpy(dstate, st_in, S * sizeof(ld_loop_state), hipMemcpyHostToDevice) : hipMemset(dstate, 0, S * sizeof(ld_loop_state))) == hipSuccess &&
-        hipMemset(dix, 0, (n_rec + 1) * 576 * 2) == hipSuccess && hipMemset(dside, 0, (S * nf + 1) * sizeof(mp3mi_frame_side)) == hipSuccess) {
-        // the three launches of the drop-in iteration_loop (dropin.cpp, frame_chain_launch), for all streams and frames at once
-        mp3mi_geom g = mp3mi_make_geom(n_streams, channels, ri, n_frames, 0, n_frames);
-        g.crc = crc;
-        mp3mi_launch_prep_tail(dT, g, dxr, dpsy, dprep, dfix, 0);
-        mp3mi_launch_prep(dT, g, dxr, dpsy, dprep, dfix, 0, 0);
-        mp3mi_launch_loop(dT, g, dxr, dpsy, dprep, dbits, dstate, dix, dside, NULL, mp3mi_loop_place{NULL, NULL, NULL, NULL, NULL, NULL, NULL, 0}, 0);
-        unsigned listed = 0;
-        if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(ix, dix, n_rec * 576 * 2, hipMemcpyDeviceToHost) == hipSuccess &&
-            hipMemcpy(side, dside, S * nf * sizeof(mp3mi_frame_side), hipMemcpyDeviceToHost) == hipSuccess &&
-            hipMemcpy(state_out, dstate, S * sizeof(ld_loop_state), hipMemcpyDeviceToHost) == hipSuccess &&
-            hipMemcpy(&listed, &dfix->count, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess) {
-            *n_listed = (int32_t) listed;
-            rc = MP3MI_OK;
-        }
-    }
-    if (dT) hipFree(dT);
-    if (dxr) hipFree(dxr);
-    if (dpsy) hipFree(dpsy);
-    if (dprep) hipFree(dprep);
-    if (dfix) hipFree(dfix);
-    if (dbits) hipFree(dbits);
-    if (dstate) hipFree(dstate);
-    if (dix) hipFree(dix);
-    if (dside) hipFree(dside);
-    free(Th);
-    free(bits);
-    return rc;
+    const double *dxr = D.copy_of(xr, n_rec * 576, 576);
+    const mp3mi_psy_out *dpsy = D.copy_of(psy, n_rec, 1);
+    mp3mi_loop_prep *dprep = D.zeros<mp3mi_loop_prep>(n_rec + 1);
+    mp3mi_prep_fixlist *dfix = (mp3mi_prep_fixlist *) D.zeros<uint8_t>(mp3mi_prep_fixlist_bytes(n_rec + 1));
+    const int32_t *dbits = D.copy_of(bits, S);
+    ld_loop_state *dstate = st_in ? D.copy_of(st_in, S) : D.zeros<ld_loop_state>(S);
+    int16_t *dix = D.zeros<int16_t>((n_rec + 1) * 576);
+    mp3mi_frame_side *dside = D.zeros<mp3mi_frame_side>(S * nf + 1);
+    if (!D.ok) return D.rc();
+    // the three launches of the drop-in iteration_loop (dropin.cpp, frame_chain_launch), for all streams and frames at once
+    mp3mi_geom g = mp3mi_make_geom(n_streams, channels, ri, n_frames, 0, n_frames);
+    g.crc = crc;
+    mp3mi_launch_prep_tail(dT, g, dxr, dpsy, dprep, dfix, 0);
+    mp3mi_launch_prep(dT, g, dxr, dpsy, dprep, dfix, 0, 0);
+    mp3mi_launch_loop(dT, g, dxr, dpsy, dprep, dbits, (void *) dstate, dix, dside, NULL, mp3mi_loop_place{NULL, NULL, NULL, NULL, NULL, NULL, NULL, 0}, 0);
+    unsigned listed = 0;
+    D.sync();
+    D.fetch(ix, dix, n_rec * 576);
+    D.fetch((mp3mi_frame_side *) side, dside, S * nf);
+    D.fetch((ld_loop_state *) state_out, dstate, S);
+    if (D.fetch(&listed, &dfix->count, 1)) *n_listed = (int32_t) listed;
+    return D.rc();
 }
