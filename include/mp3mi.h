@@ -278,6 +278,57 @@ int mp3mi_batch_slots_export(mp3mi_batch *b, int n, const int32_t *slots_host, i
 int mp3mi_batch_slots_import(mp3mi_batch *b, int n, const int32_t *slots_host, const void *state_dev, size_t state_stride,
                              const mp3mi_slot_ticket *tickets_host);
 
+/* The feeder: any number of samples per call.  A per-slot call wants a full call of samples from every open slot; real streams
+ * arrive in packets of 960 samples, in bursts, in whatever a decoder upstream hands over.  A feeder sits in front of a slot batch,
+ * keeps a FIFO of samples per slot ON THE DEVICE, cuts the rows of every tick there (k_feed, csrc/k_format.hip) and parks and
+ * resumes, with the two calls above, the streams that are short of a tick.  It touches no encoding kernel: a tick ends in one
+ * mp3mi_batch_encode_slots_kbps call on rows the feeder owns.
+ *   mp3mi_feed_create    a feeder for batch b -- on which no stream is open, and which has no feeder yet -- that encodes
+ *                        tick_frames frames (1 .. the batch's max_frames) per ready lane and tick and takes up to max_push (>= 1)
+ *                        samples per lane and call.  LANE s is slot s of the batch, one to one.
+ *   mp3mi_feed_capacity  what a lane's FIFO holds: tick_frames * 1152 + max_push samples per channel.
+ *   mp3mi_feed_tick      pcm_dev: device, int16 [n_streams][pcm_pitch][channels] in WAV order, pcm_pitch >= max_push; lane s brings
+ *                        its first n_push_host[s] samples per channel (0 .. max_push; NULL: 0 for every lane).  ctl_host,
+ *                        n_push_host and kbps_host are HOST arrays, copied before the call returns.
+ *     A lane is READY when its pending samples and the pushed ones make a tick (tick_frames * 1152), or when it is ending (below).
+ *     A ready lane encodes tick_frames frames; out_len_dev[s] receives the bytes of its file that became final, as for
+ *     mp3mi_batch_encode_slots.  A lane that is not ready delivers out_len 0; its samples stay pending, nothing of it is lost, and
+ *     a stream it holds in the batch is parked until the lane is ready again.  A tick in which no lane is ready launches no
+ *     encoding kernel; out_len_dev is zeroed all the same, in stream order.
+ *     ctl_host[s]   MP3MI_SLOT_START: a new stream begins in the lane with this call's first pushed sample, at kbps_host[s] (the
+ *                   rules of mp3mi_batch_encode_slots_kbps, checked here; NULL or 0: the slot's create-time bitrate).  A stream
+ *                   open in the lane is abandoned with its pending samples and its parked record, as mp3mi_batch_encode_slots
+ *                   abandons one.  The batch sees the START in the first tick in which the lane is ready.
+ *                   MP3MI_SLOT_END: this call's samples are the stream's last.  From here the lane DRAINS: tick_frames frames per
+ *                   tick while more than tick_frames * 1152 samples are pending; in the first tick with that many or fewer (0
+ *                   too) the batch gets its END with exactly that count, and the lane closes.  START | END with few samples is a
+ *                   one-call file.
+ *     MP3MI_ERR_ARG, with nothing enqueued and feeder and batch unchanged -- the check runs over all lanes first --: unknown ctl
+ *     bits; a push or an END on a closed lane without START; START, END or a push on a draining lane; n_push outside
+ *     0 .. max_push; pending + push above mp3mi_feed_capacity; a NULL pointer other than n_push_host / kbps_host; pcm_pitch <
+ *     max_push; out_stride < mp3mi_batch_out_stride(b, tick_frames); a kbps the per-slot call would refuse.
+ *     The bytes a lane delivers from a stream's START through the tick that closes it, concatenated, are byte for byte what
+ *     mp3mi_batch_encode_ragged gives for the stream's samples at its bitrate -- however the samples were cut into pushes and
+ *     however often the stream sat out a tick.  The call waits for nothing: ticks may be issued back to back.
+ *   mp3mi_feed_lanes     host bookkeeping only, no wait: per lane the pending samples, the frames encoded so far (-1: closed) and
+ *                        flags -- bit 0 parked, bit 1 draining, bit 2 started but not yet in the batch.  Returns the number of
+ *                        lanes that are not closed.
+ *   mp3mi_feed_destroy   resets the batch (streams in lanes are abandoned) and detaches; mp3mi_batch_destroy on a batch with a
+ *                        feeder attached frees the feeder with it (do not destroy it afterwards).
+ * While a feeder is attached the batch's streams are the feeder's: mp3mi_batch_encode, _encode_ragged, _encode_next,
+ * _encode_slots(_kbps), _flush, _reset, _slots_export, _slots_import, the host-buffer calls (_encode_host_async,
+ * _encode_slots(_kbps)_host_async) and _set_header / _set_mode / _set_error_protection return MP3MI_ERR_ARG; mp3mi_batch_sync,
+ * _stream_status, _slot_frames, _slot_kbps and the timing accessors work as ever (a parked lane's slot reads as closed).  A batch
+ * that never gets a feeder allocates and launches exactly what it did without.
+ * Not yet: Layers I and II (mp3mi_l12.h), ticks on host buffers, and more lanes than slots. */
+typedef struct mp3mi_feed mp3mi_feed;
+int mp3mi_feed_create(mp3mi_feed **out, mp3mi_batch *b, int tick_frames, int max_push);
+void mp3mi_feed_destroy(mp3mi_feed *f);
+size_t mp3mi_feed_capacity(const mp3mi_feed *f);
+int mp3mi_feed_tick(mp3mi_feed *f, const int16_t *pcm_dev, size_t pcm_pitch, const uint8_t *ctl_host, const int32_t *n_push_host,
+                    const int32_t *kbps_host, uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev);
+int mp3mi_feed_lanes(const mp3mi_feed *f, int32_t *pending_host, int64_t *frames_host, uint8_t *flags_host);
+
 /* Ragged batch: stream s has n_samples_dev[s] valid samples per channel (0 <= n <= n_frames*1152) in
  * its row of pcm_dev (row pitch n_frames*1152*channels as above).  As the reference's get_audio /
  * read_samples do (/root/reference/src/encode.c:123-269, zero fill :162-166), the last partial frame
@@ -466,6 +517,17 @@ int mp3mi_debug_peak_lines(int rate_hz, int n_gran, const double *xr, uint16_t *
 int mp3mi_debug_format_frames(int rate_hz, int channels, int kbps, int hdr_mode, int hdr_flags, int crc, int n_streams, int n_frames,
                               const int32_t *n_frames_s, const int16_t *ix, const void *side, uint8_t *out, size_t out_stride,
                               uint32_t *out_len, int32_t *status);
+/* Self-test hook: k_feed (csrc/k_format.hip), as mp3mi_feed_tick launches it, on GIVEN rings, descriptors and push rows.  Lane s of
+ * n_lanes: desc[4 s ..] = {head, pending, n_push, take} in samples per channel; its ring of cap samples at ring + s * ring_pitch *
+ * channels, its push row at push + s * push_pitch * channels, its dense row of row_samples at rows + s * row_pitch * channels (the
+ * pitches in samples per channel; ring_pitch >= cap and row_pitch >= row_samples, both multiples of 16 bytes; what lies between the
+ * records is the caller's to fill and to check).  The first `take` samples of ring[head .. head + pending) (wrapping at cap)
+ * followed by push[0 .. n_push) go to the row; the pushed samples behind them are appended to the ring at
+ * (head + pending + the pushed samples the row took) % cap.  All three arrays come back as the device holds them afterwards.
+ * MP3MI_ERR_ARG, and nothing is launched, unless for every lane head < cap, pending + n_push <= cap, take <= pending + n_push,
+ * take <= row_samples and n_push <= push_pitch.  MP3MI_ERR_NO_DEVICE without a GPU. */
+int mp3mi_debug_feed(int channels, int n_lanes, int cap, int row_samples, const uint32_t *desc, int16_t *ring, size_t ring_pitch,
+                     int16_t *push, size_t push_pitch, int16_t *rows, size_t row_pitch);
 /* Self-test hook: the iteration loop on n_streams chains of n_frames frames of GIVEN records, through the three launches of the
  * drop-in iteration_loop (csrc/dropin.cpp): k_prep_tail, k_prep on the list it leaves, k_loop with no placement and no gate
  * (csrc/loop_debug.cpp; k_loop.hip is the product's).  One format per call -- rate_hz, channels, crc (error protection) -- and a

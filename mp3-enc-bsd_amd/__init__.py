@@ -108,6 +108,14 @@ def lib():
         L.mp3mi_batch_slots_export.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
                                                ctypes.c_void_p]
         L.mp3mi_batch_slots_import.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        L.mp3mi_feed_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+        L.mp3mi_feed_destroy.argtypes = [ctypes.c_void_p]
+        L.mp3mi_feed_destroy.restype = None
+        L.mp3mi_feed_capacity.restype = ctypes.c_size_t
+        L.mp3mi_feed_capacity.argtypes = [ctypes.c_void_p]
+        L.mp3mi_feed_tick.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        L.mp3mi_feed_lanes.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.mp3mi_batch_encode_slots_host_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         L.mp3mi_batch_encode_slots_kbps_host_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
@@ -339,6 +347,12 @@ class Batch:
         self._check(self.L.mp3mi_batch_slots_import(self.h, len(sl), sl.ctypes.data, state.data_ptr(), state.shape[1], ctypes.addressof(arr)),
                     "mp3mi_batch_slots_import")
 
+    def feeder(self, tick_frames, max_push):
+        """A Feed in front of this batch (mp3mi_feed_create): streams bring any number of samples per tick, up to max_push, and a
+        tick encodes tick_frames frames of every lane that has them.  No stream may be open, and while the Feed is attached the
+        batch's encode, flush, reset, park and header calls are refused: the Feed makes them."""
+        return Feed(self, tick_frames, max_push)
+
     def set_mode(self, mode):
         """0 stereo, 2 dual channel, 3 mono (the reference's -m s|d|m); joint stereo is refused as in the reference"""
         self._check(self.L.mp3mi_batch_set_mode(self.h, mode), "mp3mi_batch_set_mode")
@@ -384,8 +398,76 @@ class Batch:
 
     def close(self):
         if self.h:
+            if getattr(self, "_feed", None) is not None:
+                self._feed.h = ctypes.c_void_p()  # (mp3mi_batch_destroy frees an attached feeder with the batch)
+                self._feed = None
             self.L.mp3mi_batch_destroy(self.h)
             self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Feed:
+    """The feeder of a Batch (include/mp3mi.h, mp3mi_feed_*): a device FIFO per slot, so that every stream may bring any number
+    of samples per call.  Lane s is slot s.  Made by Batch.feeder()."""
+
+    def __init__(self, batch, tick_frames, max_push):
+        self.batch, self.L = batch, batch.L
+        self.tick_frames, self.max_push = tick_frames, max_push
+        self.h = ctypes.c_void_p()
+        rc = self.L.mp3mi_feed_create(ctypes.byref(self.h), batch.h, tick_frames, max_push)
+        if rc != 0:
+            raise Mp3miError("mp3mi_feed_create failed with %d" % rc)
+        batch._feed = self
+
+    @property
+    def capacity(self):
+        """samples per channel a lane holds: tick_frames * 1152 + max_push"""
+        return self.L.mp3mi_feed_capacity(self.h)
+
+    def tick(self, pcm, out, out_len, start=None, end=None, n_push=None, kbps=None):
+        """One tick (mp3mi_feed_tick).  pcm: int16 cuda tensor [S, pitch * C] or [S, pitch, C], pitch >= max_push: lane s brings
+        its first n_push[s] samples per channel (None: none).  start[s]: a new stream begins in lane s with them, at kbps[s] (0 /
+        None: the slot's create-time bitrate); end[s]: they are the stream's last.  Every lane that has tick_frames * 1152 samples,
+        or is ending, encodes; out uint8 cuda [S, stride >= batch.out_stride(tick_frames)] and out_len int32 cuda [S] receive per
+        lane the bytes of its file that became final (0 for a lane that sits out).  Nothing is waited for."""
+        import numpy as np
+        S, C = self.batch.n_streams, self.batch.channels
+        assert pcm.is_cuda and out.is_cuda and out_len.is_cuda and pcm.is_contiguous() and out.is_contiguous() and pcm.shape[0] == S
+        pitch = pcm.numel() // (S * C)
+        ctl = np.zeros(S, np.uint8)
+        if start is not None:
+            ctl |= np.asarray(start, dtype=bool).reshape(S).astype(np.uint8) * 1  # MP3MI_SLOT_START
+        if end is not None:
+            ctl |= np.asarray(end, dtype=bool).reshape(S).astype(np.uint8) * 2  # MP3MI_SLOT_END
+        ns = None if n_push is None else np.ascontiguousarray(n_push, dtype=np.int32).reshape(S)
+        kb = None if kbps is None else np.ascontiguousarray(kbps, dtype=np.int32).reshape(S)
+        rc = self.L.mp3mi_feed_tick(self.h, pcm.data_ptr(), pitch, ctl.ctypes.data, None if ns is None else ns.ctypes.data,
+                                    None if kb is None else kb.ctypes.data, out.data_ptr(), out.shape[1], out_len.data_ptr())
+        if rc != 0:
+            raise Mp3miError("mp3mi_feed_tick failed with %d" % rc)
+
+    def lanes(self):
+        """(pending int32 [S], frames int64 [S] (-1: closed), flags uint8 [S]: 1 parked, 2 draining, 4 started but not yet in the
+        batch; lanes that are not closed) -- host bookkeeping, no device wait"""
+        import numpy as np
+        S = self.batch.n_streams
+        p, f, g = np.zeros(S, np.int32), np.zeros(S, np.int64), np.zeros(S, np.uint8)
+        rc = self.L.mp3mi_feed_lanes(self.h, p.ctypes.data, f.ctypes.data, g.ctypes.data)
+        if rc < 0:
+            raise Mp3miError("mp3mi_feed_lanes failed with %d" % rc)
+        return p, f, g, rc
+
+    def close(self):
+        """resets the batch and detaches (mp3mi_feed_destroy)"""
+        if self.h:
+            self.L.mp3mi_feed_destroy(self.h)
+            self.h = ctypes.c_void_p()
+            self.batch._feed = None
 
     def __del__(self):
         try:

@@ -212,7 +212,13 @@ struct mp3mi_batch {
     int last_launches;
     double tot_loop_ms, tot_all_ms;
     long tot_launches, tot_calls;
+    // a feeder in front of the batch (feed.h, mp3mi_feed_create): while one is attached, the calls that start, move or end streams
+    // and the header settings are the feeder's alone (feed_locked); feed_call: the feeder is making such a call
+    struct mp3mi_feed *feed;
+    bool feed_call;
 };
+static void feed_drop(struct mp3mi_feed *f); // (feed.h, at the end of this file)
+static inline bool feed_locked(const mp3mi_batch *b) { return b && b->feed && !b->feed_call; }
 
 // Device and pinned buffers of a batch: allocated here and nowhere else, so that mp3mi_batch_destroy knows them all
 template <typename T> static hipError_t dev_alloc(mp3mi_batch *b, T **p, size_t bytes)
@@ -546,6 +552,7 @@ extern "C" void mp3mi_batch_destroy(mp3mi_batch *b)
         if (e) hipEventDestroy(e);
     for (hipStream_t st : {H.h2d, H.d2h, b->stream, b->lstream})
         if (st) hipStreamDestroy(st);
+    if (b->feed) feed_drop(b->feed); // (its buffers were the batch's: freed above)
     delete b;
 }
 
@@ -569,6 +576,7 @@ extern "C" int mp3mi_batch_set_test_flags(mp3mi_batch *b, unsigned flags)
 
 extern "C" int mp3mi_batch_set_header(mp3mi_batch *b, int copyright, int original, int emphasis)
 {
+    if (feed_locked(b)) return MP3MI_ERR_ARG;
     if (!b || (copyright & ~1) || (original & ~1) || (emphasis & ~3)) return MP3MI_ERR_ARG;
     b->hdr_flags = (copyright << 3) | (original << 2) | emphasis;
     return MP3MI_OK;
@@ -576,6 +584,7 @@ extern "C" int mp3mi_batch_set_header(mp3mi_batch *b, int copyright, int origina
 
 extern "C" int mp3mi_batch_set_mode(mp3mi_batch *b, int mode)
 {
+    if (feed_locked(b)) return MP3MI_ERR_ARG;
     if (!b) return MP3MI_ERR_ARG;
     // -m s / d / m of the reference's driver (src/musicin.c:226-234); joint stereo is refused for Layer III by the
     // reference itself (src/musicin.c:548-552), and the mode has to fit the channel count
@@ -587,6 +596,7 @@ extern "C" int mp3mi_batch_set_mode(mp3mi_batch *b, int mode)
 
 extern "C" int mp3mi_batch_set_error_protection(mp3mi_batch *b, int on)
 {
+    if (feed_locked(b)) return MP3MI_ERR_ARG;
     if (!b || (on & ~1)) return MP3MI_ERR_ARG;
     b->crc = on;
     return MP3MI_OK;
@@ -662,6 +672,7 @@ static int reset_impl(mp3mi_batch *b)
 
 extern "C" int mp3mi_batch_reset(mp3mi_batch *b)
 {
+    if (feed_locked(b)) return MP3MI_ERR_ARG;
     if (!b) return MP3MI_ERR_ARG;
     ON_DEVICE(b);
     b->status_kept = false; // an explicit reset starts new streams: what a flush kept of the ones it ended goes with them
@@ -672,13 +683,14 @@ extern "C" int mp3mi_batch_reset(mp3mi_batch *b)
 extern "C" int mp3mi_batch_encode(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, uint8_t *out_dev,
                                   size_t out_stride, uint32_t *out_len_dev)
 {
+    if (feed_locked(b)) return MP3MI_ERR_ARG;
     return encode_impl(b, pcm_dev, NULL, n_frames, out_dev, out_stride, out_len_dev, true);
 }
 
 extern "C" int mp3mi_batch_encode_ragged(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_samples_dev, int n_frames,
                                          uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev)
 {
-    if (!n_samples_dev) return MP3MI_ERR_ARG;
+    if (!n_samples_dev || feed_locked(b)) return MP3MI_ERR_ARG;
     return encode_impl(b, pcm_dev, n_samples_dev, n_frames, out_dev, out_stride, out_len_dev, true);
 }
 
@@ -764,6 +776,7 @@ extern "C" int mp3mi_batch_encode_slots_kbps(mp3mi_batch *b, const int16_t *pcm_
                                              const int32_t *n_samples_host, const int32_t *kbps_host, uint8_t *out_dev, size_t out_stride,
                                              uint32_t *out_len_dev)
 {
+    if (feed_locked(b)) return MP3MI_ERR_ARG;
     return slots_impl(b, pcm_dev, n_frames, ctl_host, n_samples_host, kbps_host, out_dev, out_stride, out_len_dev);
 }
 
@@ -790,6 +803,7 @@ extern "C" int mp3mi_batch_slot_frames(const mp3mi_batch *b, int64_t *frames_hos
 extern "C" int mp3mi_batch_encode_next(mp3mi_batch *b, const int16_t *pcm_dev, int n_frames, uint8_t *out_dev,
                                        size_t out_stride, uint32_t *out_len_dev)
 {
+    if (feed_locked(b)) return MP3MI_ERR_ARG;
     if (b && b->book.on) {
         // per-slot bookkeeping in force: with no stream open every slot starts (the whole-batch start: state cleared for all);
         // otherwise the open streams go on and the other slots stay closed
@@ -838,7 +852,7 @@ static mp3mi_geom call_geom(const mp3mi_batch *b, const call_shape &c, int f0, i
 
 extern "C" int mp3mi_batch_flush(mp3mi_batch *b, uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev)
 {
-    if (!b || !out_dev || !out_len_dev || out_stride < min_out_stride(b, 0, true)) return MP3MI_ERR_ARG;
+    if (!b || !out_dev || !out_len_dev || out_stride < min_out_stride(b, 0, true) || feed_locked(b)) return MP3MI_ERR_ARG;
     ON_DEVICE(b);
     hold_release(b);
     const int S = b->n_streams;
@@ -971,7 +985,7 @@ static int park_run(mp3mi_batch *b, int n, const int32_t *slots_host, const mp3m
 extern "C" int mp3mi_batch_slots_export(mp3mi_batch *b, int n, const int32_t *slots_host, int close, void *state_dev, size_t state_stride,
                                         mp3mi_slot_ticket *tickets_host)
 {
-    if (!b) return MP3MI_ERR_ARG;
+    if (!b || feed_locked(b)) return MP3MI_ERR_ARG;
     mp3mi_park_table front, loop;
     const size_t state_bytes = park_tables(b, &front, &loop);
     if (!park_args_ok(b, n, slots_host, state_dev, state_stride, tickets_host, state_bytes)) return MP3MI_ERR_ARG;
@@ -1012,7 +1026,7 @@ extern "C" int mp3mi_batch_slots_export(mp3mi_batch *b, int n, const int32_t *sl
 extern "C" int mp3mi_batch_slots_import(mp3mi_batch *b, int n, const int32_t *slots_host, const void *state_dev, size_t state_stride,
                                         const mp3mi_slot_ticket *tickets_host)
 {
-    if (!b) return MP3MI_ERR_ARG;
+    if (!b || feed_locked(b)) return MP3MI_ERR_ARG;
     mp3mi_park_table front, loop;
     const size_t state_bytes = park_tables(b, &front, &loop);
     if (!park_args_ok(b, n, slots_host, state_dev, state_stride, tickets_host, state_bytes)) return MP3MI_ERR_ARG;
@@ -1567,7 +1581,7 @@ static int host_io_init(mp3mi_batch *b, int sl)
 extern "C" int mp3mi_batch_encode_host_async(mp3mi_batch *b, const int16_t *pcm_host, int n_frames, uint8_t *out_host, size_t out_stride,
                                              uint32_t *out_len_host)
 {
-    if (!b || !pcm_host || !out_host || !out_len_host || n_frames <= 0 || n_frames > b->max_frames) return MP3MI_ERR_ARG;
+    if (!b || !pcm_host || !out_host || !out_len_host || n_frames <= 0 || n_frames > b->max_frames || feed_locked(b)) return MP3MI_ERR_ARG;
     if (out_stride < min_out_stride(b, n_frames, false)) return MP3MI_ERR_ARG;
     ON_DEVICE(b);
     mp3mi_batch::host_io &H = b->hio;
@@ -1609,7 +1623,7 @@ extern "C" int mp3mi_batch_encode_slots_kbps_host_async(mp3mi_batch *b, const in
                                                         const uint8_t *ctl_host, const int32_t *n_samples_host, const int32_t *kbps_host,
                                                         uint8_t *out_host, size_t out_stride, uint32_t *out_len_host)
 {
-    if (!b || !pcm_host || !ctl_host || !out_host || !out_len_host || n_frames <= 0 || n_frames > b->max_frames) return MP3MI_ERR_ARG;
+    if (!b || !pcm_host || !ctl_host || !out_host || !out_len_host || n_frames <= 0 || n_frames > b->max_frames || feed_locked(b)) return MP3MI_ERR_ARG;
     const int S = b->n_streams;
     if (n_rows < 1 || n_rows > S || (!row_slot_host && n_rows != S)) return MP3MI_ERR_ARG;
     if (out_stride < mp3mi_batch_out_stride(b, n_frames)) return MP3MI_ERR_ARG;
@@ -1741,3 +1755,6 @@ extern "C" int mp3mi_encode_host_ex(int n_streams, int rate_hz, int channels, co
     return encode_host_impl(n_streams, rate_hz, channels, kbps, kbps_all, pcm, n_samples, n_frames,
                             (copyright << 3) | (original << 2) | emphasis, out, out_stride, out_len);
 }
+
+// ---- the feeder: a device FIFO per slot in front of the batch (mp3mi_feed_*) ----
+#include "feed.h"

@@ -178,3 +178,35 @@ extern "C" int mp3mi_debug_format_frames(int rate_hz, int channels, int kbps, in
     if (nf) D.fetch(out, dout, S * out_stride);
     return D.rc();
 }
+
+// The self-test hook mp3mi_debug_feed (include/mp3mi.h): k_feed alone, through the launcher the feeder uses, on given rings, push rows
+// and dense rows.  The three arrays go to the device whole -- the caller's pitches leave room between the lanes' records, which it
+// fills with a canary -- and come back whole.  Every descriptor is checked against the rules the feeder's tick keeps
+// (csrc/mp3mi_host.h, mp3mi_launch_feed): a descriptor that breaks one launches nothing.
+extern "C" int mp3mi_debug_feed(int channels, int n_lanes, int cap, int row_samples, const uint32_t *desc, int16_t *ring, size_t ring_pitch,
+                                int16_t *push, size_t push_pitch, int16_t *rows, size_t row_pitch)
+{
+    if (!have_device()) return MP3MI_ERR_NO_DEVICE;
+    if ((channels != 1 && channels != 2) || n_lanes <= 0 || cap <= 0 || row_samples <= 0 || !desc || !ring || !push || !rows) return MP3MI_ERR_ARG;
+    const size_t C = (size_t) channels, esz = 2 * C, S = (size_t) n_lanes;
+    if (ring_pitch < (size_t) cap || row_pitch < (size_t) row_samples || push_pitch == 0 || ring_pitch * esz % 16 != 0 || row_pitch * esz % 16 != 0)
+        return MP3MI_ERR_ARG;
+    size_t most = 0;
+    for (size_t s = 0; s < S; s++) {
+        const uint64_t head = desc[4 * s], pending = desc[4 * s + 1], n_push = desc[4 * s + 2], take = desc[4 * s + 3];
+        if (head >= (uint64_t) cap || pending + n_push > (uint64_t) cap || take > pending + n_push || take > (uint64_t) row_samples || n_push > push_pitch)
+            return MP3MI_ERR_ARG;
+        const size_t longest = (size_t) (take > n_push ? take : n_push) * esz;
+        most = longest > most ? longest : most;
+    }
+    hook_bufs D;
+    const uint32_t *ddesc = D.copy_of(desc, 4 * S);
+    int16_t *dring = D.copy_of(ring, S * ring_pitch * C), *dpush = D.copy_of(push, S * push_pitch * C), *drows = D.copy_of(rows, S * row_pitch * C);
+    if (!D.ok) return D.rc();
+    mp3mi_launch_feed(ddesc, n_lanes, dring, ring_pitch * esz, cap, channels, dpush, push_pitch * esz, drows, row_pitch * esz, most, 0);
+    D.sync();
+    D.fetch(ring, dring, S * ring_pitch * C);
+    D.fetch(push, dpush, S * push_pitch * C);
+    D.fetch(rows, drows, S * row_pitch * C);
+    return D.rc();
+}

@@ -680,6 +680,93 @@ void mp3mi_launch_rows_out(const int32_t *row_slot, int n_rows, const uint8_t *o
     hipLaunchKernelGGL(k_rows_out, dim3((unsigned) n_rows), dim3(256), 0, st, row_slot, out, out_stride, out_len, dense, dense_stride, dense_len);
 }
 
+// ---- the feeder (mp3mi_feed_tick): a device FIFO per lane in front of the per-slot call ----
+// A lane's logical stream is ring[head .. head + pending), wrapping at cap, followed by push[0 .. n_push).  k_feed moves its
+// first `take` samples into the lane's row of the dense rows the per-slot call reads, and appends what the rows do not take of
+// the push to the ring at (head + pending + the pushed samples the row took) % cap -- the position those samples have in the
+// logical stream, so the host's new head is (head + take) % cap whatever the case.  pending + n_push <= cap (the host checks),
+// so the span that is written and the span that is read never meet: nothing is moved within the ring, and no workgroup reads
+// what another writes.  That makes at most five plain copies per lane -- ring -> row (two: the wrap), push -> row, push -> ring
+// (two: the wrap) -- of spans whose source and destination are misaligned against each other by any multiple of a sample.
+//
+// feed_copy: n bytes, both ends aligned to 2.  The destination's naturally aligned 16-byte vectors are dealt to the lanes of the
+// lane's workgroups (lane of gridDim.y * 256, one store of 16 bytes each: a wavefront's store is 1 KiB, contiguous).  A vector
+// that lies wholly inside the span is put together from the ALIGNED 16-byte source vectors that hold its bytes -- one when the two
+// sides agree mod 16, else two and a funnel shift by the difference (even, 2 .. 14 bytes; uniform over the span) -- provided
+// these lie inside the source span too: nothing is loaded from outside [src, src + n).  The others, at most two at either
+// end, go sample by sample.  A wavefront's loads are contiguous as well; the second vector of a lane is the first of its
+// neighbour, so the cache serves it.
+MP3MI_DEVFN void feed_copy(uint8_t *dst, const uint8_t *src, size_t n, size_t lane, size_t step)
+{
+    if (n == 0) return;
+    const uintptr_t d0 = (uintptr_t) dst, s0 = (uintptr_t) src, dv0 = d0 & ~(uintptr_t) 15;
+    const size_t n_vec = (size_t) ((d0 + n + 15 - dv0) / 16);
+    const unsigned k = (unsigned) ((s0 - d0) & 15u); // where a destination vector's first byte lies in its first source vector
+    const unsigned ws = k >> 2, bs = (k & 2u) * 8u;
+    for (size_t v = lane; v < n_vec; v += step) {
+        const uintptr_t dv = dv0 + 16 * v;     // the destination vector
+        const uintptr_t sv = dv + (s0 - d0);   // its first byte in the source
+        const uintptr_t sa = sv - k;           // the aligned source vector that holds it
+        const bool whole = dv >= d0 && dv + 16 <= d0 + n;
+        if (whole && sa >= s0 && sa + (k ? 32 : 16) <= s0 + n) {
+            uint4 o = *(const uint4 *) sa;
+            if (k) {
+                const uint4 a = o, b = *(const uint4 *) (sa + 16);
+                const unsigned w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+                unsigned t[5];
+#pragma unroll
+                for (int j = 0; j < 5; j++) t[j] = ws == 0 ? w[j] : ws == 1 ? w[j + 1] : ws == 2 ? w[j + 2] : w[j + 3];
+                if (bs) {
+                    o.x = (t[0] >> 16) | (t[1] << 16); o.y = (t[1] >> 16) | (t[2] << 16);
+                    o.z = (t[2] >> 16) | (t[3] << 16); o.w = (t[3] >> 16) | (t[4] << 16);
+                } else {
+                    o.x = t[0]; o.y = t[1]; o.z = t[2]; o.w = t[3];
+                }
+            }
+            *(uint4 *) dv = o;
+        } else {
+            const uintptr_t lo = dv > d0 ? dv : d0, hi = dv + 16 < d0 + n ? dv + 16 : d0 + n;
+            for (uintptr_t p = lo; p < hi; p += 2) *(uint16_t *) p = *(const uint16_t *) (p + (s0 - d0));
+        }
+    }
+}
+
+// Workgroup (s, y): lane s -- its descriptor {head, pending, n_push, take} is one uniform 16-byte load -- and every
+// gridDim.y-th vector of each of its copies.  esz: bytes of a sample of all channels; cap: the ring's samples; the three pitches
+// in bytes (rows and rings: multiples of 16 from 16-byte aligned bases; the push rows: the caller's).  No LDS: nothing is reused.
+__global__ void __launch_bounds__(256) k_feed(const uint4 *__restrict__ desc, uint8_t *ring, size_t ring_pitch, unsigned cap, unsigned esz,
+                                              const uint8_t *__restrict__ push, size_t push_pitch, uint8_t *__restrict__ rows, size_t row_pitch)
+{
+    const size_t s = blockIdx.x;
+    const uint4 d = desc[s];
+    const size_t head = d.x, pending = d.y, n_push = d.z, take = d.w;
+    if (n_push == 0 && take == 0) return;
+    const size_t lane = (size_t) blockIdx.y * 256 + threadIdx.x, step = (size_t) 256 * gridDim.y;
+    uint8_t *rg = ring + s * ring_pitch, *row = rows + s * row_pitch;
+    const uint8_t *ps = push + s * push_pitch;
+    const size_t from_ring = take < pending ? take : pending; // the row's samples that come out of the ring
+    const size_t from_push = take - from_ring;                // ... and out of the push
+    const size_t r1 = from_ring < cap - head ? from_ring : cap - head;
+    feed_copy(row, rg + head * esz, r1 * esz, lane, step);
+    feed_copy(row + r1 * esz, rg, (from_ring - r1) * esz, lane, step);
+    feed_copy(row + from_ring * esz, ps, from_push * esz, lane, step);
+    const size_t n_app = n_push - from_push, at = (head + pending + from_push) % cap;
+    const size_t a1 = n_app < cap - at ? n_app : cap - at;
+    feed_copy(rg + at * esz, ps + from_push * esz, a1 * esz, lane, step);
+    feed_copy(rg, ps + (from_push + a1) * esz, (n_app - a1) * esz, lane, step);
+}
+
+void mp3mi_launch_feed(const void *desc, int n_lanes, int16_t *ring, size_t ring_pitch_bytes, int cap, int channels, const int16_t *push,
+                       size_t push_pitch_bytes, int16_t *rows, size_t row_pitch_bytes, size_t most_bytes, hipStream_t st)
+{
+    if (n_lanes <= 0) return;
+    const size_t per_wg = (size_t) 256 * 16 * 4; // four stores per lane of the longest copy
+    size_t ny = (most_bytes + per_wg - 1) / per_wg;
+    ny = ny < 1 ? 1 : ny > 8 ? 8 : ny;
+    hipLaunchKernelGGL(k_feed, dim3((unsigned) n_lanes, (unsigned) ny), dim3(256), 0, st, (const uint4 *) desc, (uint8_t *) ring, ring_pitch_bytes,
+                       (unsigned) cap, (unsigned) (2 * channels), (const uint8_t *) push, push_pitch_bytes, (uint8_t *) rows, row_pitch_bytes);
+}
+
 // the last MP3MI_PCM_HIST samples of the call (a frame has 1152 > MP3MI_PCM_HIST) are the next call's history
 __global__ void __launch_bounds__(256) k_hist_save(mp3mi_geom geo, const int16_t *__restrict__ pcm, int16_t *__restrict__ hist)
 {

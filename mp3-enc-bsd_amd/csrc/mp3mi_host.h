@@ -165,6 +165,13 @@ void mp3mi_launch_rows_in(const int32_t *row_slot, int n_rows, const int16_t *de
                           size_t width_bytes, hipStream_t st);
 void mp3mi_launch_rows_out(const int32_t *row_slot, int n_rows, const uint8_t *out, size_t out_stride, const uint32_t *out_len, uint8_t *dense,
                            size_t dense_stride, uint32_t *dense_len, hipStream_t st);
+/* k_feed (the feeder, mp3mi_feed_tick): per lane one descriptor of four uint32 {head, pending, n_push, take}, checked on the host
+   (head < cap, pending + n_push <= cap, take <= pending + n_push, take samples fit a row, n_push samples lie in the push row).  The
+   first `take` samples of ring[head .. head + pending) (wrapping at cap) ++ push[0 .. n_push) go to the lane's row; the pushed
+   samples behind them are appended to the ring at their place in that stream.  Pitches in bytes; rings and rows 16-byte aligned
+   with pitches that are multiples of 16; most_bytes: the longest copy of any lane (sizes the workgroups per lane) */
+void mp3mi_launch_feed(const void *desc, int n_lanes, int16_t *ring, size_t ring_pitch_bytes, int cap, int channels, const int16_t *push,
+                       size_t push_pitch_bytes, int16_t *rows, size_t row_pitch_bytes, size_t most_bytes, hipStream_t st);
 /* status[s] = the status word of stream s (a gather out of the strided state records) */
 void mp3mi_launch_status_gather(int n_streams, const int32_t *loop_state, int loop_state_words, int32_t *status, hipStream_t st);
 /* the reverse, for the streams a flush ended: their status words go back into the cleared state records, marked as reported */
