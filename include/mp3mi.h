@@ -480,10 +480,10 @@ int mp3mi_debug_dmath(int fn, const double *x, const double *y, double *out, siz
  * of [-80, 80].  tests/test_gpu_tiers.py asserts that their sum stays inside the guard band's 7e-7 budget. */
 int mp3mi_debug_fastmath_bounds(double out[3]);
 /* What v_cvt_pknorm_u16_f32 -- the rounding step of the quantiser's first tier -- returns on this device, over every float of the
- * range the quantiser feeds it (csrc/k_debug.hip): out[0] = max |n - a * 65535| (the proof in csrc/k_loop.hip needs <= 0.5),
+ * range the quantiser feeds it (csrc/k_debug.hip): out[0] = max |n - a * 65535| (the proof in csrc/loop_pass.h needs <= 0.5),
  * out[1] = non-monotone neighbours, out[2] = clamp / half mismatches (both 0). */
 int mp3mi_debug_pknorm_bound(double out[3]);
-/* Self-test hook: one quantise+count pass of k_loop (csrc/k_loop.hip), on n_gran granules of 576 xr each (rate_hz one of
+/* Self-test hook: one quantise+count pass of k_loop (csrc/loop_pass.h; the hook: csrc/k_loop_qc.hip), on n_gran granules of 576 xr each (rate_hz one of
  * 44100 / 48000 / 32000).  gran[4 i ..]: the step q (MP3MI_STEP_MIN .. +800, the reference's quantizerStepSize), the block type
  * (0..3), a rescale plan -- n_amp (0..16) amplifications of every scalefactor band by sqrt(2) and, before them, pre (0 / 1) one
  * pre-emphasis (not with block type 2) -- applied by the kernel's own statements to xr in double and to its cached |xr|^(3/4) in

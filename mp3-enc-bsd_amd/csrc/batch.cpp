@@ -27,7 +27,6 @@
 #include "mp3mi.h"
 
 size_t mp3mi_psy_state_size(void);
-size_t mp3mi_loop_state_size(void);
 
 // What a stream carries from call to call: one record per slot in each of these regions.  mp3mi_batch::carried is the ONE list
 // of them (carried_init, once the buffers exist), in the order of a parked stream's state record -- that order is part of the
@@ -329,7 +328,7 @@ static void carried_init(mp3mi_batch *b)
     const size_t C = (size_t) b->channels;
     const carried_region r[N_CARRIED] = {{b->psy_state, mp3mi_psy_state_size() * C, false, true},
                                          {b->pcm_hist, sizeof(int16_t) * MP3MI_PCM_HIST * C, false, true},
-                                         {b->loop_state, mp3mi_loop_state_size(), true, true},
+                                         {b->loop_state, sizeof(mp3mi_loop_state), true, true},
                                          {b->out_base, sizeof(int64_t), true, true}, // (0: a flush before the first encode delivers nothing)
                                          {b->carry, MP3MI_CARRY_BYTES, true, false},
                                          {b->carry_len, sizeof(int32_t), true, true},
@@ -456,7 +455,7 @@ static int batch_build(mp3mi_batch *b, int n_streams, int rate_hz, int channels,
     CHK(dev_alloc(b, &b->ix, ngc * 576 * sizeof(int16_t)));
     CHK(dev_alloc(b, &b->side, S * (size_t) cf * sizeof(mp3mi_frame_side)));
     CHK(dev_alloc(b, &b->psy_state, mp3mi_psy_state_size() * S * channels));
-    CHK(dev_alloc(b, &b->loop_state, mp3mi_loop_state_size() * S));
+    CHK(dev_alloc(b, &b->loop_state, sizeof(mp3mi_loop_state) * S));
     CHK(dev_alloc(b, &b->pcm_hist, sizeof(int16_t) * MP3MI_PCM_HIST * (size_t) channels * S));
     CHK(dev_alloc(b, &b->out_base, sizeof(int64_t) * S));
     CHK(dev_alloc(b, &b->carry, (size_t) MP3MI_CARRY_BYTES * S));
@@ -880,7 +879,7 @@ extern "C" int mp3mi_batch_flush(mp3mi_batch *b, uint8_t *out_dev, size_t out_st
         return MP3MI_OK;
     }
     // the tail of either kind of flush
-    const int words = (int) (mp3mi_loop_state_size() / 4);
+    const int words = (int) (sizeof(mp3mi_loop_state) / 4);
     mp3mi_launch_stream_tail(call_geom(b, cs, 0, 0, 0, S), 1, (int32_t *) b->loop_state, words, b->bits_per_frame, out_dev, out_stride, b->out_base,
                              b->carry, b->carry_len, out_len_dev, b->voided, b->lstream); // behind the last call's k_format
     CHK(hipGetLastError());
@@ -969,7 +968,7 @@ static int park_run(mp3mi_batch *b, int n, const int32_t *slots_host, const mp3m
     if (!to_state && b->status_kept) {
         // the last flush ended every stream and reset the state: the ended streams' status goes back into their slots now, as with a
         // per-slot call, so that the call after this one does not write it over the status the resumed streams bring along
-        mp3mi_launch_status_scatter(b->n_streams, (int32_t *) b->loop_state, (int) (mp3mi_loop_state_size() / 4), b->status_dev, b->lstream);
+        mp3mi_launch_status_scatter(b->n_streams, (int32_t *) b->loop_state, (int) (sizeof(mp3mi_loop_state) / 4), b->status_dev, b->lstream);
         CHK(hipGetLastError());
         b->status_kept = false;
     }
@@ -1114,7 +1113,7 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         CHK(hipGetLastError());
         CHK(hipStreamWaitEvent(b->lstream, b->ev_ctl_up, 0));
         if (kept) { // the last flush ended every stream and reset the state: the ended streams' status stays until their slot STARTs
-            mp3mi_launch_status_scatter(S, (int32_t *) b->loop_state, (int) (mp3mi_loop_state_size() / 4), b->status_dev, b->lstream);
+            mp3mi_launch_status_scatter(S, (int32_t *) b->loop_state, (int) (sizeof(mp3mi_loop_state) / 4), b->status_dev, b->lstream);
             CHK(hipGetLastError());
         }
         slot_begin(b, true, sc->dev.list, sc->n_start);
@@ -1209,7 +1208,7 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
             }
         }
     }
-    const size_t psy_state_bytes = mp3mi_psy_state_size() * (size_t) C, loop_state_bytes = mp3mi_loop_state_size();
+    const size_t psy_state_bytes = mp3mi_psy_state_size() * (size_t) C, loop_state_bytes = sizeof(mp3mi_loop_state);
     // which: 1 the FFTs, 2 k_cw, the partition sums (k_part) and k_psy (passed on as mp3mi_launch_fft's which, whose bit 1 is k_cw)
     auto stage_x = [&](int k, int which) -> int {
         const item_view v = view(k);
@@ -1374,7 +1373,7 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         mp3mi_launch_hist_save(g, pcm_dev, b->pcm_hist, b->stream);
         CHK(hipGetLastError());
         if (!whole_file) {
-            mp3mi_launch_stream_tail(g, 0, (int32_t *) b->loop_state, (int) (mp3mi_loop_state_size() / 4), b->bits_per_frame, out_dev,
+            mp3mi_launch_stream_tail(g, 0, (int32_t *) b->loop_state, (int) (sizeof(mp3mi_loop_state) / 4), b->bits_per_frame, out_dev,
                                      out_stride, b->out_base, b->carry, b->carry_len, out_len_dev, b->voided, b->lstream);
             CHK(hipGetLastError());
             if (hc && download() != MP3MI_OK) return MP3MI_ERR_HIP;
@@ -1430,7 +1429,7 @@ extern "C" int mp3mi_batch_stream_status(mp3mi_batch *b, int32_t *status_host)
     // (the state of the most recent streams: a whole-file call leaves it behind, the next call's reset clears it; a
     // flush gathers it before its reset)
     if (!b->status_kept) {
-        mp3mi_launch_status_gather(b->n_streams, (const int32_t *) b->loop_state, (int) (mp3mi_loop_state_size() / 4), b->status_dev, b->lstream);
+        mp3mi_launch_status_gather(b->n_streams, (const int32_t *) b->loop_state, (int) (sizeof(mp3mi_loop_state) / 4), b->status_dev, b->lstream);
         CHK(hipGetLastError());
     }
     CHK(hipStreamSynchronize(b->stream));

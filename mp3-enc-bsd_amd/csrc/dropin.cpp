@@ -17,7 +17,6 @@
 #include "mp3mi_dropin.h"
 
 size_t mp3mi_psy_state_size(void);
-size_t mp3mi_loop_state_size(void);
 void mp3mi_launch_filter_subband(const mp3mi_tables *T, const double *z, double *s, hipStream_t st);
 void mp3mi_launch_window_filter(const mp3mi_tables *T, double *ring, int off, const mp3mi_dropin_samples &in, double *zs, hipStream_t st);
 void mp3mi_launch_mdct_sub(const mp3mi_tables *T, const double *sb_in, double *sb_out, const int32_t *bt, double *xr, double *xr_dev, int stereo, int mode_gr,
@@ -49,14 +48,6 @@ void mp3mi_launch_prep_tail(const mp3mi_tables *T, const mp3mi_geom &g, const do
 namespace {
 
 const int WIN_FRAMES = 16; // frames of history kept in the formatter's byte window
-
-// mirrors mp3mi_loop_state in k_loop.hip (all int32)
-struct loop_state_host {
-    int32_t ResvSize;
-    int32_t sc_en_tot[2][2], sc_en[2][2][21], sc_xm[2][2][21], sc_xrmax[2][2];
-    int32_t addr[2][2][3];
-    int32_t ref_abort;
-};
 
 // a buffer that crosses the boundary: host-mapped, h for the host code, d for the kernels
 template <typename T> struct io_buf {
@@ -152,7 +143,7 @@ struct DropIn {
         int C = 0, crc = 0, bitsPerFrame = 0, bitrate_index = 0, mode = 0, hdr_flags = 0;
         const mp3mi_psy_out *rec_h = nullptr; // (host view of) the records k_loop read
         unsigned seq_loop = 0, seq_fmt = 0;
-        loop_state_host state_before;
+        mp3mi_loop_state state_before;
         uint8_t *win_before = nullptr;
         size_t win_before_bytes = 0;
     } fa;
@@ -180,7 +171,7 @@ struct DropIn {
     mp3mi_prep_fixlist *prep_fix = nullptr;
     io_buf<int16_t> ix;
     io_buf<mp3mi_frame_side> side;
-    io_buf<loop_state_host> loop_state;
+    io_buf<mp3mi_loop_state> loop_state;
     io_buf<int32_t> bits, bri;
     bool loop_first = true;
     // format
@@ -259,8 +250,7 @@ void ensure(int rate_idx)
     HIPOK(hipMalloc((void **) &D.prep_fix, mp3mi_prep_fixlist_bytes(4)));
     D.ix.alloc(4 * 576 * sizeof(int16_t));
     D.side.alloc(sizeof(mp3mi_frame_side));
-    if (sizeof(loop_state_host) != mp3mi_loop_state_size()) DIE("internal: loop state layout mismatch");
-    D.loop_state.alloc(sizeof(loop_state_host));
+    D.loop_state.alloc(sizeof(mp3mi_loop_state));
     D.bits.alloc(sizeof(int32_t));
     D.bri.alloc(sizeof(int32_t));
     HIPOK(hipMalloc((void **) &D.len_d, sizeof(uint32_t)));
@@ -812,7 +802,7 @@ extern "C" void iteration_loop(double pe[][2], double xr_org[2][2][576], III_psy
     A.have_last = true;
     const int16_t (*ix)[576] = (const int16_t (*)[576]) D.ix.h;
     const mp3mi_frame_side &sd = *D.side.h;
-    const loop_state_host &ls = *D.loop_state.h;
+    const mp3mi_loop_state &ls = *D.loop_state.h;
     // inputs the reference dies on: so does this call, with the reference's own words (its assert() prints the
     // expression and abort()s)
     if ((ls.ref_abort & 255) == MP3MI_DEV_ABORT_GLOBAL_GAIN) DIE("iteration_loop: Assertion `cod_info->global_gain < 256' failed (src/loop.c:358)");

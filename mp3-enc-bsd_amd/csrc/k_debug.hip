@@ -71,7 +71,7 @@ extern "C" int mp3mi_debug_dmath(int fn, const double *x, const double *y, doubl
 extern "C" int mp3mi_debug_fastmath_bounds(double out[3]) { (void) out; return MP3MI_ERR_NO_DEVICE; } // a statement about the hardware
 extern "C" int mp3mi_debug_pknorm_bound(double out[3]) { (void) out; return MP3MI_ERR_NO_DEVICE; }
 #else
-// ---- what v_cvt_pknorm_u16_f32 returns (the quantiser's rounding step, k_loop.hip: loop_quant_pair) ----
+// ---- what v_cvt_pknorm_u16_f32 returns (the quantiser's rounding step, loop_pass.h: loop_quant_pair) ----
 // For EVERY float a of [2^-31, 2048.5 / 65535] (218 M arguments) and the floats around both clamps: the result n against
 // a * 65535 in double (exact: a 24-bit by a 16-bit factor).  out[0] = max |n - a * 65535| (0.5: a correctly rounded product; the
 // quantiser's proof needs <= 0.5), out[1] = arguments whose successor converts to a SMALLER n (0: monotone), out[2] = arguments

@@ -1,7 +1,7 @@
 // The self-test hook mp3mi_debug_iteration_loop (include/mp3mi.h): chains of given records -- spectrum, perceptual entropy, masking
 // ratios, block type -- through the iteration loop as the drop-in iteration_loop launches it (dropin.cpp, frame_chain_launch):
 // k_prep_tail, k_prep on the list it leaves, k_loop with no placement and no gate, for S streams x nf frames in one launch.  Host
-// code only: k_loop.hip is untouched, the kernels are the ones the encoder runs.
+// code only: k_loop.hip and loop_pass.h are untouched, the kernels are the ones the encoder runs.
 //
 // What the three kernels take on trust from the stages before them is checked here first (a chain that breaks one of the rules is
 // refused, nothing is launched).  The two bounds that are not a matter of type:
@@ -34,21 +34,12 @@
 #include "host_util.h"
 #include "mp3mi.h"
 
-size_t mp3mi_loop_state_size(void);
 void mp3mi_launch_prep_tail(const mp3mi_tables *T, const mp3mi_geom &g, const double *xr, const mp3mi_psy_out *psy, mp3mi_loop_prep *prep,
                             mp3mi_prep_fixlist *fix, hipStream_t st);
 
 static const double LD_XR_MAX = 0x1p64, LD_XR_MIN = 0x1p-500;
 static const double LD_PE_MAX = 1e8;     // (int) (pe * 3.1 - mean_bits) stays an int (src/reservoir.c:117)
 static const double LD_RATIO_MAX = 1e30; // xmin = ratio * energy / width, doubled 16 times and pre-emphasised (* 8), stays finite: 2^100 * 2^138 * 2^19
-
-// mirrors mp3mi_loop_state in k_loop.hip (all int32)
-struct ld_loop_state {
-    int32_t ResvSize;
-    int32_t sc_en_tot[2][2], sc_en[2][2][21], sc_xm[2][2][21], sc_xrmax[2][2];
-    int32_t addr[2][2][3];
-    int32_t ref_abort;
-};
 
 static inline int ld_nint(double in) { return (in < 0) ? (int) (in - 0.5) : (int) (in + 0.5); } // src/loop.c:2020
 
@@ -85,9 +76,8 @@ extern "C" int mp3mi_debug_iteration_loop(int rate_hz, int channels, int crc, in
 {
     if (!have_device()) return MP3MI_ERR_NO_DEVICE;
     const mp3mi_psy_out *psy = (const mp3mi_psy_out *) psy_v;
-    const ld_loop_state *st_in = (const ld_loop_state *) state_in;
+    const mp3mi_loop_state *st_in = (const mp3mi_loop_state *) state_in;
     const int ri = rate_idx_of(rate_hz);
-    if (sizeof(ld_loop_state) != mp3mi_loop_state_size()) return MP3MI_ERR_HIP; // (internal: the layouts went apart)
     if (ri < 0 || (channels != 1 && channels != 2) || (crc & ~1) || n_streams <= 0 || n_streams > 4096 || n_frames <= 0 || n_frames > 64 ||
         !kbps || !xr || !psy || !ix || !side || !state_out || !n_listed)
         return MP3MI_ERR_ARG;
@@ -101,7 +91,7 @@ extern "C" int mp3mi_debug_iteration_loop(int rate_hz, int channels, int crc, in
         bits[s] = frame_bits(1152, ri, kbps[s], 8);
         legal = (bits[s] - (32 + 16 * crc + (channels == 1 ? 136 : 256))) / 2 / channels > 0;
         if (st_in) { // src/reservoir.c:45-93: the reservoir's size is the back pointer's bytes, within what the frame length leaves
-            const ld_loop_state &t = st_in[s];
+            const mp3mi_loop_state &t = st_in[s];
             int ResvMax = bits[s] > 7680 ? 0 : 7680 - bits[s];
             if (ResvMax > 4088) ResvMax = 4088;
             legal = legal && t.ResvSize >= 0 && t.ResvSize <= ResvMax && t.ResvSize % 8 == 0 && t.ref_abort == 0;
@@ -131,7 +121,7 @@ extern "C" int mp3mi_debug_iteration_loop(int rate_hz, int channels, int crc, in
     mp3mi_loop_prep *dprep = D.zeros<mp3mi_loop_prep>(n_rec + 1);
     mp3mi_prep_fixlist *dfix = (mp3mi_prep_fixlist *) D.zeros<uint8_t>(mp3mi_prep_fixlist_bytes(n_rec + 1));
     const int32_t *dbits = D.copy_of(bits, S);
-    ld_loop_state *dstate = st_in ? D.copy_of(st_in, S) : D.zeros<ld_loop_state>(S);
+    mp3mi_loop_state *dstate = st_in ? D.copy_of(st_in, S) : D.zeros<mp3mi_loop_state>(S);
     int16_t *dix = D.zeros<int16_t>((n_rec + 1) * 576);
     mp3mi_frame_side *dside = D.zeros<mp3mi_frame_side>(S * nf + 1);
     if (!D.ok) return D.rc();
@@ -145,7 +135,7 @@ extern "C" int mp3mi_debug_iteration_loop(int rate_hz, int channels, int crc, in
     D.sync();
     D.fetch(ix, dix, n_rec * 576);
     D.fetch((mp3mi_frame_side *) side, dside, S * nf);
-    D.fetch((ld_loop_state *) state_out, dstate, S);
+    D.fetch((mp3mi_loop_state *) state_out, dstate, S);
     if (D.fetch(&listed, &dfix->count, 1)) *n_listed = (int32_t) listed;
     return D.rc();
 }

@@ -102,7 +102,7 @@ typedef struct {
     uint8_t nj_seg[2][64];           /* bit d (1, 2, 4, 8, 16): job j + d belongs to the same band as job j (bands have < 32 jobs) */
     /* what lane l of k_loop needs to know about "its" lines and noise jobs, packed so that one 8-byte load each brings it in
        where it is used (the distortion loop) instead of a dozen registers living through the whole search; [0] long, [1] short:
-       lane_bands: [0] band (= band lane) of the lane's PAIR k < 5 -- lines 2 (l + 64 k), + 1: one band, k_loop.hip -- in bits 6k .. 6k+5;
+       lane_bands: [0] band (= band lane) of the lane's PAIR k < 5 -- lines 2 (l + 64 k), + 1: one band, loop_pass.h -- in bits 6k .. 6k+5;
                    [1] of its value j < 10 -- line 2 (l + 64 (j / 2)) + j % 2 -- in bits 6j .. 6j+5 (63: the line does not exist);
        lane_jobs: nj_first (10 bits) | nj_count << 10 (8) | nj_seg << 18 (5) | nj_job0 << 23 (6) | nj_njobs << 29 (6) |
                   lines of band l << 35 (8) | first line of band l << 43 (10; short: l = sfb * 3 + window -> first * 3 + window) */
@@ -200,7 +200,7 @@ typedef struct {
 /* q0 as its two writers store it (k_prep.hip, k_fbmdct.hip): never past the last entry of step[] */
 MP3MI_DEVFN int mp3mi_clamp_q0(int q0) { return q0 > MP3MI_STEP_MIN + MP3MI_STEP_N - 1 ? MP3MI_STEP_MIN + MP3MI_STEP_N - 1 : q0; }
 
-/* Peak cells.  The quantiser is monotone in |xr| (ix = max{p : tab[p] <= |xr| / step}, k_loop.hip) and everything the search
+/* Peak cells.  The quantiser is monotone in |xr| (ix = max{p : tab[p] <= |xr| / step}, loop_pass.h) and everything the search
  * does to the spectrum -- pre-emphasis, amplification -- multiplies all lines of a scalefactor band by one positive factor,
  * which keeps '<=' through the rounding.  So among lines that are always scaled together the one with the largest |xr| has the
  * largest quantised value in every pass of the granule: k_loop's region maxima read that one line per cell instead of walking
@@ -270,7 +270,7 @@ typedef struct {
     mp3mi_gr_side gr[2][2];
 } mp3mi_frame_side;
 
-/* The quantiser's first tier (k_loop.hip, loop_quantize) estimates x^(3/4) with the raw hardware square root and
+/* The quantiser's first tier (loop_pass.h, loop_quantize) estimates x^(3/4) with the raw hardware square root and
  * exp2 (v_sqrt_f32, v_exp_f32: 1 ulp each); its guard band budgets 7e-7 relative for the two roots, the exp2
  * and the roundings between them.  mp3mi_debug_fastmath_bounds (k_debug.hip) measures these very expressions
  * on the device.  The CPU test build substitutes libm. */

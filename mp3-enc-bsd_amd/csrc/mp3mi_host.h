@@ -2,6 +2,7 @@
 #ifndef MP3MI_HOST_H
 #define MP3MI_HOST_H
 
+#include <stddef.h>
 #include "mp3mi_dev.h"
 
 #ifdef __cplusplus
@@ -137,7 +138,15 @@ void mp3mi_launch_hold_release(unsigned *flag, unsigned ticket, hipStream_t st);
    part of the bit reservoir's slots and the headers in between, at most MP3MI_CARRY_BYTES -- wait in `carry` */
 #define MP3MI_CARRY_BYTES 2048
 void mp3mi_launch_carry_in(int n_streams, const uint8_t *carry, const int32_t *carry_len, uint8_t *out, size_t out_stride, hipStream_t st);
-/* loop_state: the streams' mp3mi_loop_state records (k_loop.hip) as words -- word 0 is ResvSize, the last word the
+/* what k_loop keeps of a stream between calls: the bit reservoir, the scfsi history and the region addresses */
+typedef struct {
+    int32_t ResvSize;
+    int32_t sc_en_tot[2][2], sc_en[2][2][21], sc_xm[2][2][21], sc_xrmax[2][2];
+    int32_t addr[2][2][3];
+    int32_t ref_abort; /* 0, or MP3MI_DEV_ABORT_* | frame << 8 -- an input the reference dies on */
+} mp3mi_loop_state;
+static_assert(offsetof(mp3mi_loop_state, ref_abort) == sizeof(mp3mi_loop_state) - 4, "ref_abort is the last word: k_format and k_stream_tail find it there");
+/* loop_state: the streams' mp3mi_loop_state records as words -- word 0 is ResvSize, the last word the
    stream's status (MP3MI_DEV_ABORT_*); voided: counts the streams whose file a call voided because of it */
 void mp3mi_launch_stream_tail(const mp3mi_geom &g, int flush, int32_t *loop_state, int loop_state_words, const int32_t *bits_per_frame,
                               uint8_t *out, size_t out_stride, int64_t *out_base, uint8_t *carry, int32_t *carry_len, uint32_t *out_len,

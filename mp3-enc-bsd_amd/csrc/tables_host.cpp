@@ -836,7 +836,7 @@ static int build_tables_unpinned(mp3mi_tables *T, int rate_idx)
         const int nb = t ? 36 : 21;
         for (int l = 0; l < 64; l++) {
             uint64_t bp = 0;
-            if (t) { /* short blocks: value j of lane l is line 2 (l + 64 (j / 2)) + j % 2 (k_loop.hip, loop_pair_of) */
+            if (t) { /* short blocks: value j of lane l is line 2 (l + 64 (j / 2)) + j % 2 (loop_pass.h, loop_pair_of) */
                 for (int j = 0; j < 10; j++) {
                     const int line = 2 * (l + 64 * (j / 2)) + j % 2;
                     bp |= (uint64_t) (line < 576 ? T->sfb_of_line_s[line] : 63) << (6 * j);
@@ -1129,7 +1129,7 @@ static int build_tables_unpinned(mp3mi_tables *T, int rate_idx)
                     e |= len << (5 * f);
                 }
                 /* the two groups with linbits have no third table: bits 10..11 of their cells hold how many of x, y are escapes
-                   (== 15), so that k_loop's walk prices the linbits without testing the values (k_loop.hip, loop_walk_step) */
+                   (== 15), so that k_loop's walk prices the linbits without testing the values (loop_pass.h, loop_walk_step) */
                 if (gi == 6 || gi == 7) e |= (unsigned) ((c / 16 == 15) + (c % 16 == 15)) << 10;
                 T->glut[groups[gi][0] + c] = (uint16_t) e;
             }

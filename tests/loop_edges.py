@@ -55,7 +55,7 @@ EXIT_NO_OVER, EXIT_LOOP_BREAK, EXIT_SCALE_BITCOUNT = 1, 2, 3
 XR_MAX, XR_MIN, STEP_MAX = 2.0 ** 64, 2.0 ** -500, 400  # the hook's domain (csrc/loop_debug.cpp)
 BIG = 1e12  # a ratio no band's noise reaches: the band never violates
 
-# mp3mi_loop_state (csrc/k_loop.hip) as the hook and the oracle exchange it, and the oracle's trace (oracle/mp3_oracle.h)
+# mp3mi_loop_state (csrc/mp3mi_host.h) as the hook and the oracle exchange it, and the oracle's trace (oracle/mp3_oracle.h)
 STATE_DT = np.dtype([("ResvSize", "<i4"), ("sc_en_tot", "<i4", (2, 2)), ("sc_en", "<i4", (2, 2, 21)), ("sc_xm", "<i4", (2, 2, 21)),
                      ("sc_xrmax", "<i4", (2, 2)), ("addr", "<i4", (2, 2, 3)), ("status", "<i4")])
 TRACE_DT = np.dtype([("q0", "<i4"), ("q_final", "<i4"), ("n_outer", "<i4"), ("n_passes", "<i4"), ("n_probes", "<i4"), ("exit_how", "<i4"),

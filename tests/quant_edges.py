@@ -1,4 +1,4 @@
-"""Granules built to sit on the edges of k_loop's quantise+count pass (csrc/k_loop.hip: loop_quantize, loop_count_bits), and the
+"""Granules built to sit on the edges of k_loop's quantise+count pass (csrc/loop_pass.h: loop_quantize, loop_count_bits), and the
 three implementations that take them: the product's self-test hook mp3mi_debug_quantize_count (the device, or the emulated CPU
 build), the oracle's mp3o_quantize_count and the unmodified reference's quantize() / count_bits() (oracle/_ref/ref_harness_qc).
 Everything is generated here, deterministically; nothing is read from files.

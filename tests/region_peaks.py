@@ -1,4 +1,4 @@
-"""Granules built for the way k_loop takes its region maxima (csrc/k_loop.hip, loop_count_bits; csrc/mp3mi_dev.h, peak cells): one
+"""Granules built for the way k_loop takes its region maxima (csrc/loop_pass.h, loop_count_bits; csrc/mp3mi_dev.h, peak cells): one
 read per cell, at the line of the cell whose |xr| is largest, instead of a walk over the region.  What can go wrong there: the
 cell that the end of the big-values region cuts, the fallback to the walks (big_values == 0, an address past the region's end),
 a peak at the edge of its cell, ties, the cells above the last scalefactor band, and whether the peak of the ORIGINAL spectrum

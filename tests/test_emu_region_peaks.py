@@ -1,4 +1,4 @@
-"""k_loop's region maxima from per-cell peak lines (csrc/k_loop.hip, loop_count_bits; csrc/mp3mi_dev.h), on the CPU emulator:
+"""k_loop's region maxima from per-cell peak lines (csrc/loop_pass.h, loop_count_bits; csrc/mp3mi_dev.h), on the CPU emulator:
 the crafted granules of tests/region_peaks.py through the pass's self-test hook against the oracle's quantise + count -- ix,
 big_values, count1, the three tables, the region counts, the addresses and the bit count, for equality --, and the property the
 fast path rests on, on 2000 random granules: after ANY per-band amplification the line with the largest original |xr| of a cell

@@ -1,4 +1,4 @@
-"""k_loop's quantise+count pass on the DEVICE (mp3mi_debug_quantize_count, csrc/k_loop.hip) against the oracle on every granule
+"""k_loop's quantise+count pass on the DEVICE (mp3mi_debug_quantize_count, csrc/k_loop_qc.hip) against the oracle on every granule
 of the edge sets S1..S7 (tests/quant_edges.py) at every rate: ix, the rescaled xr and every field, bit for bit.  And the sets
 reach what they are for: the rare tier on the boundary sets, the all-zero shortcut, the clamp at the table's end, every Huffman
 group and linbits table a maximum of at most 2047 can select."""

@@ -15,7 +15,7 @@ FLAGS = {"noise": 1, "phase": 2, "psy": 4, "quant": 8, "prep": 16, "cw": 32, "al
 
 
 def test_raw_sqrt_and_exp2_stay_inside_the_guard_band_budget(product):
-    """k_loop.hip loop_quantize: the two estimates of x^(3/4) + 0.4054 - 0.5 are
+    """loop_pass.h loop_quantize: the two estimates of x^(3/4) + 0.4054 - 0.5 are
          fma(y34, exp2_raw(-3q/16) * (1 +- 3.5e-6) / 65535, (0.4054 - 0.5 +- 2e-6) / 65535),  y34 = sqrt_raw(a * sqrt_raw(a)) [* up to 17 rescalings]
     and the band between them budgets 7e-7 relative for everything but the rescalings.  Measured on this device over
     all 2^24 floats of [1, 4) (the error repeats exactly every factor of 4), every step size the search can ask
@@ -30,7 +30,7 @@ def test_raw_sqrt_and_exp2_stay_inside_the_guard_band_budget(product):
 
 
 def test_the_quantisers_rounding_instruction_rounds_to_nearest(product):
-    """k_loop.hip loop_quant_pair: v_cvt_pknorm_u16_f32 turns the upper and the lower estimate of x^(3/4) + 0.4054 - 0.5 (scaled
+    """loop_pass.h loop_quant_pair: v_cvt_pknorm_u16_f32 turns the upper and the lower estimate of x^(3/4) + 0.4054 - 0.5 (scaled
     by 1 / 65535) into integers, a pair per instruction; the proof that a line whose two roundings agree is settled needs
     |n - a * 65535| <= 0.5 and a monotone conversion.  Every float of [2^-31, 2048.5 / 65535] (218 M arguments) against double
     arithmetic, both halves of the instruction, both clamps."""
