@@ -320,7 +320,45 @@ int mp3mi_batch_slots_import(mp3mi_batch *b, int n, const int32_t *slots_host, c
  * _encode_slots(_kbps)_host_async) and _set_header / _set_mode / _set_error_protection return MP3MI_ERR_ARG; mp3mi_batch_sync,
  * _stream_status, _slot_frames, _slot_kbps and the timing accessors work as ever (a parked lane's slot reads as closed).  A batch
  * that never gets a feeder allocates and launches exactly what it did without.
- * Not yet: Layers I and II (mp3mi_l12.h), ticks on host buffers, and more lanes than slots. */
+ *
+ * MORE LANES THAN SLOTS.  Streams that arrive in packets are slow: a tick of 32 frames holds 0.84 s of audio and takes milliseconds, so
+ * a lane that is tied to a slot leaves the slot idle nearly all the time.  A feeder made by mp3mi_feed_create_lanes has n_lanes lanes in
+ * front of the batch's n_streams slots, in any relation (fewer, as many, more): a lane's FIFO and its parked record are the lane's, a
+ * slot is lent to a lane for the ticks in which it encodes.  Each kind of feeder has its own tick: mp3mi_feed_tick returns MP3MI_ERR_ARG
+ * on a feeder made by mp3mi_feed_create_lanes, mp3mi_feed_tick_lanes on one made by mp3mi_feed_create.
+ *   mp3mi_feed_create_lanes  n_lanes >= 1; max_rows in 1 .. n_lanes: the most lanes that may push in one tick (it sizes the upload
+ *                        blocks); ring_samples: a lane's FIFO in samples per channel, at least tick_frames * 1152 + max_push, 0: exactly
+ *                        that (mp3mi_feed_capacity reports it).  A lane that is ready but waits for a slot keeps taking pushes until
+ *                        its FIFO is full, so a server sizes it for the wait it accepts.  Otherwise the rules of mp3mi_feed_create.
+ *   mp3mi_feed_n_lanes   the lanes of a feeder (n_streams for one made by mp3mi_feed_create); mp3mi_feed_lanes takes arrays of that
+ *                        many entries.
+ *   mp3mi_feed_tick_lanes  the pushes come as ROWS: row r is lane row_lane_host[r] (strictly increasing, each in 0 .. n_lanes-1; n_rows
+ *                        in 0 .. max_rows), its samples row r of pcm_dev [n_rows][pcm_pitch][channels], and ctl_host, n_push_host and
+ *                        kbps_host are indexed by row, with the meaning they have in mp3mi_feed_tick word for word.  A lane that no
+ *                        row names pushes nothing and has ctl 0; it may encode all the same (it drains, or gets a slot at last).  With
+ *                        n_rows == 0 the four row arrays and pcm_dev may be NULL; with n_rows > 0 none of them may.  All host arrays
+ *                        are copied before the call returns.
+ *     Who encodes.  A lane is READY as above.  If no more than n_streams lanes are ready, all encode.  Otherwise the n_streams lanes
+ *     encode whose current unbroken spell of being ready began in the earliest tick, ties going to the lower lane; a lane that encodes
+ *     and is still ready begins a new spell in the next tick.  So no ready lane encodes twice while another that was ready before it
+ *     has not encoded once.  A ready lane that gets no slot keeps its samples, delivers nothing, is parked if its stream is in a slot,
+ *     and shows bit 3 (value 8: ready, waiting for a slot) in mp3mi_feed_lanes' flags until the tick in which it encodes.
+ *     Where.  A chosen lane whose stream is in a slot keeps the slot.  Every other stream in a slot leaves it (parked).  The other
+ *     chosen lanes take the free slots -- those vacated in this very tick among them --, the lowest free slot going to the lowest lane:
+ *     a parked stream is resumed there, a stream the batch has not seen STARTs there.  A START at kbps 0 means the create-time bitrate
+ *     of the slot in which the stream first encodes; until then only kbps 0 may be passed with the lane's pushes.
+ *     Output is by SLOT, as mp3mi_batch_encode_slots writes it: out_dev [n_streams][out_stride], out_len_dev [n_streams].
+ *     slot_lane_host [n_streams] is filled before the call returns (host bookkeeping, no device wait): entry i is the lane that encodes
+ *     in slot i in this tick, or -1, and out_len_dev[i] is 0 where it is -1.  A tick in which nothing encodes launches no encoding
+ *     kernel and zeroes out_len_dev in stream order.  The bytes a LANE delivers from a stream's START through the tick that closes it,
+ *     gathered slot by slot through slot_lane_host and concatenated, are the stream's file, as above.
+ *     MP3MI_ERR_ARG, nothing enqueued, feeder and batch unchanged: everything mp3mi_feed_tick refuses, per row's lane; n_rows outside
+ *     0 .. max_rows; a row map out of order or out of range; a NULL row array or pcm_dev with n_rows > 0; a NULL out_dev, out_len_dev
+ *     or slot_lane_host; pending + push above mp3mi_feed_capacity (a waiting lane whose FIFO is full).
+ *     Status: mp3mi_batch_stream_status stays by SLOT; with the slot_lane_host of the tick it names the lane.  The status word travels
+ *     in the record and an abort is reported by one sync only (above).  There is no status query per lane.
+ * Not yet: Layers I and II (mp3mi_l12.h), ticks on host buffers, a status query per lane, and a direct path for a parked record between
+ * a lane and a slot (the records of a tick pass through a dense block). */
 typedef struct mp3mi_feed mp3mi_feed;
 int mp3mi_feed_create(mp3mi_feed **out, mp3mi_batch *b, int tick_frames, int max_push);
 void mp3mi_feed_destroy(mp3mi_feed *f);
@@ -328,6 +366,11 @@ size_t mp3mi_feed_capacity(const mp3mi_feed *f);
 int mp3mi_feed_tick(mp3mi_feed *f, const int16_t *pcm_dev, size_t pcm_pitch, const uint8_t *ctl_host, const int32_t *n_push_host,
                     const int32_t *kbps_host, uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev);
 int mp3mi_feed_lanes(const mp3mi_feed *f, int32_t *pending_host, int64_t *frames_host, uint8_t *flags_host);
+int mp3mi_feed_create_lanes(mp3mi_feed **out, mp3mi_batch *b, int n_lanes, int max_rows, int tick_frames, int max_push, int ring_samples);
+int mp3mi_feed_n_lanes(const mp3mi_feed *f);
+int mp3mi_feed_tick_lanes(mp3mi_feed *f, int n_rows, const int32_t *row_lane_host, const int16_t *pcm_dev, size_t pcm_pitch,
+                          const uint8_t *ctl_host, const int32_t *n_push_host, const int32_t *kbps_host, uint8_t *out_dev, size_t out_stride,
+                          uint32_t *out_len_dev, int32_t *slot_lane_host);
 
 /* Ragged batch: stream s has n_samples_dev[s] valid samples per channel (0 <= n <= n_frames*1152) in
  * its row of pcm_dev (row pitch n_frames*1152*channels as above).  As the reference's get_audio /
@@ -528,6 +571,15 @@ int mp3mi_debug_format_frames(int rate_hz, int channels, int kbps, int hdr_mode,
  * take <= row_samples and n_push <= push_pitch.  MP3MI_ERR_NO_DEVICE without a GPU. */
 int mp3mi_debug_feed(int channels, int n_lanes, int cap, int row_samples, const uint32_t *desc, int16_t *ring, size_t ring_pitch,
                      int16_t *push, size_t push_pitch, int16_t *rows, size_t row_pitch);
+/* Self-test hook: k_feed_lanes (csrc/k_format.hip), as mp3mi_feed_tick_lanes launches it, over n_active descriptors of eight uint32
+ * {head, pending, n_push, take, lane, push_row, slot, 0}: the ring is lane `lane` of n_lanes, the push row `push_row` of n_push_rows, the
+ * row that is cut `slot` of n_slots (pitches and copies as for mp3mi_debug_feed; the three arrays go up and come back whole).
+ * MP3MI_ERR_ARG (-1), and nothing is launched, unless every descriptor keeps the rules of mp3mi_debug_feed, its three indices are in
+ * range, its last word is 0, no lane is named twice, no slot by two descriptors that take and no push row by two that push.
+ * MP3MI_ERR_NO_DEVICE without a GPU. */
+int mp3mi_debug_feed_lanes(int channels, int n_active, int n_lanes, int n_push_rows, int n_slots, int cap, int row_samples,
+                           const uint32_t *desc, int16_t *ring, size_t ring_pitch, int16_t *push, size_t push_pitch, int16_t *rows,
+                           size_t row_pitch);
 /* Self-test hook: the iteration loop on n_streams chains of n_frames frames of GIVEN records, through the three launches of the
  * drop-in iteration_loop (csrc/dropin.cpp): k_prep_tail, k_prep on the list it leaves, k_loop with no placement and no gate
  * (csrc/loop_debug.cpp; k_loop.hip is the product's).  One format per call -- rate_hz, channels, crc (error protection) -- and a

@@ -116,6 +116,10 @@ def lib():
         L.mp3mi_feed_tick.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         L.mp3mi_feed_lanes.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.mp3mi_feed_create_lanes.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p] + [ctypes.c_int] * 5
+        L.mp3mi_feed_n_lanes.argtypes = [ctypes.c_void_p]
+        L.mp3mi_feed_tick_lanes.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
         L.mp3mi_batch_encode_slots_host_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         L.mp3mi_batch_encode_slots_kbps_host_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
@@ -347,11 +351,14 @@ class Batch:
         self._check(self.L.mp3mi_batch_slots_import(self.h, len(sl), sl.ctypes.data, state.data_ptr(), state.shape[1], ctypes.addressof(arr)),
                     "mp3mi_batch_slots_import")
 
-    def feeder(self, tick_frames, max_push):
+    def feeder(self, tick_frames, max_push, lanes=None, max_rows=None, ring_samples=0):
         """A Feed in front of this batch (mp3mi_feed_create): streams bring any number of samples per tick, up to max_push, and a
         tick encodes tick_frames frames of every lane that has them.  No stream may be open, and while the Feed is attached the
-        batch's encode, flush, reset, park and header calls are refused: the Feed makes them."""
-        return Feed(self, tick_frames, max_push)
+        batch's encode, flush, reset, park and header calls are refused: the Feed makes them.
+        lanes: that many lanes in front of the batch's slots, more than slots as a rule (mp3mi_feed_create_lanes): ticks go through
+        Feed.tick_lanes then.  max_rows: the most lanes that push in one tick (None: lanes); ring_samples: a lane's FIFO (0: the
+        least, tick_frames * 1152 + max_push)."""
+        return Feed(self, tick_frames, max_push, lanes, max_rows, ring_samples)
 
     def set_mode(self, mode):
         """0 stereo, 2 dual channel, 3 mono (the reference's -m s|d|m); joint stereo is refused as in the reference"""
@@ -412,17 +419,56 @@ class Batch:
 
 
 class Feed:
-    """The feeder of a Batch (include/mp3mi.h, mp3mi_feed_*): a device FIFO per slot, so that every stream may bring any number
-    of samples per call.  Lane s is slot s.  Made by Batch.feeder()."""
+    """The feeder of a Batch (include/mp3mi.h, mp3mi_feed_*): a device FIFO per lane, so that every stream may bring any number
+    of samples per call.  Lane s is slot s, unless the feeder was made with lanes=: then a slot is lent to a lane for the ticks in
+    which it encodes (tick_lanes).  Made by Batch.feeder()."""
 
-    def __init__(self, batch, tick_frames, max_push):
+    def __init__(self, batch, tick_frames, max_push, lanes=None, max_rows=None, ring_samples=0):
         self.batch, self.L = batch, batch.L
         self.tick_frames, self.max_push = tick_frames, max_push
         self.h = ctypes.c_void_p()
-        rc = self.L.mp3mi_feed_create(ctypes.byref(self.h), batch.h, tick_frames, max_push)
+        if lanes is None:
+            rc = self.L.mp3mi_feed_create(ctypes.byref(self.h), batch.h, tick_frames, max_push)
+        else:
+            rc = self.L.mp3mi_feed_create_lanes(ctypes.byref(self.h), batch.h, lanes, lanes if max_rows is None else max_rows, tick_frames,
+                                                max_push, ring_samples)
         if rc != 0:
-            raise Mp3miError("mp3mi_feed_create failed with %d" % rc)
+            raise Mp3miError("mp3mi_feed_create%s failed with %d" % ("" if lanes is None else "_lanes", rc))
         batch._feed = self
+
+    @property
+    def n_lanes(self):
+        """the feeder's lanes (mp3mi_feed_n_lanes): the batch's slots unless it was made with lanes="""
+        return self.L.mp3mi_feed_n_lanes(self.h)
+
+    def tick_lanes(self, pcm, out, out_len, rows, start=None, end=None, n_push=None, kbps=None):
+        """One tick of a feeder made with lanes= (mp3mi_feed_tick_lanes).  rows: the lanes that push, strictly increasing; pcm: int16
+        cuda tensor [len(rows), pitch * C] or [len(rows), pitch, C], pitch >= max_push (None without rows); start, end, n_push, kbps:
+        per ROW, as in tick().  out [S, stride] and out_len [S] are by SLOT.  Returns the int32 array [S] of the lane that encodes
+        in each slot in this tick, -1 where none does (host bookkeeping).  Nothing is waited for."""
+        import numpy as np
+        S, C = self.batch.n_streams, self.batch.channels
+        rl = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        R = len(rl)
+        assert out.is_cuda and out_len.is_cuda and out.is_contiguous() and out.shape[0] == S
+        ctl = np.zeros(R, np.uint8)
+        if start is not None:
+            ctl |= np.asarray(start, dtype=bool).reshape(R).astype(np.uint8) * 1  # MP3MI_SLOT_START
+        if end is not None:
+            ctl |= np.asarray(end, dtype=bool).reshape(R).astype(np.uint8) * 2  # MP3MI_SLOT_END
+        ns = np.zeros(R, np.int32) if n_push is None else np.ascontiguousarray(n_push, dtype=np.int32).reshape(R)
+        kb = np.zeros(R, np.int32) if kbps is None else np.ascontiguousarray(kbps, dtype=np.int32).reshape(R)
+        pitch = 0
+        if R:
+            assert pcm.is_cuda and pcm.is_contiguous() and pcm.shape[0] == R
+            pitch = pcm.numel() // (R * C)
+        slot_lane = np.full(S, -1, np.int32)
+        rc = self.L.mp3mi_feed_tick_lanes(self.h, R, rl.ctypes.data if R else None, pcm.data_ptr() if R else None, pitch,
+                                          ctl.ctypes.data if R else None, ns.ctypes.data if R else None, kb.ctypes.data if R else None,
+                                          out.data_ptr(), out.shape[1], out_len.data_ptr(), slot_lane.ctypes.data)
+        if rc != 0:
+            raise Mp3miError("mp3mi_feed_tick_lanes failed with %d" % rc)
+        return slot_lane
 
     @property
     def capacity(self):
@@ -452,10 +498,10 @@ class Feed:
             raise Mp3miError("mp3mi_feed_tick failed with %d" % rc)
 
     def lanes(self):
-        """(pending int32 [S], frames int64 [S] (-1: closed), flags uint8 [S]: 1 parked, 2 draining, 4 started but not yet in the
-        batch; lanes that are not closed) -- host bookkeeping, no device wait"""
+        """(pending int32 [n_lanes], frames int64 [n_lanes] (-1: closed), flags uint8 [n_lanes]: 1 parked, 2 draining, 4 started but not
+        yet in the batch, 8 ready and waiting for a slot; lanes that are not closed) -- host bookkeeping, no device wait"""
         import numpy as np
-        S = self.batch.n_streams
+        S = self.n_lanes
         p, f, g = np.zeros(S, np.int32), np.zeros(S, np.int64), np.zeros(S, np.uint8)
         rc = self.L.mp3mi_feed_lanes(self.h, p.ctypes.data, f.ctypes.data, g.ctypes.data)
         if rc < 0:

@@ -25,6 +25,14 @@
 // each stream moves the part of a record it wrote or will read: the state record lists the front stream's regions first
 // (park_tables), which makes the parts the bytes below and from the first loop-stream region's offset.  That costs a tick one
 // export, one import and four small launches however many lanes sit out, instead of a call per run of neighbouring lanes.
+//
+// The first half of this file is the feeder whose lane s IS slot s (mp3mi_feed_create, mp3mi_feed_tick), untouched by the second:
+// more lanes than slots (mp3mi_feed_create_lanes, mp3mi_feed_tick_lanes), with the indirection lane -> slot, the scheduler and
+// k_feed_lanes over the lanes that move.  They share the object, its buffers (feed_build: sized by lanes or by slots), the records
+// per lane and mp3mi_feed_lanes / mp3mi_feed_destroy; each kind has its own tick, and the old one allocates and launches what it did.
+
+#include <algorithm>
+#include <utility>
 
 struct mp3mi_feed {
     mp3mi_batch *b;
@@ -45,8 +53,20 @@ struct mp3mi_feed {
         bool waiting;          // ... the batch has not seen its START yet
         int64_t frames;        // frames encoded so far
         mp3mi_slot_ticket ticket;
+        // more lanes than slots (below): the slot that holds the lane's stream (an abandoned one while `waiting`), -1: none; the
+        // tick in which the lane's unbroken spell of being ready began, -1: it was not ready in the last tick, or encoded in it
+        bool wait_slot;    // ready in the last tick and left without a slot
+        bool seen, chosen; // (within a tick) among the tick's lanes; encodes in this tick
+        int32_t slot;
+        int64_t since;
     };
     std::vector<lane> lanes;
+    // more lanes than slots (mp3mi_feed_create_lanes; the second half of this file)
+    bool lanes_mode;
+    int n_lanes, max_rows;
+    int64_t tick_no;
+    std::vector<int32_t> slot_lane; // [S]: the lane whose stream is open in the slot, -1: none
+    std::vector<int32_t> hot;       // ascending: the lanes that are ready without a push (a tick pending, or draining)
     // what goes up per tick: descriptors uint32[4 S] | park list int32[S] | resume list int32[S]; a ring of four with fences, like
     // the batch's park lists
     typedef upload_ring<uint8_t, 4> up_ring;
@@ -74,10 +94,11 @@ static void feed_release_buffers(mp3mi_feed *f)
     f->owned1 = f->owned0;
 }
 
-static int feed_build(mp3mi_feed *f)
+// n_lanes rings and records per lane; rows and the two dense record blocks per slot; up_bytes: an upload block
+static int feed_build(mp3mi_feed *f, size_t n_lanes, size_t up_bytes)
 {
     mp3mi_batch *b = f->b;
-    const size_t S = (size_t) b->n_streams, esz = 2 * (size_t) b->channels;
+    const size_t S = (size_t) b->n_streams, L = n_lanes, esz = 2 * (size_t) b->channels;
     mp3mi_park_table front, loop;
     f->state_bytes = park_tables(b, &front, &loop);
     f->front_bytes = loop.n > 0 ? loop.r[0].off : f->state_bytes;
@@ -85,18 +106,21 @@ static int feed_build(mp3mi_feed *f)
         if (front.r[k].off >= f->front_bytes) return MP3MI_ERR_ARG; // (the record's order is front stream first: carried_init)
     f->ring_pitch = ((size_t) f->cap * esz + 15) & ~(size_t) 15;
     f->row_pitch = (size_t) f->full * esz; // (a frame of one channel is 2304 bytes = 16 * 144)
-    CHK(dev_alloc(b, &f->ring, S * f->ring_pitch));
+    CHK(dev_alloc(b, &f->ring, L * f->ring_pitch));
     CHK(dev_alloc(b, &f->rows, S * f->row_pitch));
     CHK(hipMemset(f->rows, 0, S * f->row_pitch));
-    CHK(dev_alloc(b, &f->rec_front, S * f->front_bytes));
-    CHK(dev_alloc(b, &f->rec_loop, S * (f->state_bytes - f->front_bytes)));
+    CHK(dev_alloc(b, &f->rec_front, L * f->front_bytes));
+    CHK(dev_alloc(b, &f->rec_loop, L * (f->state_bytes - f->front_bytes)));
     CHK(dev_alloc(b, &f->park_block, S * f->state_bytes));
     CHK(dev_alloc(b, &f->resume_block, S * f->state_bytes));
-    for (mp3mi_feed::up_ring::entry &en : f->up.e) CHK(ring_entry_create(b, en, 24 * S));
+    for (mp3mi_feed::up_ring::entry &en : f->up.e) CHK(ring_entry_create(b, en, up_bytes));
     CHK(hipEventCreateWithFlags(&f->ev_up, hipEventDisableTiming));
     CHK(hipEventCreateWithFlags(&f->ev_front, hipEventDisableTiming));
-    f->lanes.assign(S, mp3mi_feed::lane());
-    for (mp3mi_feed::lane &l : f->lanes) l.frames = -1;
+    f->lanes.assign(L, mp3mi_feed::lane());
+    for (mp3mi_feed::lane &l : f->lanes) {
+        l.frames = l.since = -1;
+        l.slot = -1;
+    }
     return MP3MI_OK;
 }
 
@@ -114,7 +138,7 @@ extern "C" int mp3mi_feed_create(mp3mi_feed **out, mp3mi_batch *b, int tick_fram
     f->full = tick_frames * 1152;
     f->cap = f->full + max_push;
     f->owned0 = f->owned1 = b->owned.size();
-    const int rc = feed_build(f);
+    const int rc = feed_build(f, (size_t) b->n_streams, 24 * (size_t) b->n_streams);
     f->owned1 = b->owned.size();
     if (rc != MP3MI_OK) {
         feed_release_buffers(f);
@@ -150,7 +174,7 @@ extern "C" int mp3mi_feed_lanes(const mp3mi_feed *f, int32_t *pending_host, int6
         const mp3mi_feed::lane &l = f->lanes[s];
         pending_host[s] = l.open ? l.pending : 0;
         frames_host[s] = l.open ? l.frames : -1;
-        flags_host[s] = (uint8_t) (l.open ? (l.parked ? 1 : 0) | (l.draining ? 2 : 0) | (l.waiting ? 4 : 0) : 0);
+        flags_host[s] = (uint8_t) (l.open ? (l.parked ? 1 : 0) | (l.draining ? 2 : 0) | (l.waiting ? 4 : 0) | (l.wait_slot ? 8 : 0) : 0);
         n += l.open;
     }
     return n;
@@ -159,7 +183,7 @@ extern "C" int mp3mi_feed_lanes(const mp3mi_feed *f, int32_t *pending_host, int6
 extern "C" int mp3mi_feed_tick(mp3mi_feed *f, const int16_t *pcm_dev, size_t pcm_pitch, const uint8_t *ctl_host, const int32_t *n_push_host,
                                const int32_t *kbps_host, uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev)
 {
-    if (!f || !pcm_dev || !ctl_host || !out_dev || !out_len_dev) return MP3MI_ERR_ARG;
+    if (!f || f->lanes_mode || !pcm_dev || !ctl_host || !out_dev || !out_len_dev) return MP3MI_ERR_ARG; // (lanes: mp3mi_feed_tick_lanes)
     mp3mi_batch *b = f->b;
     if (pcm_pitch < (size_t) f->max_push || out_stride < mp3mi_batch_out_stride(b, f->tick_frames)) return MP3MI_ERR_ARG;
     const int S = b->n_streams;
@@ -288,5 +312,307 @@ extern "C" int mp3mi_feed_tick(mp3mi_feed *f, const int16_t *pcm_dev, size_t pcm
         f->up.next();
     }
     f->lanes.swap(nl);
+    return MP3MI_OK;
+}
+
+// ---- more lanes than slots (mp3mi_feed_create_lanes, mp3mi_feed_tick_lanes) ----
+// A lane is no longer a slot.  Rings, records per lane, tickets and the lane table are sized by n_lanes; the rows and the two dense
+// record blocks stay sized by the batch's slots, since no more than n_streams streams encode, leave or enter in one tick.  On the
+// host the feeder keeps lane -> slot (lane::slot) and slot -> lane (slot_lane), and the HOT list: the lanes that are ready whether
+// or not they push (a tick pending, or draining).  A tick looks at the hot lanes, the lanes its rows name and the lanes in slots
+// -- never at all lanes: with 100 of 100 000 lanes pushing it touches those 100, the few that wait and the slots.
+//
+// Who encodes: the ready lanes, and with more of them than slots the n_streams whose spell of being ready began first (lane::since;
+// ties to the lower lane).  A lane that encodes ends its spell, so a lane that is ready all the time queues behind every lane that
+// was ready before it: round robin.  Where: a chosen lane keeps the slot its stream is in; every other stream in a slot leaves
+// (export with close, as a lane that sits out in mp3mi_feed_tick); the other chosen lanes take the free slots, lowest slot to
+// lowest lane, by import (parked) or by the per-slot call's START (not yet in the batch).
+//
+// A slot vacated and refilled in ONE tick.  The launches of a tick are, on each of the batch's two HIP streams and in this order:
+// the export's k_slot_park (slot regions -> park_block), the scatter (park_block -> the leaving lanes' records), the gather (the
+// entering lanes' records -> resume_block), the import's k_slot_park (resume_block -> slot regions), the per-slot call with its
+// k_slot_begin for the STARTs.  Each stream moves only the regions it owns (park_run), and a stream runs its launches in order:
+// the import or the START that writes slot k's regions on a stream is behind the export that read them on THAT stream, which is all
+// that "a record may be imported into the batch that exported it at once" (mp3mi.h) asks.  The leaving and the entering lanes of a
+// tick are different lanes, so scatter and gather touch different records; park_block and resume_block are written and read in
+// the same order tick after tick, each part on one stream only.  The rows are by slot and k_feed_lanes, their only writer, runs
+// on the front stream behind the per-slot call of the tick before, their only reader -- as k_feed does.
+//
+// The upload block of a tick: park lanes int32[S] | resume lanes int32[S] | (to a multiple of 16) | descriptors 32 bytes each, for
+// at most max_rows + S lanes that move (those that push, those that take).  The slot lists of export and import go up with those
+// calls (park_run).  One copy per tick, of the lists and the descriptors in use.
+
+static inline size_t feed_lists_bytes(const mp3mi_feed *f) { return (8 * (size_t) f->b->n_streams + 15) & ~(size_t) 15; }
+
+extern "C" int mp3mi_feed_create_lanes(mp3mi_feed **out, mp3mi_batch *b, int n_lanes, int max_rows, int tick_frames, int max_push, int ring_samples)
+{
+    if (!out) return MP3MI_ERR_ARG;
+    *out = NULL;
+    if (!b || b->feed || tick_frames < 1 || tick_frames > b->max_frames || max_push < 1 || b->book.any_open()) return MP3MI_ERR_ARG;
+    if (n_lanes < 1 || max_rows < 1 || max_rows > n_lanes || ring_samples < 0) return MP3MI_ERR_ARG;
+    const int64_t least = (int64_t) tick_frames * 1152 + max_push, cap = ring_samples ? ring_samples : least;
+    if (cap < least || cap > INT32_MAX / 8) return MP3MI_ERR_ARG; // (a lane's bytes stay far inside 32 bits)
+    ON_DEVICE(b);
+    mp3mi_feed *f = new mp3mi_feed(); // value-initialised
+    f->b = b;
+    f->lanes_mode = true;
+    f->n_lanes = n_lanes;
+    f->max_rows = max_rows;
+    f->tick_frames = tick_frames;
+    f->max_push = max_push;
+    f->full = tick_frames * 1152;
+    f->cap = (int) cap;
+    f->owned0 = f->owned1 = b->owned.size();
+    const int rc = feed_build(f, (size_t) n_lanes, feed_lists_bytes(f) + 32 * ((size_t) max_rows + (size_t) b->n_streams));
+    f->owned1 = b->owned.size();
+    if (rc != MP3MI_OK) {
+        feed_release_buffers(f);
+        feed_drop(f);
+        return rc;
+    }
+    f->slot_lane.assign((size_t) b->n_streams, -1);
+    b->feed = f;
+    *out = f;
+    return MP3MI_OK;
+}
+
+extern "C" int mp3mi_feed_n_lanes(const mp3mi_feed *f) { return f ? (int) f->lanes.size() : 0; }
+
+extern "C" int mp3mi_feed_tick_lanes(mp3mi_feed *f, int n_rows, const int32_t *row_lane_host, const int16_t *pcm_dev, size_t pcm_pitch,
+                                     const uint8_t *ctl_host, const int32_t *n_push_host, const int32_t *kbps_host, uint8_t *out_dev,
+                                     size_t out_stride, uint32_t *out_len_dev, int32_t *slot_lane_host)
+{
+    if (!f || !f->lanes_mode || !out_dev || !out_len_dev || !slot_lane_host) return MP3MI_ERR_ARG; // (no lanes: mp3mi_feed_tick)
+    mp3mi_batch *b = f->b;
+    if (n_rows < 0 || n_rows > f->max_rows || out_stride < mp3mi_batch_out_stride(b, f->tick_frames)) return MP3MI_ERR_ARG;
+    if (n_rows > 0 && (!row_lane_host || !pcm_dev || !ctl_host || !n_push_host || !kbps_host || pcm_pitch < (size_t) f->max_push)) return MP3MI_ERR_ARG;
+    const int S = b->n_streams, L = f->n_lanes;
+    const size_t esz = 2 * (size_t) b->channels;
+    typedef mp3mi_feed::lane lane;
+    // ---- 1. the rules, over all rows, before anything changes state (a lane without a row pushes nothing and breaks none) ----
+    for (int r = 0; r < n_rows; r++) {
+        const int32_t ln = row_lane_host[r];
+        if (ln < 0 || ln >= L || (r > 0 && ln <= row_lane_host[r - 1])) return MP3MI_ERR_ARG;
+        const lane &l = f->lanes[ln];
+        const int c = ctl_host[r];
+        const int32_t n = n_push_host[r], k = kbps_host[r];
+        if ((c & ~(MP3MI_SLOT_START | MP3MI_SLOT_END)) || n < 0 || n > f->max_push) return MP3MI_ERR_ARG;
+        const bool start = c & MP3MI_SLOT_START, end = c & MP3MI_SLOT_END;
+        if (l.open && l.draining && (start || end || n != 0)) return MP3MI_ERR_ARG; // its samples are all in
+        if (!l.open && !start && (end || n != 0)) return MP3MI_ERR_ARG;
+        int bi, bits;
+        // (a stream that STARTed at kbps 0 has the create-time bitrate of the slot it first encodes in: known from then on)
+        if (start ? (k != 0 && (k > b->ceil_kbps || !rate_of_kbps(b->rate_idx, k, &bi, &bits))) : (k != 0 && !(l.open && l.kbps != 0 && k == l.kbps)))
+            return MP3MI_ERR_ARG;
+        if ((int64_t) (start ? 0 : l.pending) + n > f->cap) return MP3MI_ERR_ARG;
+    }
+    // ---- 2. the lanes of this tick: the hot ones and the rows', ascending; who is ready ----
+    struct cand { int32_t ln, row, n, have, head0, pend0; bool ready, closes; };
+    std::vector<cand> cs;
+    cs.reserve(f->hot.size() + (size_t) n_rows);
+    std::vector<std::pair<int32_t, lane> > undo; // the lanes as they were, should a HIP call fail further down
+    undo.reserve(f->hot.size() + (size_t) n_rows + (size_t) S);
+    const std::vector<int32_t> slot_lane0(f->slot_lane);
+    size_t n_ready = 0;
+    for (size_t h = 0, r = 0; h < f->hot.size() || r < (size_t) n_rows;) {
+        const int32_t lh = h < f->hot.size() ? f->hot[h] : INT32_MAX, lr = r < (size_t) n_rows ? row_lane_host[r] : INT32_MAX;
+        cand c;
+        memset(&c, 0, sizeof(c));
+        c.ln = lh < lr ? lh : lr;
+        c.row = lr == c.ln ? (int32_t) r : -1;
+        h += lh == c.ln;
+        r += lr == c.ln;
+        lane &l = f->lanes[c.ln];
+        undo.push_back(std::make_pair(c.ln, l));
+        l.seen = true;
+        const int ctl = c.row >= 0 ? ctl_host[c.row] : 0;
+        c.n = c.row >= 0 ? n_push_host[c.row] : 0;
+        if (ctl & MP3MI_SLOT_START) { // a new stream; one that is open in the lane is abandoned: its samples, its record -- and its slot,
+            l.open = l.waiting = true; // where it has one, with this tick: to this lane's START if it is chosen, else by the export
+            l.parked = l.draining = false;
+            l.head = l.pending = 0;
+            l.kbps = kbps_host[c.row];
+            l.frames = 0;
+        }
+        if (!l.open) continue; // (a hot lane is open; a row on a closed lane without START brought nothing)
+        if (ctl & MP3MI_SLOT_END) l.draining = true;
+        c.head0 = l.head;
+        c.pend0 = l.pending;
+        c.have = l.pending + c.n;
+        c.closes = l.draining && c.have <= f->full;
+        c.ready = c.closes || c.have >= f->full;
+        if (c.ready && l.since < 0) l.since = f->tick_no;
+        if (!c.ready) l.since = -1;
+        n_ready += c.ready;
+        cs.push_back(c);
+    }
+    if (n_ready > (size_t) S) { // the S whose spells began first; ties to the lower lane
+        std::vector<std::pair<int64_t, int32_t> > order;
+        order.reserve(n_ready);
+        for (const cand &c : cs)
+            if (c.ready) order.push_back(std::make_pair(f->lanes[c.ln].since, c.ln));
+        std::nth_element(order.begin(), order.begin() + S, order.end());
+        for (int i = 0; i < S; i++) f->lanes[order[i].second].chosen = true;
+    } else {
+        for (const cand &c : cs)
+            if (c.ready) f->lanes[c.ln].chosen = true;
+    }
+    // ---- 3. the slots: who stays, who leaves, who enters ----
+    std::vector<int32_t> park_slots, park_lanes, resume_slots, resume_lanes, free_slots;
+    for (int s = 0; s < S; s++) {
+        const int32_t ln = f->slot_lane[s];
+        if (ln >= 0 && !f->lanes[ln].chosen) { // sits out, waits for a slot, or was abandoned for a stream that does not encode now
+            lane &l = f->lanes[ln];
+            if (!l.seen) undo.push_back(std::make_pair(ln, l)); // (a lane of no row that is not hot)
+            park_slots.push_back(s);
+            park_lanes.push_back(ln);
+            l.parked = !l.waiting;
+            l.slot = -1;
+            f->slot_lane[s] = -1;
+        }
+        if (f->slot_lane[s] < 0) free_slots.push_back(s);
+    }
+    std::vector<uint8_t> ctl((size_t) S, 0);
+    std::vector<int32_t> ns((size_t) S, 0), kb((size_t) S, 0);
+    std::vector<uint32_t> desc;
+    desc.reserve(8 * cs.size());
+    std::vector<int32_t> hot;
+    for (int s = 0; s < S; s++) slot_lane_host[s] = -1;
+    size_t most = 0, n_free = 0;
+    bool any_ready = false;
+    for (const cand &c : cs) {
+        lane &l = f->lanes[c.ln];
+        int32_t take = 0;
+        if (l.chosen) {
+            take = c.closes ? c.have : f->full;
+            if (l.slot < 0) { // the lowest free slot to the lowest lane
+                l.slot = free_slots[n_free++];
+                if (l.parked) {
+                    resume_slots.push_back(l.slot);
+                    resume_lanes.push_back(c.ln);
+                }
+            }
+            const int32_t s = l.slot;
+            any_ready = true;
+            ctl[s] = (uint8_t) ((l.waiting ? MP3MI_SLOT_START : 0) | (c.closes ? MP3MI_SLOT_END : 0));
+            ns[s] = take;
+            kb[s] = l.waiting ? l.kbps : 0;
+            if (l.waiting && l.kbps == 0) l.kbps = b->kbps_h[s];
+            slot_lane_host[s] = c.ln;
+            f->slot_lane[s] = c.closes ? -1 : c.ln;
+            l.parked = l.waiting = l.wait_slot = false;
+            l.since = -1; // a lane that is still ready begins a new spell in the next tick
+            l.frames += c.closes ? (take + 1151) / 1152 : f->tick_frames;
+        } else
+            l.wait_slot = c.ready;
+        if (c.n || take) {
+            const uint32_t d[8] = {(uint32_t) c.head0, (uint32_t) c.pend0, (uint32_t) c.n, (uint32_t) take,
+                                   (uint32_t) c.ln, (uint32_t) (c.n ? c.row : 0), (uint32_t) (take ? l.slot : 0), 0u};
+            desc.insert(desc.end(), d, d + 8);
+            const size_t longest = (size_t) (take > c.n ? take : c.n) * esz;
+            most = longest > most ? longest : most;
+        }
+        l.head = (int32_t) (((int64_t) c.head0 + take) % f->cap);
+        l.pending = c.have - take;
+        if (l.chosen && c.closes) {
+            l.open = false;
+            l.frames = -1;
+            l.slot = -1;
+        }
+        l.chosen = false;
+        if (l.open && (l.draining || l.pending >= f->full)) hot.push_back(c.ln);
+    }
+    for (const std::pair<int32_t, lane> &u : undo) f->lanes[u.first].seen = false;
+    const size_t n_active = desc.size() / 8;
+    auto fail = [&](int rc) { // the books as they were
+        for (size_t i = undo.size(); i-- > 0;) f->lanes[undo[i].first] = undo[i].second;
+        f->slot_lane = slot_lane0;
+        b->feed_call = false;
+        return rc;
+    };
+#define FCHK(call)                                                  \
+    do {                                                            \
+        if ((call) != hipSuccess) {                                 \
+            fprintf(stderr, "mp3mi: %s failed (%s:%d)\n", #call, __FILE__, __LINE__); \
+            return fail(MP3MI_ERR_HIP);                             \
+        }                                                           \
+    } while (0)
+    device_scope ds(b->device);
+    if (!ds.ok) return fail(MP3MI_ERR_HIP);
+    // ---- 4. the lists and the descriptors go up; k_feed_lanes over the lanes that move ----
+    mp3mi_feed::up_ring::entry &en = f->up.take();
+    const bool lists = !park_lanes.empty() || !resume_lanes.empty();
+    const size_t lb = feed_lists_bytes(f);
+    int32_t *park_dev = (int32_t *) en.dev, *resume_dev = park_dev + S;
+    if (n_active || lists) {
+        // The one place this call can block: the entry's readers, four ticks ago.  As a rule they are long through, and then the host
+        // neither waits nor lets a held k_loop go.  Where it must wait, the fence may be queued behind the held k_loop of the last
+        // per-slot call, which spins on its flag until the host lets it go: the host does that FIRST and waits then, so the wait ends.
+        if (!en.free.done()) {
+            hold_release(b);
+            FCHK(en.free.sync());
+        }
+        memset(en.stage, 0, lb);
+        if (!park_lanes.empty()) memcpy(en.stage, park_lanes.data(), sizeof(int32_t) * park_lanes.size());
+        if (!resume_lanes.empty()) memcpy(en.stage + 4 * (size_t) S, resume_lanes.data(), sizeof(int32_t) * resume_lanes.size());
+        if (n_active) memcpy(en.stage + lb, desc.data(), 32 * n_active);
+        FCHK(hipMemcpyAsync(en.dev, en.stage, lb + 32 * n_active, hipMemcpyHostToDevice, b->stream));
+        if (n_active) {
+            mp3mi_launch_feed_lanes(en.dev + lb, (int) n_active, f->ring, f->ring_pitch, f->cap, b->channels, pcm_dev, pcm_pitch * esz, f->rows,
+                                    f->row_pitch, most, b->stream);
+            FCHK(hipGetLastError());
+        }
+        FCHK(hipEventRecord(f->ev_up, b->stream));
+        if (lists) FCHK(hipStreamWaitEvent(b->lstream, f->ev_up, 0));
+    }
+    // the one-region tables of the records per lane: lane l's part lies at base + l * bytes
+    mp3mi_park_table tf, tl;
+    memset(&tf, 0, sizeof(tf));
+    memset(&tl, 0, sizeof(tl));
+    tf.r[0] = {f->rec_front, (uint32_t) f->front_bytes, 0u};
+    tl.r[0] = {f->rec_loop, (uint32_t) (f->state_bytes - f->front_bytes), (uint32_t) f->front_bytes};
+    tf.n = f->front_bytes ? 1 : 0;
+    tl.n = f->state_bytes > f->front_bytes ? 1 : 0;
+    std::vector<mp3mi_slot_ticket> tk(park_lanes.size() > resume_lanes.size() ? park_lanes.size() : resume_lanes.size());
+    int rc = MP3MI_OK;
+    b->feed_call = true;
+    // ---- 5. the streams that do not encode leave their slots: the SLOT list to the export, the LANE list to the scatter ----
+    if (!park_slots.empty()) {
+        rc = mp3mi_batch_slots_export(b, (int) park_slots.size(), park_slots.data(), 1, f->park_block, f->state_bytes, tk.data());
+        if (rc == MP3MI_OK) {
+            for (size_t i = 0; i < park_lanes.size(); i++) f->lanes[park_lanes[i]].ticket = tk[i];
+            mp3mi_launch_slot_park(park_dev, (int) park_lanes.size(), tf, f->park_block, f->state_bytes, 0, b->stream);
+            mp3mi_launch_slot_park(park_dev, (int) park_lanes.size(), tl, f->park_block, f->state_bytes, 0, b->lstream);
+            if (hipGetLastError() != hipSuccess) rc = MP3MI_ERR_HIP;
+        }
+    }
+    // ---- 6. the parked lanes that encode enter the free slots -- slots this tick's export vacated among them (above) ----
+    if (rc == MP3MI_OK && !resume_slots.empty()) {
+        for (size_t i = 0; i < resume_lanes.size(); i++) tk[i] = f->lanes[resume_lanes[i]].ticket;
+        mp3mi_launch_slot_park(resume_dev, (int) resume_lanes.size(), tf, f->resume_block, f->state_bytes, 1, b->stream);
+        mp3mi_launch_slot_park(resume_dev, (int) resume_lanes.size(), tl, f->resume_block, f->state_bytes, 1, b->lstream);
+        if (hipGetLastError() != hipSuccess) rc = MP3MI_ERR_HIP;
+        if (rc == MP3MI_OK)
+            rc = mp3mi_batch_slots_import(b, (int) resume_slots.size(), resume_slots.data(), f->resume_block, f->state_bytes, tk.data());
+    }
+    // ---- 7. one per-slot call on the feeder's rows: the chosen lanes' slots; every other slot is closed ----
+    if (rc == MP3MI_OK && any_ready)
+        rc = mp3mi_batch_encode_slots_kbps(b, f->rows, f->tick_frames, ctl.data(), ns.data(), kb.data(), out_dev, out_stride, out_len_dev);
+    b->feed_call = false;
+    if (rc != MP3MI_OK) return fail(rc);
+    if (!any_ready) {
+        // nothing encodes: no lengths but zeros, in stream order; and no next call's transforms will let a held k_loop go
+        hold_release(b);
+        FCHK(hipMemsetAsync(out_len_dev, 0, sizeof(uint32_t) * (size_t) S, b->lstream));
+    }
+    if (n_active || lists) { // the entry's fence behind its readers on both streams
+        FCHK(hipEventRecord(f->ev_front, b->stream));
+        FCHK(hipStreamWaitEvent(b->lstream, f->ev_front, 0));
+        FCHK(en.free.record(b->lstream));
+        f->up.next();
+    }
+#undef FCHK
+    f->hot.swap(hot);
+    f->tick_no++;
     return MP3MI_OK;
 }

@@ -210,3 +210,45 @@ extern "C" int mp3mi_debug_feed(int channels, int n_lanes, int cap, int row_samp
     D.fetch(rows, drows, S * row_pitch * C);
     return D.rc();
 }
+
+// The self-test hook mp3mi_debug_feed_lanes (include/mp3mi.h): k_feed_lanes alone, through the launcher mp3mi_feed_tick_lanes uses, on
+// given rings (one per lane), push rows and dense rows (one per slot), whole up and whole back like the hook above.  The rules the
+// feeder's scheduler keeps are checked here: a descriptor set that breaks one launches nothing.
+extern "C" int mp3mi_debug_feed_lanes(int channels, int n_active, int n_lanes, int n_push_rows, int n_slots, int cap, int row_samples,
+                                      const uint32_t *desc, int16_t *ring, size_t ring_pitch, int16_t *push, size_t push_pitch, int16_t *rows,
+                                      size_t row_pitch)
+{
+    if (!have_device()) return MP3MI_ERR_NO_DEVICE;
+    if ((channels != 1 && channels != 2) || n_active <= 0 || n_lanes <= 0 || n_push_rows <= 0 || n_slots <= 0 || n_active > n_lanes || cap <= 0 ||
+        row_samples <= 0 || !desc || !ring || !push || !rows)
+        return MP3MI_ERR_ARG;
+    const size_t C = (size_t) channels, esz = 2 * C, A = (size_t) n_active;
+    if (ring_pitch < (size_t) cap || row_pitch < (size_t) row_samples || push_pitch == 0 || ring_pitch * esz % 16 != 0 || row_pitch * esz % 16 != 0)
+        return MP3MI_ERR_ARG;
+    std::vector<char> lane_seen((size_t) n_lanes, 0), row_seen((size_t) n_push_rows, 0), slot_seen((size_t) n_slots, 0);
+    size_t most = 0;
+    for (size_t i = 0; i < A; i++) {
+        const uint32_t *d = desc + 8 * i;
+        const uint64_t head = d[0], pending = d[1], n_push = d[2], take = d[3];
+        if (head >= (uint64_t) cap || pending + n_push > (uint64_t) cap || take > pending + n_push || take > (uint64_t) row_samples || n_push > push_pitch)
+            return MP3MI_ERR_ARG;
+        if (d[4] >= (uint32_t) n_lanes || d[5] >= (uint32_t) n_push_rows || d[6] >= (uint32_t) n_slots || d[7] != 0) return MP3MI_ERR_ARG;
+        if (lane_seen[d[4]] || (n_push && row_seen[d[5]]) || (take && slot_seen[d[6]])) return MP3MI_ERR_ARG;
+        lane_seen[d[4]] = 1;
+        if (n_push) row_seen[d[5]] = 1;
+        if (take) slot_seen[d[6]] = 1;
+        const size_t longest = (size_t) (take > n_push ? take : n_push) * esz;
+        most = longest > most ? longest : most;
+    }
+    const size_t n_ring = (size_t) n_lanes * ring_pitch * C, n_pushed = (size_t) n_push_rows * push_pitch * C, n_rows = (size_t) n_slots * row_pitch * C;
+    hook_bufs D;
+    const uint32_t *ddesc = D.copy_of(desc, 8 * A);
+    int16_t *dring = D.copy_of(ring, n_ring), *dpush = D.copy_of(push, n_pushed), *drows = D.copy_of(rows, n_rows);
+    if (!D.ok) return D.rc();
+    mp3mi_launch_feed_lanes(ddesc, n_active, dring, ring_pitch * esz, cap, channels, dpush, push_pitch * esz, drows, row_pitch * esz, most, 0);
+    D.sync();
+    D.fetch(ring, dring, n_ring);
+    D.fetch(push, dpush, n_pushed);
+    D.fetch(rows, drows, n_rows);
+    return D.rc();
+}

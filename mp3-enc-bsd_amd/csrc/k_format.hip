@@ -731,19 +731,10 @@ MP3MI_DEVFN void feed_copy(uint8_t *dst, const uint8_t *src, size_t n, size_t la
     }
 }
 
-// Workgroup (s, y): lane s -- its descriptor {head, pending, n_push, take} is one uniform 16-byte load -- and every
-// gridDim.y-th vector of each of its copies.  esz: bytes of a sample of all channels; cap: the ring's samples; the three pitches
-// in bytes (rows and rings: multiples of 16 from 16-byte aligned bases; the push rows: the caller's).  No LDS: nothing is reused.
-__global__ void __launch_bounds__(256) k_feed(const uint4 *__restrict__ desc, uint8_t *ring, size_t ring_pitch, unsigned cap, unsigned esz,
-                                              const uint8_t *__restrict__ push, size_t push_pitch, uint8_t *__restrict__ rows, size_t row_pitch)
+// The five copies of one lane (above): its ring rg of cap samples, its row and its push row ps.
+MP3MI_DEVFN void feed_move(uint8_t *rg, uint8_t *row, const uint8_t *ps, size_t head, size_t pending, size_t n_push, size_t take, size_t cap,
+                           size_t esz, size_t lane, size_t step)
 {
-    const size_t s = blockIdx.x;
-    const uint4 d = desc[s];
-    const size_t head = d.x, pending = d.y, n_push = d.z, take = d.w;
-    if (n_push == 0 && take == 0) return;
-    const size_t lane = (size_t) blockIdx.y * 256 + threadIdx.x, step = (size_t) 256 * gridDim.y;
-    uint8_t *rg = ring + s * ring_pitch, *row = rows + s * row_pitch;
-    const uint8_t *ps = push + s * push_pitch;
     const size_t from_ring = take < pending ? take : pending; // the row's samples that come out of the ring
     const size_t from_push = take - from_ring;                // ... and out of the push
     const size_t r1 = from_ring < cap - head ? from_ring : cap - head;
@@ -756,15 +747,62 @@ __global__ void __launch_bounds__(256) k_feed(const uint4 *__restrict__ desc, ui
     feed_copy(rg, ps + (from_push + a1) * esz, (n_app - a1) * esz, lane, step);
 }
 
+// Workgroup (s, y): lane s -- its descriptor {head, pending, n_push, take} is one uniform 16-byte load -- and every
+// gridDim.y-th vector of each of its copies.  esz: bytes of a sample of all channels; cap: the ring's samples; the three pitches
+// in bytes (rows and rings: multiples of 16 from 16-byte aligned bases; the push rows: the caller's).  No LDS: nothing is reused.
+__global__ void __launch_bounds__(256) k_feed(const uint4 *__restrict__ desc, uint8_t *ring, size_t ring_pitch, unsigned cap, unsigned esz,
+                                              const uint8_t *__restrict__ push, size_t push_pitch, uint8_t *__restrict__ rows, size_t row_pitch)
+{
+    const size_t s = blockIdx.x;
+    const uint4 d = desc[s];
+    const size_t head = d.x, pending = d.y, n_push = d.z, take = d.w;
+    if (n_push == 0 && take == 0) return;
+    const size_t lane = (size_t) blockIdx.y * 256 + threadIdx.x, step = (size_t) 256 * gridDim.y;
+    feed_move(ring + s * ring_pitch, rows + s * row_pitch, push + s * push_pitch, head, pending, n_push, take, cap, esz, lane, step);
+}
+
+static size_t feed_grid_y(size_t most_bytes)
+{
+    const size_t per_wg = (size_t) 256 * 16 * 4; // four stores per lane of the longest copy
+    const size_t ny = (most_bytes + per_wg - 1) / per_wg;
+    return ny < 1 ? 1 : ny > 8 ? 8 : ny;
+}
+
 void mp3mi_launch_feed(const void *desc, int n_lanes, int16_t *ring, size_t ring_pitch_bytes, int cap, int channels, const int16_t *push,
                        size_t push_pitch_bytes, int16_t *rows, size_t row_pitch_bytes, size_t most_bytes, hipStream_t st)
 {
     if (n_lanes <= 0) return;
-    const size_t per_wg = (size_t) 256 * 16 * 4; // four stores per lane of the longest copy
-    size_t ny = (most_bytes + per_wg - 1) / per_wg;
-    ny = ny < 1 ? 1 : ny > 8 ? 8 : ny;
-    hipLaunchKernelGGL(k_feed, dim3((unsigned) n_lanes, (unsigned) ny), dim3(256), 0, st, (const uint4 *) desc, (uint8_t *) ring, ring_pitch_bytes,
-                       (unsigned) cap, (unsigned) (2 * channels), (const uint8_t *) push, push_pitch_bytes, (uint8_t *) rows, row_pitch_bytes);
+    hipLaunchKernelGGL(k_feed, dim3((unsigned) n_lanes, (unsigned) feed_grid_y(most_bytes)), dim3(256), 0, st, (const uint4 *) desc, (uint8_t *) ring,
+                       ring_pitch_bytes, (unsigned) cap, (unsigned) (2 * channels), (const uint8_t *) push, push_pitch_bytes, (uint8_t *) rows,
+                       row_pitch_bytes);
+}
+
+// ---- more lanes than slots (mp3mi_feed_tick_lanes) ----
+// k_feed_lanes is k_feed over a LIST: workgroup (i, y) works on the i-th lane that moves in the tick -- one that pushes, takes or
+// both -- and nothing is launched for the lanes that do neither, however many there are.  Its descriptor is 32 bytes, one uniform
+// load: {head, pending, n_push, take | lane, push_row, slot, 0}.  The ring is the lane's; the push is row push_row of the caller's
+// buffer (the caller brings a row per pushing lane, not per lane); the row that is cut is the SLOT's in which the lane encodes
+// this tick (unused when take is 0: a lane that only pushes, or waits for a slot, has none).  Two descriptors of a launch never
+// name the same lane, slot (with take > 0) or push row (with n_push > 0) -- the host's scheduler guarantees it -- so with the
+// ring's rule (above) no workgroup writes what another reads or writes.  The same five copies: feed_move.  No LDS.
+__global__ void __launch_bounds__(256) k_feed_lanes(const uint4 *__restrict__ desc, uint8_t *ring, size_t ring_pitch, unsigned cap, unsigned esz,
+                                                    const uint8_t *__restrict__ push, size_t push_pitch, uint8_t *__restrict__ rows, size_t row_pitch)
+{
+    const uint4 d = desc[2 * (size_t) blockIdx.x], w = desc[2 * (size_t) blockIdx.x + 1];
+    const size_t head = d.x, pending = d.y, n_push = d.z, take = d.w;
+    if (n_push == 0 && take == 0) return;
+    const size_t lane = (size_t) blockIdx.y * 256 + threadIdx.x, step = (size_t) 256 * gridDim.y;
+    feed_move(ring + (size_t) w.x * ring_pitch, rows + (size_t) w.z * row_pitch, push + (size_t) w.y * push_pitch, head, pending, n_push, take, cap,
+              esz, lane, step);
+}
+
+void mp3mi_launch_feed_lanes(const void *desc, int n_active, int16_t *ring, size_t ring_pitch_bytes, int cap, int channels, const int16_t *push,
+                             size_t push_pitch_bytes, int16_t *rows, size_t row_pitch_bytes, size_t most_bytes, hipStream_t st)
+{
+    if (n_active <= 0) return;
+    hipLaunchKernelGGL(k_feed_lanes, dim3((unsigned) n_active, (unsigned) feed_grid_y(most_bytes)), dim3(256), 0, st, (const uint4 *) desc,
+                       (uint8_t *) ring, ring_pitch_bytes, (unsigned) cap, (unsigned) (2 * channels), (const uint8_t *) push, push_pitch_bytes,
+                       (uint8_t *) rows, row_pitch_bytes);
 }
 
 // the last MP3MI_PCM_HIST samples of the call (a frame has 1152 > MP3MI_PCM_HIST) are the next call's history

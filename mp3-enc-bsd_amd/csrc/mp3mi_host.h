@@ -181,6 +181,12 @@ void mp3mi_launch_rows_out(const int32_t *row_slot, int n_rows, const uint8_t *o
    with pitches that are multiples of 16; most_bytes: the longest copy of any lane (sizes the workgroups per lane) */
 void mp3mi_launch_feed(const void *desc, int n_lanes, int16_t *ring, size_t ring_pitch_bytes, int cap, int channels, const int16_t *push,
                        size_t push_pitch_bytes, int16_t *rows, size_t row_pitch_bytes, size_t most_bytes, hipStream_t st);
+/* k_feed_lanes (mp3mi_feed_tick_lanes): k_feed over the n_active lanes that move in a tick.  Per entry a descriptor of eight uint32
+   {head, pending, n_push, take, lane, push_row, slot, 0}: the ring is ring + lane * pitch, the push row push + push_row * pitch, the
+   row that is cut rows + slot * pitch (unused when take is 0).  The rules of k_feed per descriptor, and no lane, no slot of a
+   taking entry and no push row of a pushing entry twice in a launch: checked on the host */
+void mp3mi_launch_feed_lanes(const void *desc, int n_active, int16_t *ring, size_t ring_pitch_bytes, int cap, int channels, const int16_t *push,
+                             size_t push_pitch_bytes, int16_t *rows, size_t row_pitch_bytes, size_t most_bytes, hipStream_t st);
 /* status[s] = the status word of stream s (a gather out of the strided state records) */
 void mp3mi_launch_status_gather(int n_streams, const int32_t *loop_state, int loop_state_words, int32_t *status, hipStream_t st);
 /* the reverse, for the streams a flush ended: their status words go back into the cleared state records, marked as reported */

@@ -8,10 +8,18 @@ of a run), three scenarios (--scenario):
   b   48 kHz packets of 960 samples, 38 or 39 packets a tick at random (a tick is 38.4): lanes run short and sit out.  (38.5 on
       average: a lane's backlog creeps up by a tenth of a packet per tick, so the lanes are sized for two ticks' packets)
   c   half of the lanes (the odd ones) push nothing every other tick: they are short then, parked, and resume the tick after
+  d   (--lanes N) more lanes than slots, mp3mi_feed_tick_lanes: N lanes in front of the slots, 48 kHz, every lane pushes one packet a
+      tick (--packet samples; default a tick's samples / (N / streams), so that streams lanes become ready in every tick and every
+      slot changes hands in every tick: with N = 8 x streams each lane is ready every 8th tick).  The lanes START staggered over
+      the first N / streams ticks, which are not timed.  Beside it the plain mp3mi_batch_encode_slots tick (the floor).  Reports
+      the lanes that waited for a slot per tick as well.
+  --host-time ROWS   (with --lanes N) the host time of mp3mi_feed_tick_lanes per call, wall clock around the call with nothing
+      waited for and the device idle before it: ROWS lanes of N bring a one-call file of a tick each, 50 ticks; reported for N and
+      for 4096 lanes, and their ratio.  Use a small batch (--streams 128 --frames 1): the rings are N times a tick.
 Prints one JSON line per run: ms per tick, the parks and resumes per tick (from mp3mi_feed_lanes, host bookkeeping), the bytes
 k_feed moves per tick (read + written, from the descriptors' arithmetic) and the library's source hash.
 
-usage: feed_bench.py [--scenario a|b|c] [--ticks 20] [--frames 32] [--streams 4096] [--reps 3]"""
+usage: feed_bench.py [--scenario a|b|c] [--lanes N [--packet P] [--host-time ROWS]] [--ticks 20] [--frames 32] [--streams 4096] [--reps 3]"""
 import argparse
 import importlib
 import json
@@ -31,9 +39,14 @@ def main():
     ap.add_argument("--frames", type=int, default=32)
     ap.add_argument("--streams", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=3, help="runs; the fastest counts (one more warms up)")
+    ap.add_argument("--lanes", type=int, default=0, help="scenario d: that many lanes in front of the slots")
+    ap.add_argument("--packet", type=int, default=0, help="scenario d: samples a lane pushes per tick")
+    ap.add_argument("--host-time", type=int, default=0, help="with --lanes: rows per tick of the host-time measurement")
     a = ap.parse_args()
     import torch
     mp3 = importlib.import_module("mp3-enc-bsd_amd")
+    if a.lanes:
+        return host_time(a, torch, mp3) if a.host_time else lanes(a, torch, mp3)
     S, nf, ch, kbps, T = a.streams, a.frames, 2, 128, a.ticks
     rate = 48000 if a.scenario == "b" else 44100
     full = nf * 1152
@@ -106,6 +119,107 @@ def main():
     print(json.dumps(dict(tool="feed_bench", scenario=a.scenario, streams=S, frames_per_tick=nf, ticks=T, rate=rate, channels=ch, kbps=kbps,
                           max_push=max_push, **res, source_hash=L.mp3mi_source_hash().decode(), version=L.mp3mi_version().decode())))
     b.close()
+
+
+def lanes(a, torch, mp3):
+    """scenario d"""
+    S, N, nf, ch, kbps, T, rate = a.streams, a.lanes, a.frames, 2, 128, a.ticks, 48000
+    full = nf * 1152
+    ratio = max(N // S, 1)
+    packet = a.packet or full // ratio
+    dev = torch.device("cuda:0")
+    pcm = torch.empty((N, packet * ch), dtype=torch.int16, device=dev)
+    row = torch.empty((S, full * ch), dtype=torch.int16, device=dev)
+    torch.cuda.synchronize()
+    mp3.synth_pcm_device(pcm, packet, ch, rate)
+    mp3.synth_pcm_device(row, full, ch, rate)
+    b = mp3.Batch(S, rate, ch, kbps, nf)
+    out = torch.zeros((S, b.out_stride(nf)), dtype=torch.uint8, device=dev)
+    out_len = torch.zeros(S, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    every = np.ones(S, bool)
+    all_lanes = np.arange(N, dtype=np.int32)
+    phase = all_lanes % ratio
+    res, stats = {}, {}
+
+    def run_feed():
+        feed = b.feeder(nf, packet, lanes=N, ring_samples=full + 2 * packet)
+        parked = np.zeros(N, bool)
+        parks = resumes = waited = encoded = 0
+        t0 = None
+        for t in range(ratio + T):
+            if t == ratio:  # every lane has STARTed and the first are ready: the timed ticks begin
+                b.sync()
+                t0 = time.perf_counter()
+            if t < ratio:
+                rows = all_lanes[phase <= t]
+                sl = feed.tick_lanes(pcm[:len(rows)], out, out_len, rows, start=phase[rows] == t, n_push=np.full(len(rows), packet, np.int32))
+            else:
+                sl = feed.tick_lanes(pcm, out, out_len, all_lanes, n_push=np.full(N, packet, np.int32))
+                g = feed.lanes()[2]
+                now = (g & 1).astype(bool)
+                parks += int((now & ~parked).sum())
+                resumes += int((parked & ~now).sum())
+                parked = now
+                waited += int(((g & 8) != 0).sum())
+                encoded += int((sl >= 0).sum())
+        b.sync()
+        ms = (time.perf_counter() - t0) * 1e3 / T
+        feed.close()
+        stats.update(parks_per_tick=round(parks / T, 1), resumes_per_tick=round(resumes / T, 1), waited_per_tick=round(waited / T, 1),
+                     encoded_per_tick=round(encoded / T, 1))
+        return ms
+
+    def run_slots():
+        b.encode_slots(row, nf, out, out_len, start=every)
+        b.sync()
+        t0 = time.perf_counter()
+        for _ in range(T):
+            b.encode_slots(row, nf, out, out_len)
+        b.sync()
+        ms = (time.perf_counter() - t0) * 1e3 / T
+        b.reset()
+        return ms
+
+    for name, fn in (("feed_lanes", run_feed), ("slots_continue", run_slots)):
+        res[name + "_ms"] = round(min([fn() for _ in range(a.reps + 1)][1:]), 3)
+    L = mp3.lib()
+    print(json.dumps(dict(tool="feed_bench", scenario="d", streams=S, lanes=N, packet=packet, frames_per_tick=nf, ticks=T, rate=rate, channels=ch,
+                          kbps=kbps, **res, **stats, source_hash=L.mp3mi_source_hash().decode(), version=L.mp3mi_version().decode())))
+    b.close()
+
+
+def host_time(a, torch, mp3):
+    """wall clock around mp3mi_feed_tick_lanes, the device idle before each call"""
+    S, nf, ch, kbps, rate, R, T = a.streams, a.frames, 2, 128, 48000, a.host_time, 50
+    full = nf * 1152
+    dev = torch.device("cuda:0")
+    pcm = torch.empty((R, full * ch), dtype=torch.int16, device=dev)
+    torch.cuda.synchronize()
+    mp3.synth_pcm_device(pcm, full, ch, rate)
+    res = {}
+    for N in (a.lanes, 4096):
+        b = mp3.Batch(S, rate, ch, kbps, nf)
+        out = torch.zeros((S, b.out_stride(nf)), dtype=torch.uint8, device=dev)
+        out_len = torch.zeros(S, dtype=torch.int32, device=dev)
+        feed = b.feeder(nf, full, lanes=N, max_rows=R)
+        one = np.ones(R, bool)
+        n = np.full(R, full, np.int32)
+        us = []
+        for t in range(T + 5):
+            rows = np.sort((np.arange(R, dtype=np.int64) * (N // R) + t * 37) % N).astype(np.int32)  # spread over the lane table
+            b.sync()
+            t0 = time.perf_counter()
+            feed.tick_lanes(pcm, out, out_len, rows, start=one, end=one, n_push=n)
+            us.append((time.perf_counter() - t0) * 1e6)
+        b.sync()
+        feed.close()
+        b.close()
+        res["us_per_call_%d" % N] = round(float(np.median(us[5:])), 1)
+    L = mp3.lib()
+    print(json.dumps(dict(tool="feed_bench", scenario="host_time", streams=S, rows=R, frames_per_tick=nf, **res,
+                          ratio=round(res["us_per_call_%d" % a.lanes] / res["us_per_call_4096"], 3),
+                          source_hash=L.mp3mi_source_hash().decode(), version=L.mp3mi_version().decode())))
 
 
 if __name__ == "__main__":
