@@ -429,11 +429,12 @@ MP3MI_DEVFN unsigned loop_cell_of_word(unsigned xy, int ylen2, int dB2)
     return idx;
 #endif
 }
-// One step of a walk: the 64 pairs [w, w + 64) of a region, a pair word xy per lane.  LAST: the region's last step, which can reach past
-// its end -- `inside` says whether this lane's pair still belongs to it; the others are priced as some cell all the same and masked out
-// of the sums (a conditional load costs three scalar instructions and two branches per step).
-template <bool ESC, bool NC3, bool LAST>
-MP3MI_DEVFN void loop_walk_step(const uint16_t *GL, unsigned xy, bool inside, int ylen2, int dB2, int lb01, const loop_walk_k &K, int &s01, int &s2)
+// A step of a walk: the 64 pairs [w, w + 64) of a region, a pair word xy per lane, in the two halves that each follow an LDS read -- the
+// cell's address from the pair word, the sums from the cell.  LAST: the region's last step, which can reach past its end -- `inside`
+// says whether this lane's pair still belongs to it; the others are priced as some cell all the same and masked out of the sums (a
+// conditional load costs three scalar instructions and two branches per step).
+template <bool ESC, bool LAST>
+MP3MI_DEVFN unsigned loop_walk_cell(unsigned xy, bool inside, int ylen2, int dB2, const loop_walk_k &K)
 {
     unsigned at;
     if (ESC) { // values above 15 occur: clamped (which also keeps a pair past the end inside the table, whatever the padding holds)
@@ -450,12 +451,51 @@ MP3MI_DEVFN void loop_walk_step(const uint16_t *GL, unsigned xy, bool inside, in
         if (LAST) xy = inside ? xy : 0u;
         at = loop_cell_of_word(xy, ylen2, dB2);
     }
-    unsigned e = *(const uint16_t *) ((const char *) GL + at);
+    return at;
+}
+template <bool ESC, bool NC3, bool LAST>
+MP3MI_DEVFN void loop_walk_add(unsigned e, bool inside, int lb01, const loop_walk_k &K, int &s01, int &s2)
+{
     if (LAST) e = inside ? e : 0u;
     int c = (int) (((e << 11) | e) & K.m1f); // candidate 0's length | candidate 1's << 16: a shift-or and a mask
     if (ESC) c += (int) ((e >> 10) & 3u) * lb01; // (how many of x, y are escapes: in the cell, tables_host.cpp)
     s01 += c;
     if (NC3) s2 += (int) (e >> 10); // (a cell's bit 15 is clear: the third length needs no mask)
+}
+template <bool ESC, bool NC3, bool LAST>
+MP3MI_DEVFN void loop_walk_step(const uint16_t *GL, unsigned xy, bool inside, int ylen2, int dB2, int lb01, const loop_walk_k &K, int &s01, int &s2)
+{
+    const unsigned at = loop_walk_cell<ESC, LAST>(xy, inside, ylen2, dB2, K);
+    loop_walk_add<ESC, NC3, LAST>(*(const uint16_t *) ((const char *) GL + at), inside, lb01, K, s01, s2);
+}
+
+// A region of N steps, the last one masked, as TWO trips to LDS and not two per step: every pair word is asked for before the first
+// cell address is formed, every cell before the first sum.  The instructions are the steps' own, in another order, less the tests
+// between the steps; the compiler joins pair reads and the steps' sums.  What the step gains by is those fewer instructions -- the
+// waits it saves pass under the other wavefronts' instructions either way (profiles/r13_experiments.txt, K2-K5).
+template <bool ESC, bool NC3, int N>
+MP3MI_DEVFN void loop_walk_n(const uint16_t *GL, const unsigned *p, int lane, int rest, int ylen2, int dB2, int lb01, const loop_walk_k &K, int &s01, int &s2)
+{
+    unsigned xy[N], at[N], e[N];
+#pragma unroll
+    for (int k = 0; k < N; k++) xy[k] = p[64 * k];
+    const bool inside = lane < rest; // of the last step: 1 .. 64 pairs
+#pragma unroll
+    for (int k = 0; k < N - 1; k++) at[k] = loop_walk_cell<ESC, false>(xy[k], true, ylen2, dB2, K);
+    at[N - 1] = loop_walk_cell<ESC, true>(xy[N - 1], inside, ylen2, dB2, K);
+#pragma unroll
+    for (int k = 0; k < N; k++) e[k] = *(const uint16_t *) ((const char *) GL + at[k]);
+#pragma unroll
+    for (int k = 0; k < N - 1; k++) loop_walk_add<ESC, NC3, false>(e[k], true, lb01, K, s01, s2);
+    loop_walk_add<ESC, NC3, true>(e[N - 1], inside, lb01, K, s01, s2);
+}
+
+MP3MI_DEVFN int loop_opaque_s(int v) // a wave-uniform value the compiler knows nothing about
+{
+#if !defined(MP3MI_EMU)
+    asm volatile("" : "+s"(v));
+#endif
+    return v;
 }
 
 template <bool ESC, bool NC3>
@@ -463,22 +503,27 @@ MP3MI_DEVFN void loop_region_walk(const uint16_t *GL, const unsigned *ixw, int l
 {
     const int ylen2 = 2 * ((dA >> 15) & 31), dB2 = 2 * dB, lb01 = ((dA >> 20) & 15) | (((dA >> 24) & 15) << 16);
     int s01 = 0, s2 = 0;
-    // Up to four whole steps of 64 pairs (a region holds at most 288) and a last, partial one: written out, every step at a constant
-    // offset from the lane's first pair -- as a loop each step paid a pointer increment and two scalar additions of bookkeeping.
     const unsigned *p = ixw + (lo >> 1) + lane; // this lane's pair of the first step
-    const int span = hi > lo ? hi - lo : 0, nfull = span >> 7, rest = (span & 127) >> 1; // (lo, hi even; a walk only runs on a region that holds a value: lo < hi)
-    if (nfull > 0) {
-        loop_walk_step<ESC, NC3, false>(GL, p[0], true, ylen2, dB2, lb01, K, s01, s2);
-        if (nfull > 1) {
-            loop_walk_step<ESC, NC3, false>(GL, p[64], true, ylen2, dB2, lb01, K, s01, s2);
-            if (nfull > 2) {
-                loop_walk_step<ESC, NC3, false>(GL, p[128], true, ylen2, dB2, lb01, K, s01, s2);
-                if (nfull > 3) loop_walk_step<ESC, NC3, false>(GL, p[192], true, ylen2, dB2, lb01, K, s01, s2);
+    // Steps of 64 pairs, every step at a constant offset from the lane's first pair; the last one is masked -- pairs past the end of
+    // the region are read all the same (L.ix is padded) and left out of the sums.  One to four steps (a long block's regions: at most
+    // 221 pairs) are written out by their number, reads first (loop_walk_n); the fifth that region 1 of a start / stop block can
+    // take follows step by step.  The number of steps is never formed: the region's pairs are compared with the step boundaries,
+    // one step -- regions 0 and 1 of every long block -- first, and what is left of them for the last step is its mask.
+    // (the count behind an optimisation barrier after the first test: the chain of tests stays a chain of scalar branches, where the
+    // compiler would build a switch and then flags to leave it by)
+    int np = hi > lo ? (hi - lo) >> 1 : 0; // (lo, hi even; a walk only runs on a region that holds a value: lo < hi)
+    if (__builtin_expect(np <= 64, 1)) loop_walk_n<ESC, NC3, 1>(GL, p, lane, np, ylen2, dB2, lb01, K, s01, s2);
+    else {
+        np = loop_opaque_s(np);
+        if (np <= 128) loop_walk_n<ESC, NC3, 2>(GL, p, lane, np - 64, ylen2, dB2, lb01, K, s01, s2);
+        else {
+            if (np <= 192) loop_walk_n<ESC, NC3, 3>(GL, p, lane, np - 128, ylen2, dB2, lb01, K, s01, s2);
+            else { // (a fifth step: the fourth is whole)
+                loop_walk_n<ESC, NC3, 4>(GL, p, lane, np - 192, ylen2, dB2, lb01, K, s01, s2);
+                if (np > 256) loop_walk_step<ESC, NC3, true>(GL, p[256], lane < np - 256, ylen2, dB2, lb01, K, s01, s2);
             }
         }
     }
-    // pairs past the end of the region are read all the same (L.ix is padded) and masked out of the sums
-    if (rest) loop_walk_step<ESC, NC3, true>(GL, p[64 * nfull], lane < rest, ylen2, dB2, lb01, K, s01, s2);
     *a01 = s01;
     *a2 = s2;
 }
