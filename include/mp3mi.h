@@ -357,8 +357,34 @@ int mp3mi_batch_slots_import(mp3mi_batch *b, int n, const int32_t *slots_host, c
  *     or slot_lane_host; pending + push above mp3mi_feed_capacity (a waiting lane whose FIFO is full).
  *     Status: mp3mi_batch_stream_status stays by SLOT; with the slot_lane_host of the tick it names the lane.  The status word travels
  *     in the record and an abort is reported by one sync only (above).  There is no status query per lane.
- * Not yet: Layers I and II (mp3mi_l12.h), ticks on host buffers, a status query per lane, and a direct path for a parked record between
- * a lane and a slot (the records of a tick pass through a dense block). */
+ *
+ * TICKS ON HOST BUFFERS.  A server receives packets into host memory and writes MP3 bytes from host memory.  For a feeder made by
+ * mp3mi_feed_create_lanes (for one lane per slot: n_lanes == n_streams), mp3mi_feed_tick_lanes_host_async is mp3mi_feed_tick_lanes --
+ * its rules, its scheduler, its lane bookkeeping and its refusals, word for word -- on host buffers; on a feeder made by
+ * mp3mi_feed_create it returns MP3MI_ERR_ARG.  Ticks on device buffers and on host buffers may alternate on one feeder.
+ *     Input is PACKED: pcm_host holds the tick's packets back to back, no pitch; row r's n_push_host[r] samples per channel begin at
+ *     sample sum(n_push_host[0 .. r)).  A row may push 0 samples.  Exactly sum(n_push) * channels * 2 bytes cross PCIe, in one copy;
+ *     with n_rows == 0, or every push 0, pcm_host may be NULL and nothing is uploaded.
+ *     Output is by ENCODING LANE, dense.  Filled before the call returns, without a device wait: *n_out_host (0 .. n_streams),
+ *     out_lane_host[0 .. n_out) (the lanes that encode in this tick, ascending) and out_slot_host[0 .. n_out) (the slot each encodes
+ *     in: mp3mi_batch_stream_status stays by slot, so this names the lane of a reference abort).  Row i of out_host (out_stride >=
+ *     mp3mi_batch_out_stride(b, tick_frames)) and out_len_host[i] receive what slot out_slot_host[i] would have delivered in
+ *     mp3mi_feed_tick_lanes; a row is zero behind its length.  Only n_out rows and lengths come down: the caller provides room for
+ *     n_streams of each, and rows and lengths from n_out on are not touched.  A tick in which nothing encodes downloads nothing.
+ *     Asynchronous, two ticks in flight; the third waits for the first.  The three lists are filled and the control arrays copied
+ *     before the call returns; pcm_host, out_host and out_len_host must stay valid until mp3mi_feed_host_wait for that tick, or
+ *     mp3mi_batch_sync, has returned.  Page-locked buffers (mp3mi_host_alloc) overlap with the kernels; pageable ones work and block.
+ *     MP3MI_ERR_ARG, nothing enqueued, feeder and batch unchanged: everything mp3mi_feed_tick_lanes refuses (there is no pcm_pitch);
+ *     a NULL out_host, out_len_host, out_lane_host, out_slot_host or n_out_host; a NULL pcm_host with a non-zero push.
+ *   mp3mi_feed_host_wait  waits for the upload and the download of the host tick issued ticks_back (0 or 1) HOST ticks ago and for
+ *                        nothing later.  It lets no call hold go: a host tick leaves none in force (its samples are still crossing
+ *                        PCIe when it is issued, so its kernels neither join the tick before nor are held for the next), and a
+ *                        later tick's stays.  MP3MI_ERR_ARG when there is no such tick.
+ *   mp3mi_feed_host_io_stats  over the host ticks so far, waiting for them: h2d_bytes, exactly sum(n_push) * channels * 2; d2h_bytes,
+ *                        exactly n_out * (out_stride + 4) per tick; the copies' event times; calls, the ticks.
+ * A feeder that never makes a host tick creates no stream, no event and no buffer for them.
+ * Not yet: Layers I and II (mp3mi_l12.h), a status query per lane, and a direct path for a parked record between a lane and a slot
+ * (the records of a tick pass through a dense block). */
 typedef struct mp3mi_feed mp3mi_feed;
 int mp3mi_feed_create(mp3mi_feed **out, mp3mi_batch *b, int tick_frames, int max_push);
 void mp3mi_feed_destroy(mp3mi_feed *f);
@@ -462,6 +488,13 @@ typedef struct mp3mi_host_io_stats {
     long calls;
 } mp3mi_host_io_stats;
 int mp3mi_batch_host_io_stats(mp3mi_batch *b, mp3mi_host_io_stats *st);
+/* The feeder's ticks on host buffers (TICKS ON HOST BUFFERS, above) */
+int mp3mi_feed_tick_lanes_host_async(mp3mi_feed *f, int n_rows, const int32_t *row_lane_host, const int16_t *pcm_host,
+                                     const uint8_t *ctl_host, const int32_t *n_push_host, const int32_t *kbps_host, uint8_t *out_host,
+                                     size_t out_stride, uint32_t *out_len_host, int32_t *out_lane_host, int32_t *out_slot_host,
+                                     int32_t *n_out_host);
+int mp3mi_feed_host_wait(mp3mi_feed *f, int ticks_back);
+int mp3mi_feed_host_io_stats(mp3mi_feed *f, mp3mi_host_io_stats *st);
 /* page-locked host memory for the call above, for callers that do not link HIP themselves; NULL on failure */
 void *mp3mi_host_alloc(size_t bytes);
 void mp3mi_host_free(void *p);
@@ -580,6 +613,14 @@ int mp3mi_debug_feed(int channels, int n_lanes, int cap, int row_samples, const 
 int mp3mi_debug_feed_lanes(int channels, int n_active, int n_lanes, int n_push_rows, int n_slots, int cap, int row_samples,
                            const uint32_t *desc, int16_t *ring, size_t ring_pitch, int16_t *push, size_t push_pitch, int16_t *rows,
                            size_t row_pitch);
+/* Self-test hook: k_feed_packed (csrc/k_format.hip), as mp3mi_feed_tick_lanes_host_async launches it.  As mp3mi_debug_feed_lanes, but
+ * the pushes lie in ONE buffer `packed` of n_packed samples (of all channels) and word 5 of a descriptor is its push's first sample
+ * there; the work list is built as the tick builds it, with wg_bytes as the bytes a workgroup moves (the product's: 256 * 16 * 4).
+ * MP3MI_ERR_ARG (-1), and nothing is launched, unless every descriptor keeps the rules of mp3mi_debug_feed (but for the push pitch),
+ * lane and slot are in range, the last word is 0, no lane is named twice, no slot by two descriptors that take, every push lies
+ * inside the packed buffer and no two pushes share a sample.  MP3MI_ERR_NO_DEVICE without a GPU. */
+int mp3mi_debug_feed_packed(int channels, int n_active, int n_lanes, int n_packed, int n_slots, int cap, int row_samples, size_t wg_bytes,
+                            const uint32_t *desc, int16_t *ring, size_t ring_pitch, int16_t *packed, int16_t *rows, size_t row_pitch);
 /* Self-test hook: the iteration loop on n_streams chains of n_frames frames of GIVEN records, through the three launches of the
  * drop-in iteration_loop (csrc/dropin.cpp): k_prep_tail, k_prep on the list it leaves, k_loop with no placement and no gate
  * (csrc/loop_debug.cpp; k_loop.hip is the product's).  One format per call -- rate_hz, channels, crc (error protection) -- and a

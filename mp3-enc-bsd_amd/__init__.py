@@ -120,6 +120,9 @@ def lib():
         L.mp3mi_feed_n_lanes.argtypes = [ctypes.c_void_p]
         L.mp3mi_feed_tick_lanes.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+        L.mp3mi_feed_tick_lanes_host_async.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_size_t] + [ctypes.c_void_p] * 4
+        L.mp3mi_feed_host_wait.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        L.mp3mi_feed_host_io_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.mp3mi_batch_encode_slots_host_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         L.mp3mi_batch_encode_slots_kbps_host_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
@@ -469,6 +472,65 @@ class Feed:
         if rc != 0:
             raise Mp3miError("mp3mi_feed_tick_lanes failed with %d" % rc)
         return slot_lane
+
+    def tick_lanes_host(self, pcm, out, out_len, rows, start=None, end=None, n_push=None, kbps=None):
+        """tick_lanes on host buffers (mp3mi_feed_tick_lanes_host_async).  pcm: a 1-D or 2-D int16 CPU tensor or numpy array that holds
+        the rows' samples PACKED, row r's n_push[r] samples per channel behind row r - 1's (None when nothing is pushed); out uint8
+        [S, stride] and out_len int32 or uint32 [S]: CPU tensors (page-locked ones overlap with the kernels) or numpy arrays, which
+        must stay alive and untouched until host_wait for this tick, or the batch's sync, has returned.  Returns (lanes, slots): int32
+        arrays of the lanes that encode in this tick, ascending, and the slot of each; row i of out and out_len[i] are lane
+        lanes[i]'s, and rows from len(lanes) on are not written.  Nothing is waited for."""
+        import numpy as np
+
+        def ptr(a):
+            if a is None:
+                return None
+            if isinstance(a, np.ndarray):
+                assert a.flags.c_contiguous
+                return a.ctypes.data
+            assert not a.is_cuda and a.is_contiguous()
+            return a.data_ptr()
+        S, C = self.batch.n_streams, self.batch.channels
+        rl = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        R = len(rl)
+        assert out.shape[0] == S and out_len.shape[0] == S and out.dtype.itemsize == 1 and out_len.dtype.itemsize == 4
+        ctl = np.zeros(R, np.uint8)
+        if start is not None:
+            ctl |= np.asarray(start, dtype=bool).reshape(R).astype(np.uint8) * 1  # MP3MI_SLOT_START
+        if end is not None:
+            ctl |= np.asarray(end, dtype=bool).reshape(R).astype(np.uint8) * 2  # MP3MI_SLOT_END
+        ns = np.zeros(R, np.int32) if n_push is None else np.ascontiguousarray(n_push, dtype=np.int32).reshape(R)
+        kb = np.zeros(R, np.int32) if kbps is None else np.ascontiguousarray(kbps, dtype=np.int32).reshape(R)
+        if pcm is not None:
+            assert pcm.dtype.itemsize == 2 and len(pcm.shape) in (1, 2)
+            n_have = 1
+            for d in pcm.shape:
+                n_have *= int(d)
+            assert n_have >= int(ns.sum()) * C, "pcm holds fewer samples than the rows push"
+        lanes, slots, n_out = np.full(S, -1, np.int32), np.full(S, -1, np.int32), ctypes.c_int32(0)
+        rc = self.L.mp3mi_feed_tick_lanes_host_async(self.h, R, rl.ctypes.data if R else None, ptr(pcm), ctl.ctypes.data if R else None,
+                                                     ns.ctypes.data if R else None, kb.ctypes.data if R else None, ptr(out), out.shape[1],
+                                                     ptr(out_len), lanes.ctypes.data, slots.ctypes.data, ctypes.addressof(n_out))
+        if rc != 0:
+            raise Mp3miError("mp3mi_feed_tick_lanes_host_async failed with %d" % rc)
+        return lanes[:n_out.value].copy(), slots[:n_out.value].copy()
+
+    def host_wait(self, ticks_back=0):
+        """waits until the host tick issued ticks_back host ticks ago (0: the latest, 1: the one before) has taken its samples and
+        delivered its rows, and for nothing later (mp3mi_feed_host_wait)"""
+        rc = self.L.mp3mi_feed_host_wait(self.h, ticks_back)
+        if rc != 0:
+            raise Mp3miError("mp3mi_feed_host_wait failed with %d" % rc)
+
+    def host_io_stats(self):
+        """{h2d_bytes, d2h_bytes, h2d_ms, d2h_ms, calls} over the host ticks so far (waits for them; mp3mi_feed_host_io_stats)"""
+        class S(ctypes.Structure):
+            _fields_ = [("h2d_bytes", ctypes.c_double), ("d2h_bytes", ctypes.c_double), ("h2d_ms", ctypes.c_double), ("d2h_ms", ctypes.c_double), ("calls", ctypes.c_long)]
+        st = S()
+        rc = self.L.mp3mi_feed_host_io_stats(self.h, ctypes.byref(st))
+        if rc != 0:
+            raise Mp3miError("mp3mi_feed_host_io_stats failed with %d" % rc)
+        return {k: getattr(st, k) for k, _ in S._fields_}
 
     @property
     def capacity(self):

@@ -215,8 +215,10 @@ struct mp3mi_batch {
     // and the header settings are the feeder's alone (feed_locked); feed_call: the feeder is making such a call
     struct mp3mi_feed *feed;
     bool feed_call;
+    bool feed_host_call; // ... for a tick on host buffers, whose samples are still crossing PCIe: neither joined nor held (encode_impl)
 };
 static void feed_drop(struct mp3mi_feed *f); // (feed.h, at the end of this file)
+static hipError_t feed_host_sync(struct mp3mi_feed *f); // (the feeder's own copy streams, where it has made ticks on host buffers)
 static inline bool feed_locked(const mp3mi_batch *b) { return b && b->feed && !b->feed_call; }
 
 // Device and pinned buffers of a batch: allocated here and nowhere else, so that mp3mi_batch_destroy knows them all
@@ -1241,7 +1243,7 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         // (A per-slot call on host buffers does not join: its first transforms wait for the tick's PCM to cross PCIe, and a
         // k_loop held for that long -- a tick is one chunk, so the held launch is the whole tick before -- leaves the chip idle
         // during the upload: 29.7 ms per 4096 x 32 tick against 16.4 resident.  Let go at once, that k_loop runs beside the upload.)
-        if (b->held && !y_after(v0) && !(hc && sc)) {
+        if (b->held && !y_after(v0) && !(hc && sc) && !b->feed_host_call) { // (a feeder's tick on host buffers: the same upload, the same rule)
             if (stage_x(0, 1) != MP3MI_OK) return MP3MI_ERR_HIP;
             mp3mi_launch_hold_release(b->hold_flag_d, b->hold_seq, b->stream);
             CHK(hipGetLastError());
@@ -1336,7 +1338,7 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         }
         CHK(hipMemsetAsync(b->gate_count + 1, 0, sizeof(unsigned), b->lstream));
         CHK(hipStreamWaitEvent(b->lstream, b->ev_front[v.ev], 0));
-        if (b->hold_calls && k == n_items - 1 && !(hc && sc)) { // (a per-slot call on host buffers is not held: the next one would not join, above)
+        if (b->hold_calls && k == n_items - 1 && !(hc && sc) && !b->feed_host_call) { // (a per-slot call on host buffers is not held: the next one would not join, above)
             // the call's LAST k_loop: held until the next call's first transforms are through (its first item then runs beside
             // this launch), the host lets go (hold_release), or the bound has passed: 20 ms, more for chunks so long that what the
             // front stream still holds of this item plus the next call's transforms take longer (0.4 ms per frame of a chunk)
@@ -1410,6 +1412,7 @@ extern "C" int mp3mi_batch_sync(mp3mi_batch *b)
         CHK(hipStreamSynchronize(b->hio.h2d));
         CHK(hipStreamSynchronize(b->hio.d2h));
     }
+    if (b->feed) CHK(feed_host_sync(b->feed)); // (ticks on host buffers: the same promise)
     CHK(hipGetLastError());
     // streams whose file was voided since the last sync: the reference dies on those inputs (mp3mi.h)
     unsigned voided = 0;

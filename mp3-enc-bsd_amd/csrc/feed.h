@@ -72,10 +72,37 @@ struct mp3mi_feed {
     typedef upload_ring<uint8_t, 4> up_ring;
     up_ring up;
     hipEvent_t ev_up, ev_front;
+    // ticks on host buffers (mp3mi_feed_tick_lanes_host_async; the third part of this file): two copy streams and two tick slots of
+    // the feeder's own, created with the first such tick and freed with the feeder (by hand, not through mp3mi_batch::owned, whose
+    // range [owned0, owned1) is closed at create)
+    struct host_ticks {
+        bool ready;
+        hipStream_t h2d, d2h;
+        size_t dev_stride;            // mp3mi_batch_out_stride(b, tick_frames): of tick_slot::out
+        struct tick_slot {
+            int16_t *stage;           // the tick's packets back to back: max_rows * max_push samples of all channels
+            uint8_t *out;             // [S][dev_stride]: what the per-slot call writes
+            uint32_t *len;            // [S]
+            uint8_t *out_rows;        // [n_out][the caller's out_stride]: grows with the caller's stride
+            size_t out_rows_cap;      // bytes
+            uint32_t *len_rows;       // [S]
+            fence stage_free, out_free; // the staging has been read by k_feed_packed / the dense rows by the download
+            hipEvent_t ev_enc;        // the loop stream has gathered the tick's rows (k_rows_out)
+            hipEvent_t t_up[2], t_dn[2]; // around the upload and around the download (the second is what consumers wait for)
+            bool pending, up, dn;     // a tick of this slot has not been harvested; it uploaded samples; it downloaded rows
+            double bytes_up, bytes_dn;
+        } slot[2];
+        unsigned tick_no;             // host ticks issued
+        double tot_up_bytes, tot_dn_bytes, tot_up_ms, tot_dn_ms;
+        long tot_calls;
+    } ht;
 };
+
+static void feed_host_free(mp3mi_feed *f);
 
 static void feed_drop(mp3mi_feed *f) // the handles and the object; the buffers are the batch's (mp3mi_batch::owned)
 {
+    feed_host_free(f); // (but for those of the ticks on host buffers)
     for (mp3mi_feed::up_ring::entry &en : f->up.e) en.free.destroy();
     for (hipEvent_t e : {f->ev_up, f->ev_front})
         if (e) hipEventDestroy(e);
@@ -159,6 +186,7 @@ extern "C" void mp3mi_feed_destroy(mp3mi_feed *f)
     (void) mp3mi_batch_reset(b); // the streams in the slots are abandoned with the parked and the pending ones
     b->feed_call = false;
     for (hipStream_t st : {b->stream, b->lstream}) hipStreamSynchronize(st);
+    (void) feed_host_sync(f);
     feed_release_buffers(f);
     b->feed = NULL;
     feed_drop(f);
@@ -342,7 +370,16 @@ extern "C" int mp3mi_feed_tick(mp3mi_feed *f, const int16_t *pcm_dev, size_t pcm
 // at most max_rows + S lanes that move (those that push, those that take).  The slot lists of export and import go up with those
 // calls (park_run).  One copy per tick, of the lists and the descriptors in use.
 
+//
+// A tick on host buffers (below) sends two more things up in the same block, behind the descriptors: the work list of k_feed_packed,
+// at most MP3MI_FEED_MAX_PARTS items of 8 bytes per descriptor, and the slots of the lanes that encode, int32[S], for k_rows_out.
+
 static inline size_t feed_lists_bytes(const mp3mi_feed *f) { return (8 * (size_t) f->b->n_streams + 15) & ~(size_t) 15; }
+static inline size_t feed_block_bytes(const mp3mi_feed *f)
+{
+    const size_t most_active = (size_t) f->max_rows + (size_t) f->b->n_streams;
+    return feed_lists_bytes(f) + (32 + 8 * (size_t) MP3MI_FEED_MAX_PARTS) * most_active + 4 * (size_t) f->b->n_streams;
+}
 
 extern "C" int mp3mi_feed_create_lanes(mp3mi_feed **out, mp3mi_batch *b, int n_lanes, int max_rows, int tick_frames, int max_push, int ring_samples)
 {
@@ -363,7 +400,7 @@ extern "C" int mp3mi_feed_create_lanes(mp3mi_feed **out, mp3mi_batch *b, int n_l
     f->full = tick_frames * 1152;
     f->cap = (int) cap;
     f->owned0 = f->owned1 = b->owned.size();
-    const int rc = feed_build(f, (size_t) n_lanes, feed_lists_bytes(f) + 32 * ((size_t) max_rows + (size_t) b->n_streams));
+    const int rc = feed_build(f, (size_t) n_lanes, feed_block_bytes(f));
     f->owned1 = b->owned.size();
     if (rc != MP3MI_OK) {
         feed_release_buffers(f);
@@ -378,14 +415,24 @@ extern "C" int mp3mi_feed_create_lanes(mp3mi_feed **out, mp3mi_batch *b, int n_l
 
 extern "C" int mp3mi_feed_n_lanes(const mp3mi_feed *f) { return f ? (int) f->lanes.size() : 0; }
 
-extern "C" int mp3mi_feed_tick_lanes(mp3mi_feed *f, int n_rows, const int32_t *row_lane_host, const int16_t *pcm_dev, size_t pcm_pitch,
-                                     const uint8_t *ctl_host, const int32_t *n_push_host, const int32_t *kbps_host, uint8_t *out_dev,
-                                     size_t out_stride, uint32_t *out_len_dev, int32_t *slot_lane_host)
+// What a tick on host buffers adds to a tick (mp3mi_feed_tick_lanes_host_async, below): the caller's packed samples and their count,
+// the caller's dense output with its stride, and the two lists it is told.  The tick itself -- the rules, who encodes and where, the
+// lists, the parking, the per-slot call -- is feed_tick_lanes_impl for both kinds; hc == NULL is the tick on device buffers.
+struct feed_host_call {
+    const int16_t *pcm;
+    size_t n_pushed;      // samples per channel of all rows
+    uint8_t *out;
+    size_t out_stride;
+    uint32_t *out_len;
+    int32_t *out_lane, *out_slot, *n_out;
+};
+static int feed_host_begin(mp3mi_feed *f, const feed_host_call *hc);
+
+static int feed_tick_lanes_impl(mp3mi_feed *f, int n_rows, const int32_t *row_lane_host, const int16_t *pcm_dev, size_t pcm_pitch,
+                                const uint8_t *ctl_host, const int32_t *n_push_host, const int32_t *kbps_host, uint8_t *out_dev, size_t out_stride,
+                                uint32_t *out_len_dev, int32_t *slot_lane_host, const feed_host_call *hc)
 {
-    if (!f || !f->lanes_mode || !out_dev || !out_len_dev || !slot_lane_host) return MP3MI_ERR_ARG; // (no lanes: mp3mi_feed_tick)
     mp3mi_batch *b = f->b;
-    if (n_rows < 0 || n_rows > f->max_rows || out_stride < mp3mi_batch_out_stride(b, f->tick_frames)) return MP3MI_ERR_ARG;
-    if (n_rows > 0 && (!row_lane_host || !pcm_dev || !ctl_host || !n_push_host || !kbps_host || pcm_pitch < (size_t) f->max_push)) return MP3MI_ERR_ARG;
     const int S = b->n_streams, L = f->n_lanes;
     const size_t esz = 2 * (size_t) b->channels;
     typedef mp3mi_feed::lane lane;
@@ -405,6 +452,22 @@ extern "C" int mp3mi_feed_tick_lanes(mp3mi_feed *f, int n_rows, const int32_t *r
         if (start ? (k != 0 && (k > b->ceil_kbps || !rate_of_kbps(b->rate_idx, k, &bi, &bits))) : (k != 0 && !(l.open && l.kbps != 0 && k == l.kbps)))
             return MP3MI_ERR_ARG;
         if ((int64_t) (start ? 0 : l.pending) + n > f->cap) return MP3MI_ERR_ARG;
+    }
+    // (a tick on host buffers: its copy streams and the tick slot of its turn, whose buffers stand in for the caller's device ones;
+    // row r's samples begin at sample first[r] of the slot's staging)
+    std::vector<uint32_t> first;
+    std::vector<int32_t> by_slot;
+    if (hc) {
+        const int rc = feed_host_begin(f, hc);
+        if (rc != MP3MI_OK) return rc;
+        mp3mi_feed::host_ticks::tick_slot &io = f->ht.slot[f->ht.tick_no & 1u];
+        out_dev = io.out;
+        out_stride = f->ht.dev_stride;
+        out_len_dev = io.len;
+        by_slot.assign((size_t) S, -1);
+        slot_lane_host = by_slot.data();
+        first.assign((size_t) n_rows, 0u);
+        for (int r = 1; r < n_rows; r++) first[r] = first[r - 1] + (uint32_t) n_push_host[r - 1];
     }
     // ---- 2. the lanes of this tick: the hot ones and the rows', ascending; who is ready ----
     struct cand { int32_t ln, row, n, have, head0, pend0; bool ready, closes; };
@@ -507,7 +570,7 @@ extern "C" int mp3mi_feed_tick_lanes(mp3mi_feed *f, int n_rows, const int32_t *r
             l.wait_slot = c.ready;
         if (c.n || take) {
             const uint32_t d[8] = {(uint32_t) c.head0, (uint32_t) c.pend0, (uint32_t) c.n, (uint32_t) take,
-                                   (uint32_t) c.ln, (uint32_t) (c.n ? c.row : 0), (uint32_t) (take ? l.slot : 0), 0u};
+                                   (uint32_t) c.ln, c.n ? (hc ? first[c.row] : (uint32_t) c.row) : 0u, (uint32_t) (take ? l.slot : 0), 0u};
             desc.insert(desc.end(), d, d + 8);
             const size_t longest = (size_t) (take > c.n ? take : c.n) * esz;
             most = longest > most ? longest : most;
@@ -544,7 +607,26 @@ extern "C" int mp3mi_feed_tick_lanes(mp3mi_feed *f, int n_rows, const int32_t *r
     const bool lists = !park_lanes.empty() || !resume_lanes.empty();
     const size_t lb = feed_lists_bytes(f);
     int32_t *park_dev = (int32_t *) en.dev, *resume_dev = park_dev + S;
-    if (n_active || lists) {
+    // (a tick on host buffers: the lanes that encode, ascending, and their slots -- told to the caller now, and the slots sent up
+    // for k_rows_out behind the work list of k_feed_packed)
+    mp3mi_feed::host_ticks::tick_slot *io = hc ? &f->ht.slot[f->ht.tick_no & 1u] : NULL;
+    std::vector<uint32_t> work;
+    size_t n_items = 0, n_out = 0;
+    if (hc) {
+        std::vector<std::pair<int32_t, int32_t> > enc;
+        for (int s = 0; s < S; s++)
+            if (slot_lane_host[s] >= 0) enc.push_back(std::make_pair(slot_lane_host[s], (int32_t) s));
+        std::sort(enc.begin(), enc.end());
+        n_out = enc.size();
+        for (size_t i = 0; i < n_out; i++) {
+            hc->out_lane[i] = enc[i].first;
+            hc->out_slot[i] = enc[i].second;
+        }
+        *hc->n_out = (int32_t) n_out;
+        work.resize(2 * (size_t) MP3MI_FEED_MAX_PARTS * n_active + 1);
+        n_items = mp3mi_feed_work_list(desc.data(), n_active, esz, MP3MI_FEED_WG_BYTES, work.data());
+    }
+    if (n_active || lists || n_out) {
         // The one place this call can block: the entry's readers, four ticks ago.  As a rule they are long through, and then the host
         // neither waits nor lets a held k_loop go.  Where it must wait, the fence may be queued behind the held k_loop of the last
         // per-slot call, which spins on its flag until the host lets it go: the host does that FIRST and waits then, so the wait ends.
@@ -556,8 +638,22 @@ extern "C" int mp3mi_feed_tick_lanes(mp3mi_feed *f, int n_rows, const int32_t *r
         if (!park_lanes.empty()) memcpy(en.stage, park_lanes.data(), sizeof(int32_t) * park_lanes.size());
         if (!resume_lanes.empty()) memcpy(en.stage + 4 * (size_t) S, resume_lanes.data(), sizeof(int32_t) * resume_lanes.size());
         if (n_active) memcpy(en.stage + lb, desc.data(), 32 * n_active);
-        FCHK(hipMemcpyAsync(en.dev, en.stage, lb + 32 * n_active, hipMemcpyHostToDevice, b->stream));
-        if (n_active) {
+        const size_t work_at = lb + 32 * n_active, slots_at = work_at + 8 * n_items;
+        if (n_items) memcpy(en.stage + work_at, work.data(), 8 * n_items);
+        if (n_out) memcpy(en.stage + slots_at, hc->out_slot, sizeof(int32_t) * n_out);
+        FCHK(hipMemcpyAsync(en.dev, en.stage, slots_at + sizeof(int32_t) * n_out, hipMemcpyHostToDevice, b->stream));
+        if (hc && hc->n_pushed) { // the tick's packets, as they are: one copy on the feeder's upload stream, beside whatever runs
+            FCHK(hipEventRecord(io->t_up[0], f->ht.h2d));
+            FCHK(hipMemcpyAsync(io->stage, hc->pcm, hc->n_pushed * esz, hipMemcpyHostToDevice, f->ht.h2d));
+            FCHK(hipEventRecord(io->t_up[1], f->ht.h2d));
+            FCHK(hipStreamWaitEvent(b->stream, io->t_up[1], 0));
+        }
+        if (n_active && hc) {
+            mp3mi_launch_feed_packed(en.dev + lb, en.dev + work_at, (int) n_items, f->ring, f->ring_pitch, f->cap, b->channels, io->stage, f->rows,
+                                     f->row_pitch, b->stream);
+            FCHK(hipGetLastError());
+            if (hc->n_pushed) FCHK(io->stage_free.record(b->stream));
+        } else if (n_active) {
             mp3mi_launch_feed_lanes(en.dev + lb, (int) n_active, f->ring, f->ring_pitch, f->cap, b->channels, pcm_dev, pcm_pitch * esz, f->rows,
                                     f->row_pitch, most, b->stream);
             FCHK(hipGetLastError());
@@ -596,16 +692,32 @@ extern "C" int mp3mi_feed_tick_lanes(mp3mi_feed *f, int n_rows, const int32_t *r
             rc = mp3mi_batch_slots_import(b, (int) resume_slots.size(), resume_slots.data(), f->resume_block, f->state_bytes, tk.data());
     }
     // ---- 7. one per-slot call on the feeder's rows: the chosen lanes' slots; every other slot is closed ----
+    b->feed_host_call = hc != NULL;
     if (rc == MP3MI_OK && any_ready)
         rc = mp3mi_batch_encode_slots_kbps(b, f->rows, f->tick_frames, ctl.data(), ns.data(), kb.data(), out_dev, out_stride, out_len_dev);
-    b->feed_call = false;
+    b->feed_call = b->feed_host_call = false;
     if (rc != MP3MI_OK) return fail(rc);
     if (!any_ready) {
         // nothing encodes: no lengths but zeros, in stream order; and no next call's transforms will let a held k_loop go
         hold_release(b);
-        FCHK(hipMemsetAsync(out_len_dev, 0, sizeof(uint32_t) * (size_t) S, b->lstream));
+        if (!hc) FCHK(hipMemsetAsync(out_len_dev, 0, sizeof(uint32_t) * (size_t) S, b->lstream)); // (a host tick downloads no row then)
     }
-    if (n_active || lists) { // the entry's fence behind its readers on both streams
+    if (n_out) {
+        // the download, behind the per-slot call on the loop stream: the encoding slots' bytes and lengths into dense rows of the
+        // caller's stride, by encoding lane (k_rows_out zeroes a row behind its length), and from there two plain copies on the
+        // feeder's download stream
+        mp3mi_launch_rows_out((const int32_t *) (en.dev + lb + 32 * n_active + 8 * n_items), (int) n_out, out_dev, out_stride, out_len_dev, io->out_rows,
+                              hc->out_stride, io->len_rows, b->lstream);
+        FCHK(hipGetLastError());
+        FCHK(hipEventRecord(io->ev_enc, b->lstream));
+        FCHK(hipStreamWaitEvent(f->ht.d2h, io->ev_enc, 0));
+        FCHK(hipEventRecord(io->t_dn[0], f->ht.d2h));
+        FCHK(hipMemcpyAsync(hc->out, io->out_rows, hc->out_stride * n_out, hipMemcpyDeviceToHost, f->ht.d2h));
+        FCHK(hipMemcpyAsync(hc->out_len, io->len_rows, sizeof(uint32_t) * n_out, hipMemcpyDeviceToHost, f->ht.d2h));
+        FCHK(hipEventRecord(io->t_dn[1], f->ht.d2h));
+        FCHK(io->out_free.record(f->ht.d2h));
+    }
+    if (n_active || lists || n_out) { // the entry's fence behind its readers on both streams
         FCHK(hipEventRecord(f->ev_front, b->stream));
         FCHK(hipStreamWaitEvent(b->lstream, f->ev_front, 0));
         FCHK(en.free.record(b->lstream));
@@ -614,5 +726,191 @@ extern "C" int mp3mi_feed_tick_lanes(mp3mi_feed *f, int n_rows, const int32_t *r
 #undef FCHK
     f->hot.swap(hot);
     f->tick_no++;
+    if (hc) { // the tick has taken its slot
+        io->pending = true;
+        io->up = hc->n_pushed != 0;
+        io->dn = n_out != 0;
+        io->bytes_up = (double) (hc->n_pushed * esz);
+        io->bytes_dn = (double) n_out * (double) (hc->out_stride + sizeof(uint32_t));
+        f->ht.tick_no++;
+    }
+    return MP3MI_OK;
+}
+
+extern "C" int mp3mi_feed_tick_lanes(mp3mi_feed *f, int n_rows, const int32_t *row_lane_host, const int16_t *pcm_dev, size_t pcm_pitch,
+                                     const uint8_t *ctl_host, const int32_t *n_push_host, const int32_t *kbps_host, uint8_t *out_dev,
+                                     size_t out_stride, uint32_t *out_len_dev, int32_t *slot_lane_host)
+{
+    if (!f || !f->lanes_mode || !out_dev || !out_len_dev || !slot_lane_host) return MP3MI_ERR_ARG; // (no lanes: mp3mi_feed_tick)
+    mp3mi_batch *b = f->b;
+    if (n_rows < 0 || n_rows > f->max_rows || out_stride < mp3mi_batch_out_stride(b, f->tick_frames)) return MP3MI_ERR_ARG;
+    if (n_rows > 0 && (!row_lane_host || !pcm_dev || !ctl_host || !n_push_host || !kbps_host || pcm_pitch < (size_t) f->max_push)) return MP3MI_ERR_ARG;
+    return feed_tick_lanes_impl(f, n_rows, row_lane_host, pcm_dev, pcm_pitch, ctl_host, n_push_host, kbps_host, out_dev, out_stride, out_len_dev,
+                                slot_lane_host, NULL);
+}
+
+// ---- ticks on host buffers (mp3mi_feed_tick_lanes_host_async, mp3mi_feed_host_wait, mp3mi_feed_host_io_stats) ----
+// A server has its packets in host memory and writes MP3 bytes from host memory.  The tick is the tick above; what differs is where
+// the samples come from and where the bytes go.
+//   upload stream (the feeder's)    the tick's packets, PACKED -- sum(n_push) samples, one copy -- into the tick slot's staging | event
+//   front stream                    the upload block (lists, descriptors, work list, encoding slots) | waits for that event |
+//                                   k_feed_packed: staging -> rings and rows | ... the tick as above, the per-slot call writing the
+//                                   tick slot's out [S][device stride] and len [S]
+//   loop stream                     ... behind the per-slot call's k_stream_tail: k_rows_out, the encoding slots' rows -> dense rows
+//                                   of the caller's stride, by encoding lane | event
+//   download stream (the feeder's)  waits for that event | dense rows -> out_host, lengths -> out_len_host: n_out of each
+// Orderings the tick rests on.  The rings and the rows are written by k_feed_packed and k_feed_lanes alike on the front stream only,
+// so device ticks and host ticks may alternate.  A tick slot -- staging, out, len, dense rows -- is used by every second host tick;
+// before the slot is used again the HOST has seen the fences of its last tick (staging read, rows downloaded), so no stream waits
+// for another on that account.  That wait is the one place a host tick may block beyond the upload block's; as there, the fences
+// are queried first, and only when one is not through does the host let a held k_loop go, and then wait: the download is queued
+// behind the tick's per-slot call, whose last k_loop may be the one that is held.
+static void feed_host_free(mp3mi_feed *f)
+{
+    mp3mi_feed::host_ticks &H = f->ht;
+    for (hipStream_t st : {H.h2d, H.d2h})
+        if (st) hipStreamSynchronize(st);
+    for (mp3mi_feed::host_ticks::tick_slot &io : H.slot) {
+        for (void *p : {(void *) io.stage, (void *) io.out, (void *) io.len, (void *) io.out_rows, (void *) io.len_rows})
+            if (p) hipFree(p);
+        io.stage_free.destroy();
+        io.out_free.destroy();
+        for (hipEvent_t e : {io.ev_enc, io.t_up[0], io.t_up[1], io.t_dn[0], io.t_dn[1]})
+            if (e) hipEventDestroy(e);
+    }
+    for (hipStream_t st : {H.h2d, H.d2h})
+        if (st) hipStreamDestroy(st);
+    memset(&H, 0, sizeof(H));
+}
+
+// everything the host ticks put on the feeder's own streams is through (mp3mi_batch_sync, behind the batch's streams)
+static hipError_t feed_host_sync(mp3mi_feed *f)
+{
+    for (hipStream_t st : {f->ht.h2d, f->ht.d2h})
+        if (st) {
+            const hipError_t e = hipStreamSynchronize(st);
+            if (e != hipSuccess) return e;
+        }
+    return hipSuccess;
+}
+
+// The host has seen the end of the slot's last tick: its copies are through, and their times and bytes are booked.
+static int feed_host_harvest(mp3mi_feed *f, int sl)
+{
+    mp3mi_feed::host_ticks &H = f->ht;
+    mp3mi_feed::host_ticks::tick_slot &io = H.slot[sl];
+    if (!io.pending) return MP3MI_OK;
+    if (!(io.stage_free.done() && io.out_free.done())) {
+        hold_release(f->b);
+        CHK(io.stage_free.sync());
+        CHK(io.out_free.sync());
+    }
+    float ms = 0;
+    if (io.up) {
+        CHK(hipEventSynchronize(io.t_up[1])); // (ahead of stage_free: at once)
+        CHK(hipEventElapsedTime(&ms, io.t_up[0], io.t_up[1]));
+        H.tot_up_ms += ms;
+    }
+    if (io.dn) {
+        CHK(hipEventSynchronize(io.t_dn[1]));
+        CHK(hipEventElapsedTime(&ms, io.t_dn[0], io.t_dn[1]));
+        H.tot_dn_ms += ms;
+    }
+    H.tot_up_bytes += io.bytes_up;
+    H.tot_dn_bytes += io.bytes_dn;
+    H.tot_calls++;
+    io.pending = false;
+    // (the fences stand for THAT tick: one that uploads or downloads nothing must not find them)
+    io.stage_free.recorded = io.out_free.recorded = false;
+    return MP3MI_OK;
+}
+
+// The copy streams with the first host tick, a tick slot's buffers with the first tick that takes it; then the slot's last tick is
+// waited for (at most two host ticks in flight), and the dense rows grow to the caller's stride.  What a failure leaves behind
+// goes with the feeder.
+static int feed_host_begin(mp3mi_feed *f, const feed_host_call *hc)
+{
+    mp3mi_batch *b = f->b;
+    mp3mi_feed::host_ticks &H = f->ht;
+    const size_t S = (size_t) b->n_streams, esz = 2 * (size_t) b->channels;
+    if ((uint64_t) f->max_rows * (uint64_t) f->max_push > (uint64_t) UINT32_MAX) return MP3MI_ERR_ARG; // (a push's first sample is a descriptor word)
+    ON_DEVICE(b);
+    if (!H.ready) {
+        H.dev_stride = mp3mi_batch_out_stride(b, f->tick_frames);
+        if (!H.h2d) CHK(hipStreamCreateWithFlags(&H.h2d, hipStreamNonBlocking));
+        if (!H.d2h) CHK(hipStreamCreateWithFlags(&H.d2h, hipStreamNonBlocking));
+        H.ready = true;
+    }
+    const int sl = (int) (H.tick_no & 1u);
+    mp3mi_feed::host_ticks::tick_slot &io = H.slot[sl];
+    if (!io.stage) CHK(hipMalloc((void **) &io.stage, (size_t) f->max_rows * (size_t) f->max_push * esz));
+    if (!io.out) CHK(hipMalloc((void **) &io.out, S * H.dev_stride));
+    if (!io.len) CHK(hipMalloc((void **) &io.len, S * sizeof(uint32_t)));
+    if (!io.len_rows) CHK(hipMalloc((void **) &io.len_rows, S * sizeof(uint32_t)));
+    if (!io.stage_free.ev) CHK(io.stage_free.create());
+    if (!io.out_free.ev) CHK(io.out_free.create());
+    if (!io.ev_enc) CHK(hipEventCreateWithFlags(&io.ev_enc, hipEventDisableTiming));
+    for (hipEvent_t *e : {&io.t_up[0], &io.t_up[1], &io.t_dn[0], &io.t_dn[1]})
+        if (!*e) CHK(hipEventCreate(e));
+    if (feed_host_harvest(f, sl) != MP3MI_OK) return MP3MI_ERR_HIP;
+    if (io.out_rows_cap < S * hc->out_stride) { // (behind the slot's last download: harvested above)
+        if (io.out_rows) {
+            CHK(hipFree(io.out_rows));
+            io.out_rows = NULL;
+            io.out_rows_cap = 0;
+        }
+        CHK(hipMalloc((void **) &io.out_rows, S * hc->out_stride));
+        io.out_rows_cap = S * hc->out_stride;
+    }
+    return MP3MI_OK;
+}
+
+extern "C" int mp3mi_feed_tick_lanes_host_async(mp3mi_feed *f, int n_rows, const int32_t *row_lane_host, const int16_t *pcm_host,
+                                                const uint8_t *ctl_host, const int32_t *n_push_host, const int32_t *kbps_host, uint8_t *out_host,
+                                                size_t out_stride, uint32_t *out_len_host, int32_t *out_lane_host, int32_t *out_slot_host,
+                                                int32_t *n_out_host)
+{
+    if (!f || !f->lanes_mode || !out_host || !out_len_host || !out_lane_host || !out_slot_host || !n_out_host) return MP3MI_ERR_ARG;
+    mp3mi_batch *b = f->b;
+    if (n_rows < 0 || n_rows > f->max_rows || out_stride < mp3mi_batch_out_stride(b, f->tick_frames)) return MP3MI_ERR_ARG;
+    if (n_rows > 0 && (!row_lane_host || !ctl_host || !n_push_host || !kbps_host)) return MP3MI_ERR_ARG;
+    size_t n_pushed = 0;
+    for (int r = 0; r < n_rows; r++) {
+        if (n_push_host[r] < 0 || n_push_host[r] > f->max_push) return MP3MI_ERR_ARG;
+        n_pushed += (size_t) n_push_host[r];
+    }
+    if (n_pushed && !pcm_host) return MP3MI_ERR_ARG;
+    const feed_host_call hc = {pcm_host, n_pushed, out_host, out_stride, out_len_host, out_lane_host, out_slot_host, n_out_host};
+    return feed_tick_lanes_impl(f, n_rows, row_lane_host, NULL, 0, ctl_host, n_push_host, kbps_host, NULL, 0, NULL, NULL, &hc);
+}
+
+// Waits for the upload and the download of ONE host tick: the latest (0) or the one before (1).  No call hold is let go (the ticket
+// rule of mp3mi_batch_host_wait: only the hold that very tick left in force).  A host tick leaves none (mp3mi_batch::feed_host_call),
+// and what it waits for was enqueued with the tick, ahead of whatever a later device tick holds: a later tick's hold stays, and a
+// server collects tick t while tick t + 1 keeps its place in the pipeline.
+extern "C" int mp3mi_feed_host_wait(mp3mi_feed *f, int ticks_back)
+{
+    if (!f || ticks_back < 0 || ticks_back > 1) return MP3MI_ERR_ARG;
+    mp3mi_feed::host_ticks &H = f->ht;
+    if (!H.ready || H.tick_no <= (unsigned) ticks_back) return MP3MI_ERR_ARG;
+    mp3mi_batch *b = f->b;
+    ON_DEVICE(b);
+    mp3mi_feed::host_ticks::tick_slot &io = H.slot[(H.tick_no - 1u - (unsigned) ticks_back) & 1u];
+    if (!io.pending || (io.stage_free.done() && io.out_free.done())) return MP3MI_OK;
+    if (io.up) CHK(hipEventSynchronize(io.t_up[1]));
+    if (io.dn) CHK(hipEventSynchronize(io.t_dn[1]));
+    return MP3MI_OK;
+}
+
+extern "C" int mp3mi_feed_host_io_stats(mp3mi_feed *f, mp3mi_host_io_stats *st)
+{
+    if (!f || !st) return MP3MI_ERR_ARG;
+    ON_DEVICE(f->b);
+    memset(st, 0, sizeof(*st));
+    if (!f->ht.ready) return MP3MI_OK;
+    if (feed_host_harvest(f, 0) != MP3MI_OK || feed_host_harvest(f, 1) != MP3MI_OK) return MP3MI_ERR_HIP;
+    st->calls = f->ht.tot_calls;
+    st->h2d_bytes = f->ht.tot_up_bytes; st->d2h_bytes = f->ht.tot_dn_bytes;
+    st->h2d_ms = f->ht.tot_up_ms; st->d2h_ms = f->ht.tot_dn_ms;
     return MP3MI_OK;
 }

@@ -8,6 +8,9 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
+#include <utility>
+#include <vector>
 #include "host_util.h"
 #include "mp3mi.h"
 
@@ -249,6 +252,49 @@ extern "C" int mp3mi_debug_feed_lanes(int channels, int n_active, int n_lanes, i
     D.sync();
     D.fetch(ring, dring, n_ring);
     D.fetch(push, dpush, n_pushed);
+    D.fetch(rows, drows, n_rows);
+    return D.rc();
+}
+
+// The self-test hook mp3mi_debug_feed_packed (include/mp3mi.h): k_feed_packed alone, through the launcher and the work list
+// mp3mi_feed_tick_lanes_host_async uses, on given rings (one per lane), a packed push buffer of n_packed samples and dense rows (one
+// per slot), whole up and whole back like the hooks above.  wg_bytes: what a workgroup moves, for the work list (the product's is
+// MP3MI_FEED_WG_BYTES; a small one deals every descriptor to several workgroups).  A descriptor set outside the rules launches nothing.
+extern "C" int mp3mi_debug_feed_packed(int channels, int n_active, int n_lanes, int n_packed, int n_slots, int cap, int row_samples, size_t wg_bytes,
+                                       const uint32_t *desc, int16_t *ring, size_t ring_pitch, int16_t *packed, int16_t *rows, size_t row_pitch)
+{
+    if (!have_device()) return MP3MI_ERR_NO_DEVICE;
+    if ((channels != 1 && channels != 2) || n_active <= 0 || n_lanes <= 0 || n_packed <= 0 || n_slots <= 0 || n_active > n_lanes || cap <= 0 ||
+        row_samples <= 0 || wg_bytes == 0 || !desc || !ring || !packed || !rows)
+        return MP3MI_ERR_ARG;
+    const size_t C = (size_t) channels, esz = 2 * C, A = (size_t) n_active;
+    if (ring_pitch < (size_t) cap || row_pitch < (size_t) row_samples || ring_pitch * esz % 16 != 0 || row_pitch * esz % 16 != 0) return MP3MI_ERR_ARG;
+    std::vector<char> lane_seen((size_t) n_lanes, 0), slot_seen((size_t) n_slots, 0);
+    std::vector<std::pair<uint64_t, uint64_t> > spans; // the pushes' samples in the packed buffer: inside it, and no two share a sample
+    for (size_t i = 0; i < A; i++) {
+        const uint32_t *d = desc + 8 * i;
+        const uint64_t head = d[0], pending = d[1], n_push = d[2], take = d[3];
+        if (head >= (uint64_t) cap || pending + n_push > (uint64_t) cap || take > pending + n_push || take > (uint64_t) row_samples) return MP3MI_ERR_ARG;
+        if (d[4] >= (uint32_t) n_lanes || (uint64_t) d[5] + n_push > (uint64_t) n_packed || d[6] >= (uint32_t) n_slots || d[7] != 0) return MP3MI_ERR_ARG;
+        if (lane_seen[d[4]] || (take && slot_seen[d[6]])) return MP3MI_ERR_ARG;
+        lane_seen[d[4]] = 1;
+        if (take) slot_seen[d[6]] = 1;
+        if (n_push) spans.push_back(std::make_pair((uint64_t) d[5], (uint64_t) d[5] + n_push));
+    }
+    std::sort(spans.begin(), spans.end());
+    for (size_t i = 1; i < spans.size(); i++)
+        if (spans[i].first < spans[i - 1].second) return MP3MI_ERR_ARG;
+    std::vector<uint32_t> work(2 * MP3MI_FEED_MAX_PARTS * A);
+    const size_t n_items = mp3mi_feed_work_list(desc, A, esz, wg_bytes, work.data());
+    const size_t n_ring = (size_t) n_lanes * ring_pitch * C, n_pushed = (size_t) n_packed * C, n_rows = (size_t) n_slots * row_pitch * C;
+    hook_bufs D;
+    const uint32_t *ddesc = D.copy_of(desc, 8 * A), *dwork = D.copy_of(work.data(), 2 * n_items);
+    int16_t *dring = D.copy_of(ring, n_ring), *dpush = D.copy_of(packed, n_pushed), *drows = D.copy_of(rows, n_rows);
+    if (!D.ok) return D.rc();
+    mp3mi_launch_feed_packed(ddesc, dwork, (int) n_items, dring, ring_pitch * esz, cap, channels, dpush, drows, row_pitch * esz, 0);
+    D.sync();
+    D.fetch(ring, dring, n_ring);
+    D.fetch(packed, dpush, n_pushed);
     D.fetch(rows, drows, n_rows);
     return D.rc();
 }

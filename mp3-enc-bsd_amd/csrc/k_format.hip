@@ -805,6 +805,36 @@ void mp3mi_launch_feed_lanes(const void *desc, int n_active, int16_t *ring, size
                        (uint8_t *) rows, row_pitch_bytes);
 }
 
+// ---- ticks on host buffers (mp3mi_feed_tick_lanes_host_async) ----
+// k_feed_packed is k_feed_lanes with two differences.  The pushes of a tick lie back to back in one staging buffer, so word 5 of a
+// descriptor is the push's first SAMPLE there and a push begins at any even byte: feed_copy takes that as it takes any other
+// misalignment -- it loads aligned source vectors that lie wholly inside [src, src + n) and goes sample by sample at the ends, so
+// it never reads a neighbouring packet, let alone past the buffer.  And the grid is 1-D over a work list the host built
+// (mp3mi_feed_work_list): item {descriptor, part | parts << 16}, one uniform 8-byte load; the workgroup is part `part` of the
+// `parts` among which the descriptor's vectors are dealt.  A packet of a few KB beside rows of 147 KB then costs one workgroup,
+// not the eight the longest copy of the launch asks for.  No LDS.
+__global__ void __launch_bounds__(256) k_feed_packed(const uint4 *__restrict__ desc, const uint2 *__restrict__ work, uint8_t *ring, size_t ring_pitch,
+                                                     unsigned cap, unsigned esz, const uint8_t *__restrict__ packed, uint8_t *__restrict__ rows,
+                                                     size_t row_pitch)
+{
+    const uint2 it = work[blockIdx.x];
+    const uint4 d = desc[2 * (size_t) it.x], w = desc[2 * (size_t) it.x + 1];
+    const size_t head = d.x, pending = d.y, n_push = d.z, take = d.w;
+    if (n_push == 0 && take == 0) return;
+    const size_t part = it.y & 0xFFFFu, parts = it.y >> 16;
+    const size_t lane = part * 256 + threadIdx.x, step = 256 * parts;
+    feed_move(ring + (size_t) w.x * ring_pitch, rows + (size_t) w.z * row_pitch, packed + (size_t) w.y * esz, head, pending, n_push, take, cap, esz,
+              lane, step);
+}
+
+void mp3mi_launch_feed_packed(const void *desc, const void *work, int n_items, int16_t *ring, size_t ring_pitch_bytes, int cap, int channels,
+                              const int16_t *packed, int16_t *rows, size_t row_pitch_bytes, hipStream_t st)
+{
+    if (n_items <= 0) return;
+    hipLaunchKernelGGL(k_feed_packed, dim3((unsigned) n_items), dim3(256), 0, st, (const uint4 *) desc, (const uint2 *) work, (uint8_t *) ring,
+                       ring_pitch_bytes, (unsigned) cap, (unsigned) (2 * channels), (const uint8_t *) packed, (uint8_t *) rows, row_pitch_bytes);
+}
+
 // the last MP3MI_PCM_HIST samples of the call (a frame has 1152 > MP3MI_PCM_HIST) are the next call's history
 __global__ void __launch_bounds__(256) k_hist_save(mp3mi_geom geo, const int16_t *__restrict__ pcm, int16_t *__restrict__ hist)
 {

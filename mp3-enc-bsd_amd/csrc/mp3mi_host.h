@@ -187,6 +187,32 @@ void mp3mi_launch_feed(const void *desc, int n_lanes, int16_t *ring, size_t ring
    taking entry and no push row of a pushing entry twice in a launch: checked on the host */
 void mp3mi_launch_feed_lanes(const void *desc, int n_active, int16_t *ring, size_t ring_pitch_bytes, int cap, int channels, const int16_t *push,
                              size_t push_pitch_bytes, int16_t *rows, size_t row_pitch_bytes, size_t most_bytes, hipStream_t st);
+/* k_feed_packed (mp3mi_feed_tick_lanes_host_async): k_feed_lanes on a PACKED push buffer and over a WORK LIST.  Word 5 of a
+   descriptor is the push's first sample (of all channels) in `packed`, so a push begins at any even byte; the grid is 1-D over
+   n_items work items of two uint32 {descriptor index, part | parts << 16}: workgroup `part` of the `parts` that share the
+   descriptor's copies.  mp3mi_feed_work_list builds the list: a descriptor gets ceil(its longest copy / wg_bytes) workgroups, at
+   least 1 and at most MP3MI_FEED_MAX_PARTS, whatever the other descriptors of the launch move.  work: room for
+   2 * MP3MI_FEED_MAX_PARTS * n_active words; returns the items.  The product's wg_bytes is MP3MI_FEED_WG_BYTES */
+#define MP3MI_FEED_MAX_PARTS 8
+#define MP3MI_FEED_WG_BYTES ((size_t) 256 * 16 * 4) /* four stores per lane of the longest copy, as k_feed's grid */
+static inline size_t mp3mi_feed_work_list(const uint32_t *desc, size_t n_active, size_t esz, size_t wg_bytes, uint32_t *work)
+{
+    size_t n_items = 0;
+    for (size_t i = 0; i < n_active; i++) {
+        const uint32_t n_push = desc[8 * i + 2], take = desc[8 * i + 3];
+        const size_t longest = (size_t) (take > n_push ? take : n_push) * esz;
+        size_t parts = (longest + wg_bytes - 1) / wg_bytes;
+        parts = parts < 1 ? 1 : parts > MP3MI_FEED_MAX_PARTS ? MP3MI_FEED_MAX_PARTS : parts;
+        for (size_t p = 0; p < parts; p++) {
+            work[2 * n_items] = (uint32_t) i;
+            work[2 * n_items + 1] = (uint32_t) (p | parts << 16);
+            n_items++;
+        }
+    }
+    return n_items;
+}
+void mp3mi_launch_feed_packed(const void *desc, const void *work, int n_items, int16_t *ring, size_t ring_pitch_bytes, int cap, int channels,
+                              const int16_t *packed, int16_t *rows, size_t row_pitch_bytes, hipStream_t st);
 /* status[s] = the status word of stream s (a gather out of the strided state records) */
 void mp3mi_launch_status_gather(int n_streams, const int32_t *loop_state, int loop_state_words, int32_t *status, hipStream_t st);
 /* the reverse, for the streams a flush ended: their status words go back into the cleared state records, marked as reported */

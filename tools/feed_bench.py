@@ -16,10 +16,19 @@ of a run), three scenarios (--scenario):
   --host-time ROWS   (with --lanes N) the host time of mp3mi_feed_tick_lanes per call, wall clock around the call with nothing
       waited for and the device idle before it: ROWS lanes of N bring a one-call file of a tick each, 50 ticks; reported for N and
       for 4096 lanes, and their ratio.  Use a small batch (--streams 128 --frames 1): the rings are N times a tick.
+  --host   scenarios a, b and d (--lanes N) as defined above, on HOST buffers (mp3mi_feed_tick_lanes_host_async; for a and b a feeder
+      with as many lanes as slots).  Three variants of the same ticks on the same library, alternating, --reps runs each: `device`,
+      mp3mi_feed_tick_lanes on resident packets (the floor); `device_copies`, the same call between synchronous copies -- the packet
+      rectangle [n_rows][max_push][C] up, [streams][out_stride] and the lengths down -- which is what a caller with host buffers had
+      before; `host`, ticks issued back to back from page-locked buffers, tick t collected with host_wait(1) behind tick t + 1's
+      issue.  Prints per variant the ms per tick of every run, for `host` the wall-clock ms from collection to collection of one run
+      and h2d_bytes / d2h_bytes per tick (mp3mi_feed_host_io_stats), and the workgroups k_feed_lanes and k_feed_packed launch per
+      tick (from the descriptors' arithmetic).  The packed buffer is the first sum(n_push) samples of the rectangle: the same
+      samples where every row pushes max_push (a, d), the same amount elsewhere (b).
 Prints one JSON line per run: ms per tick, the parks and resumes per tick (from mp3mi_feed_lanes, host bookkeeping), the bytes
 k_feed moves per tick (read + written, from the descriptors' arithmetic) and the library's source hash.
 
-usage: feed_bench.py [--scenario a|b|c] [--lanes N [--packet P] [--host-time ROWS]] [--ticks 20] [--frames 32] [--streams 4096] [--reps 3]"""
+usage: feed_bench.py [--scenario a|b|c] [--host] [--lanes N [--packet P] [--host-time ROWS]] [--ticks 20] [--frames 32] [--streams 4096] [--reps 3]"""
 import argparse
 import importlib
 import json
@@ -42,9 +51,14 @@ def main():
     ap.add_argument("--lanes", type=int, default=0, help="scenario d: that many lanes in front of the slots")
     ap.add_argument("--packet", type=int, default=0, help="scenario d: samples a lane pushes per tick")
     ap.add_argument("--host-time", type=int, default=0, help="with --lanes: rows per tick of the host-time measurement")
+    ap.add_argument("--host", action="store_true", help="scenarios a, b, d on host buffers, beside the device tick with and without copies")
     a = ap.parse_args()
     import torch
     mp3 = importlib.import_module("mp3-enc-bsd_amd")
+    if a.host:
+        if a.scenario == "c" or a.host_time:
+            ap.error("--host takes scenarios a, b and d (--lanes)")
+        return host(a, torch, mp3)
     if a.lanes:
         return host_time(a, torch, mp3) if a.host_time else lanes(a, torch, mp3)
     S, nf, ch, kbps, T = a.streams, a.frames, 2, 128, a.ticks
@@ -186,6 +200,105 @@ def lanes(a, torch, mp3):
     L = mp3.lib()
     print(json.dumps(dict(tool="feed_bench", scenario="d", streams=S, lanes=N, packet=packet, frames_per_tick=nf, ticks=T, rate=rate, channels=ch,
                           kbps=kbps, **res, **stats, source_hash=L.mp3mi_source_hash().decode(), version=L.mp3mi_version().decode())))
+    b.close()
+
+
+def host(a, torch, mp3):
+    """ticks on host buffers against the device tick, with and without synchronous copies around it"""
+    S, nf, ch, kbps, T = a.streams, a.frames, 2, 128, a.ticks
+    full, esz = nf * 1152, 4
+    rng = np.random.default_rng(1)
+    if a.lanes:
+        name, N, rate = "d", a.lanes, 48000
+        ratio = max(N // S, 1)
+        max_push = a.packet or full // ratio
+        ring, skip = full + 2 * max_push, ratio
+        lane = np.arange(N, dtype=np.int32)
+        plan = [(lane[lane % ratio <= t], lane[lane % ratio <= t] % ratio == t, None) for t in range(ratio)]
+        plan += [(lane, None, None)] * T
+    else:
+        name, N, rate = a.scenario, S, 48000 if a.scenario == "b" else 44100
+        max_push, ring, skip = (full, 0, 0) if name == "a" else (2 * 39 * 960, 0, 0)
+        lane = np.arange(N, dtype=np.int32)
+        plan = [(lane, np.ones(N, bool) if t == 0 else None, None if name == "a" else (960 * rng.integers(38, 40, N)).astype(np.int32)) for t in range(T)]
+    plan = [(r, st, np.full(len(r), max_push, np.int32) if n is None else n) for r, st, n in plan]
+    dev = torch.device("cuda:0")
+    rect_d = torch.empty((N, max_push * ch), dtype=torch.int16, device=dev)
+    torch.cuda.synchronize()
+    mp3.synth_pcm_device(rect_d, max_push, ch, rate)
+    rect_h = torch.empty((N, max_push * ch), dtype=torch.int16).pin_memory()
+    rect_h.copy_(rect_d)
+    b = mp3.Batch(S, rate, ch, kbps, nf)
+    stride = b.out_stride(nf)
+    out_d = torch.zeros((S, stride), dtype=torch.uint8, device=dev)
+    len_d = torch.zeros(S, dtype=torch.int32, device=dev)
+    outs_h = [torch.zeros((S, stride), dtype=torch.uint8).pin_memory() for _ in range(3)]
+    lens_h = [torch.zeros(S, dtype=torch.int32).pin_memory() for _ in range(3)]
+    torch.cuda.synchronize()
+    work = {}
+
+    def run(variant):
+        feed = b.feeder(nf, max_push, lanes=N, ring_samples=ring)
+        marks, wg_lanes, wg_packed = [], 0, 0
+        for t, (rows, st, n) in enumerate(plan):
+            if t == skip:
+                feed.host_wait(0) if variant == "host" and t else None
+                b.sync()
+                t0 = time.perf_counter()
+                marks = [t0]
+            R = len(rows)
+            if variant == "host":
+                lanes_t, _ = feed.tick_lanes_host(rect_h, outs_h[t % 3], lens_h[t % 3], rows, start=st, n_push=n)
+                if t > skip:
+                    feed.host_wait(1)
+                    marks.append(time.perf_counter())
+            else:
+                if variant == "device_copies":
+                    rect_d[:R].copy_(rect_h[:R])
+                    torch.cuda.synchronize()
+                sl = feed.tick_lanes(rect_d[:R], out_d, len_d, rows, start=st, n_push=n)
+                if variant == "device_copies":
+                    outs_h[0].copy_(out_d)
+                    lens_h[0].copy_(len_d)
+                    torch.cuda.synchronize()
+                if t >= skip and "wg" not in work:  # what the two kernels launch for this tick: a descriptor per lane that pushes or takes
+                    take = np.zeros(N, np.int64)
+                    take[sl[sl >= 0]] = full
+                    longest = np.maximum(take[rows], n) * esz
+                    per = 256 * 16 * 4
+                    wg_lanes += R * int(min(max(-(-int(longest.max()) // per), 1), 8))
+                    wg_packed += int(np.clip(-(-longest // per), 1, 8).sum())
+        if variant == "host":
+            feed.host_wait(0)
+            marks.append(time.perf_counter())
+        b.sync()
+        ms = (time.perf_counter() - t0) * 1e3 / T
+        extra = {}
+        if variant == "host":
+            st = feed.host_io_stats()
+            extra = dict(h2d_bytes_per_tick=st["h2d_bytes"] / st["calls"], d2h_bytes_per_tick=st["d2h_bytes"] / st["calls"],
+                         h2d_ms_per_tick=round(st["h2d_ms"] / st["calls"], 3), d2h_ms_per_tick=round(st["d2h_ms"] / st["calls"], 3),
+                         per_tick_ms=[round((y - x) * 1e3, 3) for x, y in zip(marks, marks[1:])])
+        elif "wg" not in work:
+            work["wg"] = dict(k_feed_lanes_workgroups_per_tick=wg_lanes // T, k_feed_packed_workgroups_per_tick=wg_packed // T)
+        feed.close()
+        return ms, extra
+
+    variants = ("device", "device_copies", "host")
+    ms = {v: [] for v in variants}
+    extra = {}
+    for r in range(a.reps + 1):  # the variants alternate; the first round warms up
+        for v in variants:
+            m, e = run(v)
+            if r > 0:
+                ms[v].append(round(m, 3))
+                extra.update(e)
+    L = mp3.lib()
+    print(json.dumps(dict(tool="feed_bench", mode="host", scenario=name, streams=S, lanes=N, max_push=max_push, frames_per_tick=nf, ticks=T, rate=rate,
+                          channels=ch, kbps=kbps, call_hold=os.environ.get("MP3MI_CALL_HOLD", "default"),
+                          **{v + "_ms": ms[v] for v in variants}, **{v + "_ms_median": float(np.median(ms[v])) for v in variants},
+                          copies_h2d_bytes_per_tick=len(plan[-1][0]) * max_push * esz, copies_d2h_bytes_per_tick=S * (stride + 4), **extra, **work.get("wg", {}),
+                          source_hash=L.mp3mi_source_hash().decode(), version=L.mp3mi_version().decode())))
     b.close()
 
 
