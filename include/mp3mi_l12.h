@@ -90,7 +90,8 @@ int mp3mi_l12_batch_reset(mp3mi_l12_batch *b);
  *   out_dev, out_len_dev  device, [n_streams][out_stride] and [n_streams]: out_len_dev[s] is the bytes of slot s's file the call
  *                  produced -- 0 for a closed slot, whose row is left alone whatever its PCM row holds
  * The bytes a slot delivers from a stream's START call through its END call, concatenated, are byte for byte what
- * mp3mi_l12_batch_encode gives for the same samples as one stream of a ragged whole-file call (bitrate: the slot's, from create).
+ * mp3mi_l12_batch_encode gives for the same samples as one stream of a ragged whole-file call (bitrate: the slot's, from create,
+ * unless the stream's START chose another: mp3mi_l12_batch_encode_slots_kbps below).
  * MP3MI_ERR_ARG, with nothing enqueued and the batch unchanged: ctl bits other than the two; END on a closed slot without
  * START; a sample count that is not full for a continuing or starting slot, outside 0 .. full for an ending one, not 0 for a
  * closed one; a NULL pointer other than n_samples_host; n_frames outside 1 .. max_frames; out_stride below
@@ -107,6 +108,81 @@ int mp3mi_l12_batch_encode_slots(mp3mi_l12_batch *b, const int16_t *pcm_dev, int
 /* frames_host[s] = frames encoded so far by the stream open in slot s, -1 if none is; returns the number of open slots.
  * Host-side bookkeeping only: waits for nothing. */
 int mp3mi_l12_batch_slot_frames(const mp3mi_l12_batch *b, int64_t *frames_host);
+
+/* A bitrate per stream, chosen at START -- as mp3mi_batch_encode_slots_kbps / mp3mi_batch_slot_kbps of mp3mi.h.  The call is
+ * mp3mi_l12_batch_encode_slots with one more host array; kbps_host == NULL is exactly that call.
+ *   kbps_host   host, [n_streams] int32, copied before the call returns
+ *     a slot that STARTs      0: the bitrate the slot was created with; otherwise a bitrate of the batch's layer (the table at
+ *                             mp3mi_l12_batch_create) that is not above the batch's CEILING, the largest bitrate it was created
+ *                             with.  In Layer II the bitrate also selects the stream's allocation table and subband limit
+ *                             (src/common.c:291-318), exactly as at create
+ *     any other slot          0, or the bitrate of the stream open there: one persistent array serves call after call
+ * The ceiling sizes the output rows: a frame's bytes do not decrease as the bitrate grows, so mp3mi_l12_batch_out_stride holds for
+ * every bitrate a START may name.  The bitrate belongs to the STREAM: it holds until the stream is over -- by END, by
+ * mp3mi_l12_batch_flush or _reset, abandoned by a new START in its slot, or by a whole-file mp3mi_l12_batch_encode -- through every
+ * call that continues it (mp3mi_l12_batch_encode_next among them), and afterwards the slot is back at its create-time bitrate.  Calls
+ * that start every stream afresh (mp3mi_l12_batch_encode; an encode_next with no slot open) encode at the create-time bitrates, as
+ * on a batch that never saw another.  The bytes of a stream are those of mp3mi_l12_batch_encode of its samples at ITS bitrate.
+ * MP3MI_ERR_ARG, nothing enqueued, the batch unchanged: the rules of mp3mi_l12_batch_encode_slots, and a kbps_host entry that breaks
+ * the two above.
+ *   mp3mi_l12_batch_slot_kbps   kbps_host[s] = the bitrate of the stream open in slot s, the slot's create-time bitrate where none is;
+ *                               returns the ceiling.  Host-side bookkeeping only: waits for nothing. */
+int mp3mi_l12_batch_encode_slots_kbps(mp3mi_l12_batch *b, const int16_t *pcm_dev, int n_frames, const uint8_t *ctl_host,
+                                      const int32_t *n_samples_host, const int32_t *kbps_host, uint8_t *out_dev, size_t out_stride,
+                                      uint32_t *out_len_dev);
+int mp3mi_l12_batch_slot_kbps(const mp3mi_l12_batch *b, int32_t *kbps_host);
+
+/* Parking and resuming streams -- as mp3mi_batch_slots_export / _import of mp3mi.h: an open stream leaves its slot, sits out any
+ * number of calls, and goes on later in any closed slot of this batch or of another batch of the same format, on this GPU or
+ * another; or a snapshot of it is taken while it goes on.  The bytes the stream delivers from START through END, concatenated
+ * over every slot and batch it lived in, are its file, as if it had never moved.
+ *   A parked stream is a TICKET, host memory, and a STATE RECORD, device memory.
+ *   mp3mi_l12_slot_ticket       plain data, may be stored and sent anywhere
+ *     magic, version            MP3MI_L12_SLOT_TICKET_MAGIC, MP3MI_L12_SLOT_TICKET_VERSION (the layout of ticket and record)
+ *     state_bytes               mp3mi_l12_batch_slot_state_bytes of the batch that exported it
+ *     layer, rate_hz, channels  the format of that batch, and what mp3mi_l12_batch_set_mode, _set_header (copyright << 3 |
+ *     hdr_mode, hdr_flags,      original << 2 | emphasis) and _set_error_protection had been given when it was exported
+ *     error_protection
+ *     kbps                      the stream's bitrate
+ *     reserved                  0
+ *     frames                    frames the stream has encoded
+ *   the state record            all a stream of these layers carries from call to call: its PCM history, the row of the FFT
+ *                               windows' ([1792][channels] int16) and behind it the row of the filterbank's ([1056][channels]
+ *                               int16) -- channels * 5696 bytes, a multiple of 16 that depends on the channel count alone
+ *                               (mp3mi_l12_batch_slot_state_bytes).  No reservoir, no carried bytes, no status word.  The
+ *                               bitrate travels in the ticket alone: nothing in a record is ever used as an index, so a damaged
+ *                               record gives wrong audio and nothing worse
+ *   mp3mi_l12_batch_slots_export  slots_host: n DISTINCT slots, 1 .. n_streams of them, each with a stream open.  Record i goes to
+ *                               (char *) state_dev + i * state_stride, ticket i to tickets_host[i].  state_stride >=
+ *                               state_bytes; it and state_dev multiples of 16.  close != 0: the slots are closed WITHOUT a
+ *                               flush -- nothing is delivered, the file's last byte included; slot_frames gives -1 and slot_kbps
+ *                               the create-time bitrate there.  close == 0: a snapshot; the streams go on, and the record may be
+ *                               imported any number of times
+ *   mp3mi_l12_batch_slots_import  slots_host: n distinct CLOSED slots.  Every ticket must match the library and the batch in every
+ *                               field: magic, version, state_bytes; layer, rate, channels; mode, header flags, error protection
+ *                               as the batch has them NOW; reserved 0; kbps a bitrate of the layer not above the batch's ceiling;
+ *                               frames >= 0.  Afterwards slot i is open at the ticket's frame count and bitrate, whatever the
+ *                               slot was created with: the next per-slot call continues the stream with ctl 0, and so does
+ *                               mp3mi_l12_batch_encode_next.  Works as the first call on a fresh batch, after a flush or a reset
+ * Both return MP3MI_ERR_ARG, with nothing enqueued and the batch unchanged, where a rule is broken.  Neither waits for the device:
+ * the copies run on the batch's stream, behind every call before and ahead of every call after, so a record may be imported into
+ * the batch that exported it at once; any other reader or writer of the record (another batch, a copy to the host) calls
+ * mp3mi_l12_batch_sync on the exporting batch first.  Until a batch's first bitrate array, export or import nothing of this exists:
+ * it allocates, copies and launches exactly what it did without. */
+#define MP3MI_L12_SLOT_TICKET_MAGIC 0x4B54324Du /* "M2TK" */
+#define MP3MI_L12_SLOT_TICKET_VERSION 1u
+typedef struct mp3mi_l12_slot_ticket {
+    uint32_t magic, version;
+    uint64_t state_bytes;
+    int32_t layer, rate_hz, channels, hdr_mode;
+    int32_t hdr_flags, error_protection, kbps, reserved;
+    int64_t frames;
+} mp3mi_l12_slot_ticket; /* 56 bytes, no padding */
+size_t mp3mi_l12_batch_slot_state_bytes(const mp3mi_l12_batch *b);
+int mp3mi_l12_batch_slots_export(mp3mi_l12_batch *b, int n, const int32_t *slots_host, int close, void *state_dev, size_t state_stride,
+                                 mp3mi_l12_slot_ticket *tickets_host);
+int mp3mi_l12_batch_slots_import(mp3mi_l12_batch *b, int n, const int32_t *slots_host, const void *state_dev, size_t state_stride,
+                                 const mp3mi_l12_slot_ticket *tickets_host);
 
 /* Two-tier decisions (mp3mi.h, MP3MI_TEST_PHASE_EXACT | _PSY_EXACT | _CW_EXACT): force the exact tier; bytes must not change */
 int mp3mi_l12_batch_set_test_flags(mp3mi_l12_batch *b, unsigned flags);

@@ -44,6 +44,14 @@ class SlotTicket(ctypes.Structure):
                 ("error_protection", ctypes.c_int32), ("kbps", ctypes.c_int32), ("frames", ctypes.c_int64)]
 
 
+class SlotTicketL12(ctypes.Structure):
+    """include/mp3mi_l12.h: mp3mi_l12_slot_ticket -- what the host knows of a parked Layer I / II stream (BatchL12.export_slots /
+    import_slots)"""
+    _fields_ = [("magic", ctypes.c_uint32), ("version", ctypes.c_uint32), ("state_bytes", ctypes.c_uint64), ("layer", ctypes.c_int32),
+                ("rate_hz", ctypes.c_int32), ("channels", ctypes.c_int32), ("hdr_mode", ctypes.c_int32), ("hdr_flags", ctypes.c_int32),
+                ("error_protection", ctypes.c_int32), ("kbps", ctypes.c_int32), ("reserved", ctypes.c_int32), ("frames", ctypes.c_int64)]
+
+
 def default_options(**kw):
     o = BatchOptions()
     lib().mp3mi_batch_options_default(ctypes.byref(o))
@@ -149,6 +157,14 @@ def lib():
         L.mp3mi_l12_batch_encode_slots.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                    ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         L.mp3mi_l12_batch_slot_frames.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        L.mp3mi_l12_batch_encode_slots_kbps.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        L.mp3mi_l12_batch_slot_kbps.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        L.mp3mi_l12_batch_slot_state_bytes.restype = ctypes.c_size_t
+        L.mp3mi_l12_batch_slot_state_bytes.argtypes = [ctypes.c_void_p]
+        L.mp3mi_l12_batch_slots_export.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
+                                                   ctypes.c_void_p]
+        L.mp3mi_l12_batch_slots_import.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         L.mp3mi_l12_batch_total_timing.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]
         L.mp3mi_l12_batch_kernel_timing.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.mp3mi_version.restype = ctypes.c_char_p
@@ -639,12 +655,15 @@ class BatchL12:
     def reset(self):
         self._check(self.L.mp3mi_l12_batch_reset(self.h), "mp3mi_l12_batch_reset")
 
-    def encode_slots(self, pcm, n_frames, out, out_len, start=None, end=None, n_samples=None):
+    def encode_slots(self, pcm, n_frames, out, out_len, start=None, end=None, n_samples=None, kbps=None):
         """Continuous batching (mp3mi_l12_batch_encode_slots): every stream index is a slot in which one stream after another
         begins (start[s] true: with this call's first sample, from silence) and ends (end[s] true: this call holds its last
         n_samples[s] samples per channel).  start / end: boolean sequences of n_streams (None: all false); n_samples: an int
         sequence (None: a full call for every open or starting slot, 0 for the others).  Tensors as for encode_next; out /
-        out_len receive per slot the bytes of its file this call produced (0 for a closed slot)."""
+        out_len receive per slot the bytes of its file this call produced (0 for a closed slot).  kbps: an int sequence, per slot
+        the bitrate of the stream that STARTs there (0: the slot's create-time bitrate; a bitrate of the layer, at most the largest
+        the batch was created with) and 0 or the open stream's own bitrate elsewhere (mp3mi_l12_batch_encode_slots_kbps); None: the
+        call without it."""
         import numpy as np
         assert pcm.is_cuda and out.is_cuda and out_len.is_cuda and pcm.is_contiguous() and out.is_contiguous()
         S = self.n_streams
@@ -654,6 +673,12 @@ class BatchL12:
         if end is not None:
             ctl |= np.asarray(end, dtype=bool).reshape(S).astype(np.uint8) * 2  # MP3MI_SLOT_END
         ns = None if n_samples is None else np.ascontiguousarray(n_samples, dtype=np.int32).reshape(S)
+        if kbps is not None:
+            kb = np.ascontiguousarray(kbps, dtype=np.int32).reshape(S)
+            self._check(self.L.mp3mi_l12_batch_encode_slots_kbps(self.h, pcm.data_ptr(), n_frames, ctl.ctypes.data, None if ns is None else ns.ctypes.data,
+                                                                 kb.ctypes.data, out.data_ptr(), out.stride(0), out_len.data_ptr()),
+                        "mp3mi_l12_batch_encode_slots_kbps")
+            return
         self._check(self.L.mp3mi_l12_batch_encode_slots(self.h, pcm.data_ptr(), n_frames, ctl.ctypes.data, None if ns is None else ns.ctypes.data,
                                                         out.data_ptr(), out.stride(0), out_len.data_ptr()), "mp3mi_l12_batch_encode_slots")
 
@@ -665,6 +690,47 @@ class BatchL12:
         if rc < 0:
             raise Mp3miError("mp3mi_l12_batch_slot_frames failed with %d" % rc)
         return f
+
+    def slot_kbps(self):
+        """(numpy int32 [n_streams]: the bitrate of the stream open in each slot, the slot's create-time bitrate where none is;
+        the batch's ceiling in kbps -- the largest bitrate a START may choose) (no device wait)"""
+        import numpy as np
+        k = np.zeros(self.n_streams, np.int32)
+        rc = self.L.mp3mi_l12_batch_slot_kbps(self.h, k.ctypes.data)
+        if rc < 0:
+            raise Mp3miError("mp3mi_l12_batch_slot_kbps failed with %d" % rc)
+        return k, rc
+
+    def slot_state_bytes(self):
+        """bytes of one parked stream's device record (a multiple of 16): the least row size of export_slots' state tensor"""
+        return self.L.mp3mi_l12_batch_slot_state_bytes(self.h)
+
+    def export_slots(self, slots, state, close=True):
+        """Parks the streams open in `slots` (distinct slot indices): row i of state -- a uint8 cuda tensor [len(slots), stride] with
+        contiguous rows, stride >= slot_state_bytes() and a multiple of 16 -- receives the device record of slots[i]'s stream, its PCM
+        history; returns the tickets, a ctypes array of SlotTicketL12, one per slot (host bookkeeping; no device wait).  close: the
+        slots are closed afterwards without a flush -- nothing is delivered; False: the streams go on and the records are a
+        snapshot.  sync() before the records are read by anything but this batch's own import_slots
+        (mp3mi_l12_batch_slots_export)."""
+        import numpy as np
+        sl = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        assert state.is_cuda and state.is_contiguous() and state.dtype.itemsize == 1 and state.dim() == 2 and state.shape[0] >= len(sl)
+        tickets = (SlotTicketL12 * max(len(sl), 1))()
+        self._check(self.L.mp3mi_l12_batch_slots_export(self.h, len(sl), sl.ctypes.data, 1 if close else 0, state.data_ptr(), state.stride(0),
+                                                        ctypes.addressof(tickets)), "mp3mi_l12_batch_slots_export")
+        return tickets
+
+    def import_slots(self, slots, state, tickets):
+        """Resumes parked streams in the closed slots `slots`: row i of state (as export_slots wrote it, of this batch or of
+        another batch of the same format) and tickets[i] go into slots[i], which is open afterwards at the ticket's frame count
+        and bitrate; the next encode_slots continues it (start and end false).  No device wait (mp3mi_l12_batch_slots_import)."""
+        import numpy as np
+        sl = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        assert state.is_cuda and state.is_contiguous() and state.dtype.itemsize == 1 and state.dim() == 2 and state.shape[0] >= len(sl)
+        assert len(tickets) >= len(sl)
+        arr = (SlotTicketL12 * max(len(sl), 1))(*list(tickets)[:len(sl)])
+        self._check(self.L.mp3mi_l12_batch_slots_import(self.h, len(sl), sl.ctypes.data, state.data_ptr(), state.stride(0), ctypes.addressof(arr)),
+                    "mp3mi_l12_batch_slots_import")
 
     def sync(self):
         self._check(self.L.mp3mi_l12_batch_sync(self.h), "mp3mi_l12_batch_sync")

@@ -971,7 +971,7 @@ void mp3mi_launch_l12_flush(int n_streams, const uint8_t *slot_ctl, uint8_t *out
 // zero-filled buffers -- whatever the stream before it left there.  One workgroup per LISTED slot (the host lists the call's START
 // slots: no scan over all slots) zeroes the slot's rows of the two history buffers with 16-byte stores: a row is L12_PCM_HIST or
 // MP3MI_PCM_HIST samples per channel of 2 bytes, 3584 or 2112 bytes per channel -- multiples of 16, like the buffers' bases.
-static_assert((L12_PCM_HIST * sizeof(int16_t)) % 16 == 0 && (MP3MI_PCM_HIST * sizeof(int16_t)) % 16 == 0, "k12_slot_begin stores 16 bytes at a time");
+static_assert((L12_PCM_HIST * sizeof(int16_t)) % 16 == 0 && (MP3MI_PCM_HIST * sizeof(int16_t)) % 16 == 0, "k12_slot_begin and k12_slot_park move 16 bytes at a time");
 __global__ void __launch_bounds__(256) k12_slot_begin(const int32_t *__restrict__ list, int channels, int16_t *__restrict__ hist,
                                                       int16_t *__restrict__ fb_hist)
 {
@@ -986,6 +986,54 @@ void mp3mi_launch_l12_slot_begin(const int32_t *list, int n_list, int channels, 
 {
     if (n_list <= 0) return;
     hipLaunchKernelGGL(k12_slot_begin, dim3((unsigned) n_list), dim3(256), 0, st, list, channels, hist, fb_hist);
+}
+
+// ---- parking and resuming streams (mp3mi_l12_batch_slots_export / _import): the state record of a stream is its two history rows
+// one behind the other -- hist's, then fb_hist's -- and nothing else.  Workgroup (i, y) moves its share of listed slot list[i]'s rows
+// between the live buffers and record i, (char *) state + i * state_stride: to_state gathers (export), otherwise it scatters
+// (import).  Units of 16 bytes, one per lane and access, consecutive lanes on consecutive units: every row is 224 or 132 of them
+// per channel (the static_assert above), the rows' and the records' bases are multiples of 16 (the host checks state and
+// state_stride), so each wavefront's loads and stores are whole 1 KiB runs.  Every byte is read once and written once: no LDS.  The
+// slot index is one uniform load per workgroup.  The host bounds n_list, the slots and the record area; nothing read from a record
+// is used as an index.
+__global__ void __launch_bounds__(256) k12_slot_park(const int32_t *__restrict__ list, int channels, int16_t *hist, int16_t *fb_hist,
+                                                     uint8_t *state, size_t state_stride, int to_state)
+{
+    const size_t s = (size_t) list[blockIdx.x];
+    const int n_h = (int) (L12_PCM_HIST * sizeof(int16_t) / 16) * channels, n_f = (int) (MP3MI_PCM_HIST * sizeof(int16_t) / 16) * channels;
+    uint4 *h = (uint4 *) (hist + s * L12_PCM_HIST * (size_t) channels), *f = (uint4 *) (fb_hist + s * MP3MI_PCM_HIST * (size_t) channels);
+    uint4 *rec = (uint4 *) (state + (size_t) blockIdx.x * state_stride);
+    for (int i = (int) (blockIdx.y * 256 + threadIdx.x); i < n_h + n_f; i += (int) (256 * gridDim.y)) {
+        uint4 *live = i < n_h ? h + i : f + (i - n_h);
+        if (to_state) rec[i] = *live;
+        else *live = rec[i];
+    }
+}
+void mp3mi_launch_l12_slot_park(const int32_t *list, int n_list, int channels, int16_t *hist, int16_t *fb_hist, void *state,
+                                size_t state_stride, int to_state, hipStream_t st)
+{
+    if (n_list <= 0) return;
+    // (a record is 356 units per channel: two workgroups of 256 lanes cover a mono one in one pass)
+    hipLaunchKernelGGL(k12_slot_park, dim3((unsigned) n_list, 2u), dim3(256), 0, st, list, channels, hist, fb_hist, (uint8_t *) state,
+                       state_stride, to_state);
+}
+
+// ---- a bitrate per stream (mp3mi_l12_batch_encode_slots_kbps): cfg[e[i].slot] = e[i].cfg for the n slots whose stream starts,
+// arrives (import) or starts afresh at another bitrate than the one cfg holds for the slot.  The host computed the values
+// (l12_stream_cfg_of) into the call's control block; on the batch's stream, ahead of the k12_alloc that reads cfg.  One lane per
+// entry, one 16-byte load of the value and one 16-byte store: an l12_stream_cfg is 16 bytes, an entry 32, and the host lists no slot
+// twice and none out of range.
+static_assert(sizeof(l12_stream_cfg) == 16 && sizeof(l12_rate_entry) == 32, "k12_slot_rate moves an l12_stream_cfg as one 16-byte unit");
+__global__ void __launch_bounds__(64) k12_slot_rate(const l12_rate_entry *__restrict__ e, int n, l12_stream_cfg *__restrict__ cfg)
+{
+    const int i = (int) (blockIdx.x * 64 + threadIdx.x);
+    if (i >= n) return;
+    *(uint4 *) &cfg[e[i].slot] = *(const uint4 *) &e[i].cfg;
+}
+void mp3mi_launch_l12_slot_rate(const l12_rate_entry *e, int n, l12_stream_cfg *cfg, hipStream_t st)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k12_slot_rate, dim3((unsigned) ((n + 63) / 64)), dim3(64), 0, st, e, n, cfg);
 }
 
 ULP_CENSUS_ACCESSOR(mp3mi_debug_ulp_census_l12)

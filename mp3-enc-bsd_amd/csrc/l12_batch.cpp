@@ -5,7 +5,9 @@
 //
 // Frames are independent but for PCM history (l12_dev.h), so a chunk is just these four launches in stream order, and
 // chunks follow each other on the batch's one HIP stream.  A per-slot call (mp3mi_l12_batch_encode_slots) puts its control block's
-// upload and k12_slot_begin ahead of them on the same stream.  No CPU fallback.
+// upload and k12_slot_begin ahead of them on the same stream -- and k12_slot_rate, where a stream begins at another bitrate than its
+// slot's (mp3mi_l12_batch_encode_slots_kbps); an export or an import (mp3mi_l12_batch_slots_export / _import) is a slot list's upload
+// and one k12_slot_park there.  No CPU fallback.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -21,7 +23,14 @@ struct mp3mi_l12_batch {
     unsigned test_flags;
     int debug;
     int max_frame_bytes;     // of the longest frame in an output row (l12_row_frame_bytes)
-    std::vector<l12_stream_cfg> cfg_h;
+    std::vector<l12_stream_cfg> cfg_h; // as created
+    // A bitrate per stream (mp3mi_l12_batch_encode_slots_kbps): kbps_h the slots' create-time bitrates and ceil_kbps the largest of
+    // them; slot_kbps_h the bitrate of the stream open in each slot, kbps_h[s] where none is; dev_kbps_h the bitrate the device's
+    // cfg[s] stands at.  cfg[s] is what slot_kbps_h says wherever a stream is open; elsewhere it may lag (rate_dirty: somewhere
+    // dev_kbps_h differs from kbps_h) and is put right, by k12_slot_rate, where a stream next begins there.
+    std::vector<int32_t> kbps_h, slot_kbps_h, dev_kbps_h;
+    int ceil_kbps;
+    bool rate_dirty;
     hipStream_t stream;
     hipEvent_t ev0, ev1;
     std::vector<hipEvent_t> kev; // five per chunk of the last call: around the four launches
@@ -47,8 +56,11 @@ struct mp3mi_l12_batch {
     // the control block of a per-slot call (l12_ctl_block), twice, taken in turn: calls are issued back to back, and an entry's
     // fence is recorded behind the last kernel that reads its device copy -- the host waits for it before it writes the staging
     // again (the per-slot call two before).  Created with the first per-slot call: a batch that never makes one holds none of it.
+    // An entry also carries the slot list of a park (mp3mi_l12_batch_slots_export / _import) and, behind the block, the entries
+    // of k12_slot_rate (l12_rate_at) -- that part only from the first turn that needs it (ctl_cap: bytes an entry has).
     typedef upload_ring<uint8_t, 2> ctl_ring;
     ctl_ring ctl;
+    size_t ctl_cap[2];
 };
 
 // The control block of a per-slot call, one array per slot after the other: what the kernels read of it (l12_geom) and the list of
@@ -69,9 +81,20 @@ static l12_ctl_block l12_ctl_at(uint8_t *p, int S)
     c.ctl = (uint8_t *) (c.list + S);
     return c;
 }
+// Behind the control block, at a multiple of 16 bytes: what k12_slot_rate reads, room for an entry per slot
+static size_t l12_rate_off(int S) { return (l12_ctl_bytes(S) + 15) / 16 * 16; }
+static size_t l12_rate_bytes(int S) { return (size_t) S * sizeof(l12_rate_entry); }
+static l12_rate_entry *l12_rate_at(uint8_t *p, int S) { return (l12_rate_entry *) (p + l12_rate_off(S)); }
+static void l12_rate_set(l12_rate_entry *e, int slot, const l12_stream_cfg &c)
+{
+    memset(e, 0, sizeof(*e));
+    e->cfg = c;
+    e->slot = slot;
+}
 struct l12_slot_call { // a per-slot call: its control block on the device, and the ring entry it took
     l12_ctl_block dev;
     int n_start;
+    int n_rate;         // slots whose cfg the call writes first (l12_rate_at of the entry)
     mp3mi_l12_batch::ctl_ring::entry *blk;
 };
 
@@ -108,6 +131,8 @@ extern "C" int mp3mi_l12_batch_create(mp3mi_l12_batch **out, int layer, int n_st
     b->hist[0] = b->hist[1] = b->fb_hist[0] = b->fb_hist[1] = NULL; b->hist_cur = 0;
     b->book.init(n_streams);
     memset((void *) &b->ctl, 0, sizeof(b->ctl));
+    b->ctl_cap[0] = b->ctl_cap[1] = 0;
+    b->ceil_kbps = 0; b->rate_dirty = false;
     if (hipGetDevice(&b->device) != hipSuccess) { delete b; return MP3MI_ERR_HIP; }
     b->cfg_h.resize((size_t) n_streams);
     b->max_frame_bytes = 0;
@@ -116,7 +141,11 @@ extern "C" int mp3mi_l12_batch_create(mp3mi_l12_batch **out, int layer, int n_st
         if (!l12_stream_cfg_of(layer, rate_hz, ri, channels, kbps ? kbps[s] : kbps_all, &c)) { delete b; return MP3MI_ERR_ARG; }
         const int fb = (int) l12_row_frame_bytes(layer, channels, c.frame_bits);
         if (fb > b->max_frame_bytes) b->max_frame_bytes = fb;
+        b->kbps_h.push_back(kbps ? kbps[s] : kbps_all);
+        if (b->kbps_h.back() > b->ceil_kbps) b->ceil_kbps = b->kbps_h.back();
     }
+    b->slot_kbps_h = b->kbps_h;
+    b->dev_kbps_h = b->kbps_h;
     const size_t budget = (size_t) (scratch_mb ? scratch_mb : 32768u) << 20;
     // per stream the chunk's buffers also hold the lb warm-up passes and three extra filterbank granules, whatever its length
     const size_t per_stream_fixed = (size_t) b->lb * channels * ((size_t) 3 * L12_ROW * sizeof(float) + 32 * sizeof(float)) + (size_t) 4 * channels * 576 * sizeof(double);
@@ -245,16 +274,66 @@ static int l12_hist_ensure(mp3mi_l12_batch *b)
 }
 
 // The control block this call takes, its entry created with its first turn; the host waits for the per-slot call two before,
-// whose kernels read the device copy and whose upload read the staging it is about to write
-static int l12_ctl_take(mp3mi_l12_batch *b, mp3mi_l12_batch::ctl_ring::entry **blk)
+// whose kernels read the device copy and whose upload read the staging it is about to write.  with_rates: the turn needs room for
+// the entry's rate entries too (l12_rate_at) -- an entry that was created without is created anew, once its readers are through
+static int l12_ctl_take(mp3mi_l12_batch *b, mp3mi_l12_batch::ctl_ring::entry **blk, bool with_rates = false)
 {
     mp3mi_l12_batch::ctl_ring::entry &en = b->ctl.take();
-    const size_t bytes = l12_ctl_bytes(b->n_streams);
-    if (!en.stage) CHK(hipHostMalloc((void **) &en.stage, bytes, 0));
-    if (!en.dev) CHK(hipMalloc((void **) &en.dev, bytes));
+    size_t &cap = b->ctl_cap[b->ctl.calls % 2u];
+    const size_t bytes = with_rates ? l12_rate_off(b->n_streams) + l12_rate_bytes(b->n_streams) : l12_ctl_bytes(b->n_streams);
     if (!en.free.ev) CHK(en.free.create());
     CHK(en.free.sync());
+    if (cap < bytes) {
+        if (en.stage) CHK(hipHostFree(en.stage));
+        en.stage = NULL;
+        CHK(hipFree(en.dev));
+        en.dev = NULL;
+        cap = 0;
+        CHK(hipHostMalloc((void **) &en.stage, bytes, 0));
+        CHK(hipMalloc((void **) &en.dev, bytes));
+        cap = bytes;
+    }
     *blk = &en;
+    return MP3MI_OK;
+}
+
+// The n_rate rate entries of a turn go up and k12_slot_rate writes cfg from them: on the batch's stream, ahead of the k12_alloc that
+// follows
+static int l12_rates_write(mp3mi_l12_batch *b, mp3mi_l12_batch::ctl_ring::entry *blk, int n_rate)
+{
+    const int S = b->n_streams;
+    CHK(hipMemcpyAsync(l12_rate_at(blk->dev, S), l12_rate_at(blk->stage, S), sizeof(l12_rate_entry) * (size_t) n_rate, hipMemcpyHostToDevice, b->stream));
+    mp3mi_launch_l12_slot_rate(l12_rate_at(blk->dev, S), n_rate, b->cfg, b->stream);
+    CHK(hipGetLastError());
+    return MP3MI_OK;
+}
+
+// Every stream is over: the slots are closed and at their create-time bitrates again (cfg follows where streams next begin)
+static void l12_streams_over(mp3mi_l12_batch *b)
+{
+    b->book.close();
+    if (b->rate_dirty) b->slot_kbps_h = b->kbps_h;
+}
+
+// Every stream starts afresh (a whole-file call, an encode_next with no stream open), at its slot's create-time bitrate: cfg goes
+// back to it where it stands at another -- those slots alone, in a turn of the control ring of its own.  A batch that never saw
+// another bitrate does nothing here.
+static int l12_rates_restore(mp3mi_l12_batch *b)
+{
+    if (!b->rate_dirty) return MP3MI_OK;
+    const int S = b->n_streams;
+    mp3mi_l12_batch::ctl_ring::entry *blk;
+    { const int rc = l12_ctl_take(b, &blk, true); if (rc != MP3MI_OK) return rc; }
+    l12_rate_entry *st = l12_rate_at(blk->stage, S);
+    int n = 0;
+    for (int s = 0; s < S; s++)
+        if (b->dev_kbps_h[(size_t) s] != b->kbps_h[(size_t) s]) l12_rate_set(&st[n++], s, b->cfg_h[(size_t) s]);
+    { const int rc = l12_rates_write(b, blk, n); if (rc != MP3MI_OK) return rc; }
+    CHK(blk->free.record(b->stream));
+    b->ctl.next();
+    b->dev_kbps_h = b->kbps_h;
+    b->slot_kbps_h = b->kbps_h;
+    b->rate_dirty = false;
     return MP3MI_OK;
 }
 
@@ -273,10 +352,12 @@ static int l12_encode_impl(mp3mi_l12_batch *b, const int16_t *pcm_dev, const int
     // equal chunks (as batch.cpp cuts a Layer III call): a short remainder -- 191 + 191 + 1 frames of the 383-frame bench call --
     // costs four full launches over all streams and recomputes the warm-up passes for one frame
     const int nchunks = (n_frames + b->chunk_frames - 1) / b->chunk_frames, cfr = (n_frames + nchunks - 1) / nchunks;
+    if (!sc && (whole_file || b->book.frames_all == 0)) { const int rc = l12_rates_restore(b); if (rc != MP3MI_OK) return rc; }
     if (sc) {
         // the control block goes up on the batch's one stream, ahead of its readers; the slots that START begin from silence
         { const int rc = l12_hist_ensure(b); if (rc != MP3MI_OK) return rc; }
         CHK(hipMemcpyAsync(sc->blk->dev, sc->blk->stage, l12_ctl_bytes(S), hipMemcpyHostToDevice, b->stream));
+        if (sc->n_rate > 0) { const int rc = l12_rates_write(b, sc->blk, sc->n_rate); if (rc != MP3MI_OK) return rc; }
         mp3mi_launch_l12_slot_begin(sc->dev.list, sc->n_start, C, b->hist[b->hist_cur], b->fb_hist[b->hist_cur], b->stream);
     }
     int chunk = 0;
@@ -337,7 +418,7 @@ static int l12_encode_impl(mp3mi_l12_batch *b, const int16_t *pcm_dev, const int
         b->hist_cur ^= 1;
         if (sc) CHK(sc->blk->free.record(b->stream)); // behind the last reader of the control block
         else b->book.frames_all += n_frames;          // (a per-slot call: l12_slots_impl keeps the slots' frames)
-    } else b->book.close();
+    } else l12_streams_over(b);
     CHK(hipEventRecord(b->ev1, b->stream));
     b->kev_chunks = chunk;
     b->timing_open = true;
@@ -353,8 +434,14 @@ extern "C" int mp3mi_l12_batch_encode(mp3mi_l12_batch *b, const int16_t *pcm_dev
 }
 
 // ---- per-slot streaming (mp3mi_l12_batch_encode_slots) ----
+// A bitrate a stream of this batch may have: one of the layer's, as create takes them, not above the ceiling that sized the rows
+static bool l12_kbps_ok(const mp3mi_l12_batch *b, int32_t kbps, l12_stream_cfg *c)
+{
+    return kbps <= b->ceil_kbps && l12_stream_cfg_of(b->layer, b->rate_hz, b->rate_idx, b->channels, kbps, c);
+}
+
 static int l12_slots_impl(mp3mi_l12_batch *b, const int16_t *pcm_dev, int n_frames, const uint8_t *ctl_host, const int32_t *n_samples_host,
-                          uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev)
+                          const int32_t *kbps_host, uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev)
 {
     if (!b || !pcm_dev || !ctl_host || !out_dev || !out_len_dev || n_frames < 1 || n_frames > b->max_frames) return MP3MI_ERR_ARG;
     if (out_stride < mp3mi_l12_batch_out_stride(b, n_frames)) return MP3MI_ERR_ARG;
@@ -363,24 +450,194 @@ static int l12_slots_impl(mp3mi_l12_batch *b, const int16_t *pcm_dev, int n_fram
     b->book.now(f.data());
     // every rule first: a call that breaks one leaves the batch as it was
     if (!b->book.rules_ok(f.data(), n_frames, b->spf, ctl_host, n_samples_host)) return MP3MI_ERR_ARG;
+    bool other_rate = false; // a stream STARTs at another bitrate than its slot was created with
+    for (int s = 0; kbps_host && s < S; s++) { // a STARTing stream's bitrate (0: the slot's own); any other slot's is 0, or what the open stream has
+        const bool open = f[s] >= 0, start = ctl_host[s] & MP3MI_SLOT_START;
+        const int32_t k = kbps_host[s];
+        l12_stream_cfg c;
+        if (k != 0 && (start ? !l12_kbps_ok(b, k, &c) : !(open && k == b->slot_kbps_h[(size_t) s]))) return MP3MI_ERR_ARG;
+        other_rate |= start && k != 0 && k != b->kbps_h[(size_t) s];
+    }
     ON_DEVICE(b);
+    // cfg is written for the START slots where it stands at another bitrate than the stream's -- never on a batch that has not
+    // seen another bitrate than its slots' own, which takes its turn and launches as it always did
+    const bool rates = b->rate_dirty || other_rate;
     l12_slot_call sc;
-    if (l12_ctl_take(b, &sc.blk) != MP3MI_OK) return MP3MI_ERR_HIP;
+    if (l12_ctl_take(b, &sc.blk, rates) != MP3MI_OK) return MP3MI_ERR_HIP;
     const l12_ctl_block st = l12_ctl_at(sc.blk->stage, S); // the staging copy: the caller's two arrays are copied here
     sc.dev = l12_ctl_at(sc.blk->dev, S);
     sc.n_start = b->book.fill(f.data(), n_frames, b->spf, ctl_host, n_samples_host, st.fabs, st.n_samples, st.ctl, st.list);
+    sc.n_rate = 0;
+    std::vector<int32_t> kb, dk; // the books behind the call, kept only where they can change
+    if (rates) { kb = b->slot_kbps_h; dk = b->dev_kbps_h; }
+    for (int i = 0; rates && i < sc.n_start; i++) {
+        const int s = st.list[i];
+        l12_stream_cfg c;
+        kb[(size_t) s] = (kbps_host && kbps_host[s]) ? kbps_host[s] : b->kbps_h[(size_t) s];
+        if (dk[(size_t) s] == kb[(size_t) s]) continue;
+        (void) l12_stream_cfg_of(b->layer, b->rate_hz, b->rate_idx, b->channels, kb[(size_t) s], &c); // (checked above, or at create)
+        l12_rate_set(&l12_rate_at(sc.blk->stage, S)[sc.n_rate++], s, c);
+        dk[(size_t) s] = kb[(size_t) s];
+    }
+    for (int s = 0; rates && s < S; s++)
+        if (ctl_host[s] & MP3MI_SLOT_END) kb[(size_t) s] = b->kbps_h[(size_t) s]; // the stream takes its bitrate with it
     const int rc = l12_encode_impl(b, pcm_dev, NULL, n_frames, out_dev, out_stride, out_len_dev, false, &sc);
     if (rc != MP3MI_OK) return rc;
     b->ctl.next();
+    if (rates) {
+        b->slot_kbps_h.swap(kb);
+        b->dev_kbps_h.swap(dk);
+        b->rate_dirty = b->dev_kbps_h != b->kbps_h;
+    }
     b->book.advance(f.data(), ctl_host, n_frames);
     b->book.settle(f.data());
     return MP3MI_OK;
 }
 
+extern "C" int mp3mi_l12_batch_encode_slots_kbps(mp3mi_l12_batch *b, const int16_t *pcm_dev, int n_frames, const uint8_t *ctl_host,
+                                                 const int32_t *n_samples_host, const int32_t *kbps_host, uint8_t *out_dev,
+                                                 size_t out_stride, uint32_t *out_len_dev)
+{
+    return l12_slots_impl(b, pcm_dev, n_frames, ctl_host, n_samples_host, kbps_host, out_dev, out_stride, out_len_dev);
+}
+
 extern "C" int mp3mi_l12_batch_encode_slots(mp3mi_l12_batch *b, const int16_t *pcm_dev, int n_frames, const uint8_t *ctl_host,
                                             const int32_t *n_samples_host, uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev)
 {
-    return l12_slots_impl(b, pcm_dev, n_frames, ctl_host, n_samples_host, out_dev, out_stride, out_len_dev);
+    return mp3mi_l12_batch_encode_slots_kbps(b, pcm_dev, n_frames, ctl_host, n_samples_host, NULL, out_dev, out_stride, out_len_dev);
+}
+
+extern "C" int mp3mi_l12_batch_slot_kbps(const mp3mi_l12_batch *b, int32_t *kbps_host)
+{
+    if (!b || !kbps_host) return MP3MI_ERR_ARG;
+    memcpy(kbps_host, b->slot_kbps_h.data(), sizeof(int32_t) * (size_t) b->n_streams);
+    return b->ceil_kbps;
+}
+
+// ---- parking and resuming streams (mp3mi_l12_batch_slots_export / _import) ----
+// A stream carries its two rows of PCM history and nothing else: the state record is the row of hist and behind it the row of
+// fb_hist, both of the copy the NEXT call reads (hist_cur); frames and bitrate travel in the ticket.  One turn of the control ring
+// takes the slot list up, one k12_slot_park moves the rows, on the batch's one stream -- behind every call before, ahead of every
+// call after; the host waits for nothing but the turn's own fence (the turn two before).
+extern "C" size_t mp3mi_l12_batch_slot_state_bytes(const mp3mi_l12_batch *b)
+{
+    return b ? (size_t) b->channels * (L12_PCM_HIST + MP3MI_PCM_HIST) * sizeof(int16_t) : 0;
+}
+
+// What export and import ask of their arguments alike
+static bool l12_park_args_ok(const mp3mi_l12_batch *b, int n, const int32_t *slots_host, const void *state_dev, size_t state_stride,
+                             const void *tickets)
+{
+    if (!b || !slots_host || !state_dev || !tickets || n < 1 || n > b->n_streams) return false;
+    if (state_stride < mp3mi_l12_batch_slot_state_bytes(b) || state_stride % 16 != 0 || (uintptr_t) state_dev % 16 != 0) return false;
+    std::vector<char> seen((size_t) b->n_streams, 0);
+    for (int i = 0; i < n; i++) {
+        const int32_t s = slots_host[i];
+        if (s < 0 || s >= b->n_streams || seen[(size_t) s]) return false;
+        seen[(size_t) s] = 1;
+    }
+    return true;
+}
+
+// The turn of an export (to_state) or an import: n_rate > 0 -- an import of streams at other bitrates than cfg holds for their
+// slots -- has the entry's rate entries written by fill_rates before they go up
+template <typename F> static int l12_park_run(mp3mi_l12_batch *b, int n, const int32_t *slots_host, void *state_dev, size_t state_stride,
+                                              int to_state, int n_rate, F fill_rates)
+{
+    mp3mi_l12_batch::ctl_ring::entry *blk;
+    { const int rc = l12_ctl_take(b, &blk, n_rate > 0); if (rc != MP3MI_OK) return rc; }
+    { const int rc = l12_hist_ensure(b); if (rc != MP3MI_OK) return rc; } // (an import as a fresh batch's first call)
+    memcpy(blk->stage, slots_host, sizeof(int32_t) * (size_t) n);
+    CHK(hipMemcpyAsync(blk->dev, blk->stage, sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, b->stream));
+    mp3mi_launch_l12_slot_park((const int32_t *) blk->dev, n, b->channels, b->hist[b->hist_cur], b->fb_hist[b->hist_cur], state_dev,
+                               state_stride, to_state, b->stream);
+    CHK(hipGetLastError());
+    if (n_rate > 0) {
+        fill_rates(l12_rate_at(blk->stage, b->n_streams));
+        const int rc = l12_rates_write(b, blk, n_rate);
+        if (rc != MP3MI_OK) return rc;
+    }
+    CHK(blk->free.record(b->stream));
+    b->ctl.next();
+    return MP3MI_OK;
+}
+
+extern "C" int mp3mi_l12_batch_slots_export(mp3mi_l12_batch *b, int n, const int32_t *slots_host, int close, void *state_dev,
+                                            size_t state_stride, mp3mi_l12_slot_ticket *tickets_host)
+{
+    static_assert(sizeof(mp3mi_l12_slot_ticket) == 56, "the ticket of mp3mi_l12.h has no padding");
+    if (!l12_park_args_ok(b, n, slots_host, state_dev, state_stride, tickets_host)) return MP3MI_ERR_ARG;
+    std::vector<int64_t> f((size_t) b->n_streams);
+    b->book.now(f.data());
+    for (int i = 0; i < n; i++)
+        if (f[(size_t) slots_host[i]] < 0) return MP3MI_ERR_ARG; // no stream open there
+    ON_DEVICE(b);
+    const int rc = l12_park_run(b, n, slots_host, state_dev, state_stride, 1, 0, [](l12_rate_entry *) {});
+    if (rc != MP3MI_OK) return rc;
+    for (int i = 0; i < n; i++) { // all of it host bookkeeping: no wait
+        const size_t s = (size_t) slots_host[i];
+        mp3mi_l12_slot_ticket &t = tickets_host[i];
+        memset(&t, 0, sizeof(t));
+        t.magic = MP3MI_L12_SLOT_TICKET_MAGIC;
+        t.version = MP3MI_L12_SLOT_TICKET_VERSION;
+        t.state_bytes = (uint64_t) mp3mi_l12_batch_slot_state_bytes(b);
+        t.layer = b->layer;
+        t.rate_hz = b->rate_hz;
+        t.channels = b->channels;
+        t.hdr_mode = b->mode;
+        t.hdr_flags = b->hdr_flags;
+        t.error_protection = b->crc;
+        t.kbps = b->slot_kbps_h[s];
+        t.frames = f[s];
+        if (close) { // the stream takes its bitrate with it (cfg follows at the slot's next START)
+            f[s] = -1;
+            b->slot_kbps_h[s] = b->kbps_h[s];
+        }
+    }
+    // (the whole-batch counter cannot say "all but these": the per-slot bookkeeping takes over; slot_book::settle hands back as ever)
+    b->book.settle(f.data());
+    return MP3MI_OK;
+}
+
+extern "C" int mp3mi_l12_batch_slots_import(mp3mi_l12_batch *b, int n, const int32_t *slots_host, const void *state_dev, size_t state_stride,
+                                            const mp3mi_l12_slot_ticket *tickets_host)
+{
+    if (!l12_park_args_ok(b, n, slots_host, state_dev, state_stride, tickets_host)) return MP3MI_ERR_ARG;
+    const int S = b->n_streams;
+    std::vector<int64_t> f((size_t) S);
+    b->book.now(f.data());
+    std::vector<l12_stream_cfg> val((size_t) n);
+    int n_rate = 0; // streams that arrive at another bitrate than cfg holds for their slots
+    for (int i = 0; i < n; i++) {
+        const size_t s = (size_t) slots_host[i];
+        const mp3mi_l12_slot_ticket &t = tickets_host[i];
+        if (f[s] >= 0) return MP3MI_ERR_ARG; // a stream is open there
+        if (t.magic != MP3MI_L12_SLOT_TICKET_MAGIC || t.version != MP3MI_L12_SLOT_TICKET_VERSION ||
+            t.state_bytes != (uint64_t) mp3mi_l12_batch_slot_state_bytes(b))
+            return MP3MI_ERR_ARG;
+        if (t.layer != b->layer || t.rate_hz != b->rate_hz || t.channels != b->channels || t.hdr_mode != b->mode ||
+            t.hdr_flags != b->hdr_flags || t.error_protection != b->crc || t.reserved != 0)
+            return MP3MI_ERR_ARG;
+        if (!l12_kbps_ok(b, t.kbps, &val[(size_t) i]) || t.frames < 0) return MP3MI_ERR_ARG;
+        n_rate += t.kbps != b->dev_kbps_h[s];
+    }
+    ON_DEVICE(b);
+    // cfg of a resumed stream is rebuilt here, from the ticket's checked bitrate: nothing of a device record is used as an index
+    const int rc = l12_park_run(b, n, slots_host, const_cast<void *>(state_dev), state_stride, 0, n_rate, [&](l12_rate_entry *rt) {
+        for (int i = 0; i < n; i++)
+            if (tickets_host[i].kbps != b->dev_kbps_h[(size_t) slots_host[i]]) l12_rate_set(rt++, slots_host[i], val[(size_t) i]);
+    });
+    if (rc != MP3MI_OK) return rc;
+    for (int i = 0; i < n; i++) {
+        const size_t s = (size_t) slots_host[i];
+        f[s] = tickets_host[i].frames;
+        b->slot_kbps_h[s] = b->dev_kbps_h[s] = tickets_host[i].kbps;
+    }
+    if (n_rate > 0) b->rate_dirty = b->dev_kbps_h != b->kbps_h;
+    // the per-slot bookkeeping from here on, also on a batch nothing has run on yet (slot_book::settle hands back only with every
+    // slot open at one frame count, and then the whole-batch path continues them from the same history)
+    b->book.settle(f.data());
+    return MP3MI_OK;
 }
 
 extern "C" int mp3mi_l12_batch_slot_frames(const mp3mi_l12_batch *b, int64_t *frames_host)
@@ -398,7 +655,7 @@ extern "C" int mp3mi_l12_batch_encode_next(mp3mi_l12_batch *b, const int16_t *pc
         // go on and the other slots stay closed
         if (b->book.any_open()) {
             std::vector<uint8_t> ctl((size_t) b->n_streams, 0);
-            return l12_slots_impl(b, pcm_dev, n_frames, ctl.data(), NULL, out_dev, out_stride, out_len_dev);
+            return l12_slots_impl(b, pcm_dev, n_frames, ctl.data(), NULL, NULL, out_dev, out_stride, out_len_dev);
         }
         if (!pcm_dev || !out_dev || !out_len_dev || n_frames < 1 || n_frames > b->max_frames || out_stride < mp3mi_l12_batch_out_stride(b, n_frames))
             return MP3MI_ERR_ARG; // (before the bookkeeping changes)
@@ -426,7 +683,7 @@ extern "C" int mp3mi_l12_batch_flush(mp3mi_l12_batch *b, uint8_t *out_dev, size_
         CHK(blk->free.record(b->stream));
         b->ctl.next();
     }
-    b->book.close();
+    l12_streams_over(b);
     CHK(hipGetLastError());
     return MP3MI_OK;
 }
@@ -434,7 +691,7 @@ extern "C" int mp3mi_l12_batch_flush(mp3mi_l12_batch *b, uint8_t *out_dev, size_
 extern "C" int mp3mi_l12_batch_reset(mp3mi_l12_batch *b)
 {
     if (!b) return MP3MI_ERR_ARG;
-    b->book.close();
+    l12_streams_over(b);
     return MP3MI_OK;
 }
 

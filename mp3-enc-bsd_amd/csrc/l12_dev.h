@@ -79,6 +79,13 @@ struct l12_stream_cfg {
     int32_t bitrate_index, frame_bits, table, sblimit;
 };
 
+/* what k12_slot_rate reads (mp3mi_l12_batch_encode_slots_kbps): the cfg the host computed for a slot whose stream begins or arrives
+   at another bitrate than cfg[slot] stands at.  32 bytes */
+struct l12_rate_entry {
+    l12_stream_cfg cfg;
+    int32_t slot, pad[3];
+};
+
 /* per frame, device: the seams tests compare with oracle/stage_dump_l12.h (written only when the batch's debug
  * switch is on) */
 struct l12_frame_dbg {
@@ -100,6 +107,14 @@ void mp3mi_launch_l12_flush(int n_streams, const uint8_t *slot_ctl, uint8_t *out
 /* k12_slot_begin: the n_list slots of `list` (a call's MP3MI_SLOT_START slots) begin from silence: their rows of hist
    ([n_streams][L12_PCM_HIST][channels]) and fb_hist ([n_streams][MP3MI_PCM_HIST][channels]) are zeroed */
 void mp3mi_launch_l12_slot_begin(const int32_t *list, int n_list, int channels, int16_t *hist, int16_t *fb_hist, hipStream_t st);
+/* k12_slot_park: the two history rows of the n_list slots of `list` move between the live buffers and the state records
+   (char *) state + i * state_stride ([hist row][fb_hist row], channels * (L12_PCM_HIST + MP3MI_PCM_HIST) * 2 bytes): to_state
+   gathers them into the records (export), otherwise the records are scattered into the rows (import).  state and state_stride
+   are multiples of 16 */
+void mp3mi_launch_l12_slot_park(const int32_t *list, int n_list, int channels, int16_t *hist, int16_t *fb_hist, void *state,
+                                size_t state_stride, int to_state, hipStream_t st);
+/* k12_slot_rate: cfg[e[i].slot] = e[i].cfg, i < n (e: device, 16-byte aligned; no slot listed twice) */
+void mp3mi_launch_l12_slot_rate(const l12_rate_entry *e, int n, l12_stream_cfg *cfg, hipStream_t st);
 extern "C" int mp3mi_build_tables_l12(mp3mi_tables_l12 *T, int rate_idx, int layer);
 #endif
 

@@ -29,10 +29,13 @@ The line then carries park_vs_continue and the bytes of a state record.
 
 --layer 1|2: cases (a), (b), (c) on the Layer I / II batch (mp3mi_l12_batch_encode_next, mp3mi_l12_batch_encode_slots): Layer I at
 192 kbps in ticks of 12 frames, Layer II at 128 kbps in ticks of 4 (--frames sets another length); in (b) one slot STARTs a tick
-after the others, or the batch would hand every tick back to the whole-batch path (profiles/l12_slots_bench.jsonl).
+after the others, or the batch would hand every tick back to the whole-batch path (profiles/l12_slots_bench.jsonl).  --mixed-kbps:
+the batch is created at the layer's largest bitrate (448 / 384) and every START of (b) and (c) draws 64 / 128 / 192 / 448 (Layer I) or
+64 / 128 / 192 / 384 (Layer II: allocation tables 2, 0, 1, 1 -- mp3mi_l12_batch_encode_slots_kbps).  --park N: case (p) as above, on
+mp3mi_l12_batch_slots_export / _import (profiles/l12_park_bench.jsonl).
 
 usage: slots_bench.py [--calls 20] [--frames 32] [--streams 4096] [--reps 3] [--mixed-kbps] [--park N] [--host [--occupancy 1.0] [--map]]
-       slots_bench.py --layer 1|2 [--calls 20] [--frames N] [--streams 4096] [--reps 3]"""
+       slots_bench.py --layer 1|2 [--calls 20] [--frames N] [--streams 4096] [--reps 3] [--mixed-kbps] [--park N]"""
 import argparse
 import importlib
 import json
@@ -59,8 +62,8 @@ def main():
     ap.add_argument("--layer", type=int, default=3, choices=(1, 2, 3), help="1 | 2: the Layer I / II batch (mp3mi_l12_batch_encode_slots)")
     a = ap.parse_args()
     if a.layer != 3:
-        if a.host or a.mixed_kbps or a.park:
-            ap.error("--layer 1|2 times the three resident cases only")
+        if a.host:
+            ap.error("--layer 1|2 times the resident cases only")
         return l12_main(a)
     if a.host:
         if a.mixed_kbps or a.park:
@@ -157,11 +160,17 @@ def main():
 
 
 def l12_main(a):
-    """--layer 1|2: cases (a), (b), (c) on the Layer I / II batch; calls of --frames frames (default: 12 Layer I, 4 Layer II --
-    about 0.1 s of audio a tick), Layer I at 192 kbps, Layer II at 128"""
+    """--layer 1|2: cases (a), (b), (c) and, with --park, (p) on the Layer I / II batch; calls of --frames frames (default: 12 Layer I,
+    4 Layer II -- about 0.1 s of audio a tick), Layer I at 192 kbps, Layer II at 128; --mixed-kbps: created at 448 / 384, a drawn
+    bitrate per START"""
     import torch
     mp3 = importlib.import_module("mp3-enc-bsd_amd")
-    S, rate, ch, kbps = a.streams, 44100, 2, 192 if a.layer == 1 else 128
+    S, rate, ch = a.streams, 44100, 2
+    kbps = ((448 if a.layer == 1 else 384) if a.mixed_kbps else (192 if a.layer == 1 else 128))
+    rates = np.array([64, 128, 192, kbps], np.int32)
+    N = a.park
+    if N and not 0 < 2 * N <= S:
+        raise SystemExit("--park N needs 2 N <= streams")
     nf = a.frames if a.frames != 32 else (12 if a.layer == 1 else 4)
     full = nf * mp3.L12_FRAME_SAMPLES[a.layer]
     dev = torch.device("cuda:0")
@@ -174,6 +183,16 @@ def l12_main(a):
     torch.cuda.synchronize()
     rng = np.random.default_rng(1)
     every = np.ones(S, bool)
+    drawn = []  # the bitrates of run_continue's streams
+
+    def draw(start):
+        """kbps of a call: a drawn bitrate for every START (None without --mixed-kbps: the call without the array)"""
+        return np.where(start, rates[rng.integers(0, 4, S)], 0).astype(np.int32) if a.mixed_kbps else None
+
+    def slots(**kw):
+        if kw.get("kbps") is None:
+            kw.pop("kbps", None)  # (the call as it was before there was an array)
+        b.encode_slots(pcm, nf, out, out_len, **kw)
 
     def run_next():
         for _ in range(a.calls):
@@ -184,13 +203,15 @@ def l12_main(a):
         # back to the whole-batch path, which is case (a))
         first = every.copy()
         first[S - 1] = False
-        b.encode_slots(pcm, nf, out, out_len, start=first)
-        b.encode_slots(pcm, nf, out, out_len, start=~first)
+        kb = draw(every)
+        drawn[:] = [] if kb is None else [kb]
+        slots(start=first, kbps=None if kb is None else np.where(first, kb, 0))
+        slots(start=~first, kbps=None if kb is None else np.where(first, 0, kb))
         for _ in range(a.calls - 2):
-            b.encode_slots(pcm, nf, out, out_len)
+            slots()
 
     def run_churn():
-        b.encode_slots(pcm, nf, out, out_len, start=every)
+        slots(start=every, kbps=draw(every))
         closed = np.zeros(S, bool)
         for _ in range(a.calls - 1):
             start = closed.copy()
@@ -198,11 +219,26 @@ def l12_main(a):
             end[rng.choice(np.flatnonzero(~closed), S // 32, replace=False)] = True
             ns = np.full(S, full, np.int32)
             ns[end] = rng.integers(0, full + 1, int(end.sum()))
-            b.encode_slots(pcm, nf, out, out_len, start=start, end=end, n_samples=ns)
+            slots(start=start, end=end, n_samples=ns, kbps=draw(start))
             closed = end
 
+    state = [torch.zeros((N, b.slot_state_bytes()), dtype=torch.uint8, device=dev) for _ in range(2)] if N else None
+
+    def run_park():
+        """every slot STARTs; tick k >= 1 resumes the N streams tick k - 1 parked, in the slots they left, parks the streams of the
+        next N slots of a random walk (record sets by the tick's parity), and encodes: S - N streams are live in every tick"""
+        order = rng.permutation(S).astype(np.int32)
+        slots(start=every, kbps=draw(every))
+        away = None  # (slots, tickets) of the tick before
+        for k in range(1, a.calls):
+            if away is not None:
+                b.import_slots(away[0], state[(k - 1) & 1], away[1])
+            sl = order[((k - 1) * N + np.arange(N)) % S]
+            away = (sl, b.export_slots(sl, state[k & 1]))
+            slots()
+
     res = {}
-    for name, fn in (("encode_next", run_next), ("slots_continue", run_continue), ("slots_churn", run_churn)):
+    for name, fn in (("encode_next", run_next), ("slots_continue", run_continue), ("slots_churn", run_churn)) + ((("slots_park", run_park),) if N else ()):
         best = None
         for r in range(a.reps + 1):  # the first run warms up
             b.reset()
@@ -215,11 +251,14 @@ def l12_main(a):
             if r > 0:
                 best = ms if best is None else min(best, ms)
         res[name] = round(best, 3)
+    state_bytes = b.slot_state_bytes() if N else 0
     b.close()
     print(json.dumps({"tool": "slots_bench --layer", "layer": a.layer, "streams": S, "frames_per_call": nf, "calls": a.calls, "rate": rate,
                       "channels": ch, "kbps": kbps, "ms_per_call": res,
                       "continue_vs_next": round(res["slots_continue"] / res["encode_next"], 4),
                       "churn_vs_continue": round(res["slots_churn"] / res["slots_continue"], 4),
+                      **({"mixed_kbps": True, "mean_kbps_continue": round(float(drawn[0].mean()), 1)} if a.mixed_kbps else {}),
+                      **({"park": N, "park_vs_continue": round(res["slots_park"] / res["slots_continue"], 4), "state_bytes": state_bytes} if N else {}),
                       "source_hash": mp3.lib().mp3mi_source_hash().decode()}))
 
 
