@@ -831,6 +831,11 @@ struct call_shape {
     const uint8_t *slot_ctl;  // device, per slot: MP3MI_SLOT_DEV_* (mp3mi_geom::slot_ctl); both NULL otherwise
     bool whole_file;
 };
+struct item_view { // an ITEM of a call: the frames of one chunk of one part of the streams (encode_impl)
+    mp3mi_geom g;      // of the part: n_streams, n_samples / hist / out_base advanced
+    int slot, ev;      // double-buffer slot of the chunk; index of the (slot, part) events
+    size_t s0, rec0;   // first stream; (granule, channel) records of the chunk before the part
+};
 static mp3mi_geom call_geom(const mp3mi_batch *b, const call_shape &c, int f0, int nf, size_t s0, int n)
 {
     mp3mi_geom g = mp3mi_make_geom(n, b->channels, b->rate_idx, c.n_frames, f0, nf);
@@ -1065,45 +1070,61 @@ extern "C" int mp3mi_batch_slots_import(mp3mi_batch *b, int n, const int32_t *sl
     return MP3MI_OK;
 }
 
-static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_samples_dev, int n_frames, uint8_t *out_dev,
-                       size_t out_stride, uint32_t *out_len_dev, bool whole_file, const host_call *hc, const slot_call *sc)
+// One call of encode_impl, as its stages (below, in the order of their calls) share it: the caller's arguments, the call's shape,
+// its cut into chunks and items, its timing set.  (Built behind fresh_start, which decides the shape's fabs0.)
+struct encode_call {
+    mp3mi_batch *b;
+    const int16_t *pcm_dev; uint8_t *out_dev; size_t out_stride; uint32_t *out_len_dev; // the device buffers the kernels read and write
+    bool whole_file;
+    const host_call *hc; // NULL: the caller's buffers are those
+    const slot_call *sc; // NULL: no per-slot call
+    call_shape cs;
+    int nchunks, cfr, P, n_items; // chunks, frames of a chunk, parts, items = nchunks * P
+    size_t pcm_pitch;
+    mp3mi_batch::timing_set *ts;
+    bool joined; // the first item runs beside the held k_loop of the call before (join_or_release)
+    size_t psy_state_bytes, loop_state_bytes;
+    item_view view(int k) const
+    {
+        item_view v;
+        const int c = k / P, part = k % P, S = b->n_streams;
+        const int f0 = c * cfr;
+        const int nf = (cs.n_frames - f0 < cfr) ? cs.n_frames - f0 : cfr;
+        v.s0 = (size_t) part * (size_t) b->part_streams;
+        const int n = S - (int) v.s0 < b->part_streams ? S - (int) v.s0 : b->part_streams;
+        v.g = call_geom(b, cs, f0, nf, v.s0, n);
+        v.slot = (c + b->slot_base) & 1;
+        v.ev = v.slot * P + part;
+        v.rec0 = v.s0 * 2 * (size_t) nf * (size_t) b->channels;
+        return v;
+    }
+    // A part larger than the resident wavefronts (on the emulator, whose single CU holds 16) keeps every SIMD full to its end,
+    // so the feed-forward kernels of the next item find no freed slots beside it, only cycles to take: there the item's
+    // stage Y waits for the k_loop before it, and nothing of stage X runs beside that k_loop.
+    bool y_after(const item_view &iv) const { return iv.g.n_streams > mp3mi_loop_resident(); }
+    // (A per-slot call on host buffers does not join: its first transforms wait for the tick's PCM to cross PCIe, and a
+    // k_loop held for that long -- a tick is one chunk, so the held launch is the whole tick before -- leaves the chip idle
+    // during the upload: 29.7 ms per 4096 x 32 tick against 16.4 resident.  Let go at once, that k_loop runs beside the upload.)
+    bool waits_for_upload() const { return (hc && sc) || b->feed_host_call; } // (a feeder's tick on host buffers: the same upload, the same rule)
+};
+
+static int fresh_start(mp3mi_batch *b, bool whole_file, const slot_call *sc)
 {
-    if (!b || !pcm_dev || !out_dev || !out_len_dev || n_frames <= 0 || n_frames > b->max_frames) return MP3MI_ERR_ARG;
-    if (out_stride < min_out_stride(b, n_frames, !whole_file)) return MP3MI_ERR_ARG;
-    ON_DEVICE(b);
-    const int S = b->n_streams, C = b->channels;
-    if (b->debug && !b->sb_dbg) {
-        const size_t ngc = (size_t) S * 2 * (size_t) b->chunk_frames * (size_t) C;
-        CHK(dev_alloc(b, &b->sb_dbg, ngc * 576 * sizeof(double)));
-    }
-    // The call before this one may still be running.  Its kernels and this call's share nothing but the batch's own
-    // buffers, and every one of those is either touched on ONE stream only (in-order: the FFT outputs, the subband
-    // samples, the psy state and the PCM history on the front stream; ix, the side information, the loop state, the
-    // carry and the caller's output on the loop stream) or double-buffered across the two (psy / xr / prep: the slots
-    // go on alternating from call to call, and a slot's writer waits for the k_loop that read it last, ev_loop).  So
-    // this call's feed-forward kernels start at once and fill the chip while the last k_loop of the call before -- 4096
-    // wavefronts, serial, nothing beside them -- runs out: back-to-back calls lose no pipeline fill.
-    // a whole-file call starts every stream afresh; a streaming call continues (the first one after create / reset /
-    // flush / a whole-file call starts afresh too)
-    if (whole_file || (!sc && b->book.frames_all == 0 && !b->fresh)) {
-        for (const carried_region &r : b->carried) // (each region on the stream that owns it)
-            if (r.zero) CHK(hipMemsetAsync(r.base, 0, r.bytes * (size_t) S, r.loop ? b->lstream : b->stream));
-        // streams that per-slot calls began at bitrates of their own end here.  (The host mirror is reset with the copy's enqueue, not
-        // with the call's success: a HIP error further down leaves a call half enqueued, like any MP3MI_ERR_HIP of this function,
-        // and no entry point recovers a batch from that, so the mirror is not rolled back.)
-        if (rates_restore(b) != MP3MI_OK) return MP3MI_ERR_HIP;
-        b->book.frames_all = 0;
-    }
-    // (a per-slot call: every slot has its own frame index, in the control block; k_loop counts the frame of a status from the
-    // call's first, and k_stream_tail places it in the stream)
-    const long fabs0 = sc ? 0 : b->book.frames_all;
-    if (sc) n_samples_dev = sc->dev.n_samples;
-    const bool kept = b->status_kept;
-    b->fresh = false;
-    b->status_kept = false;
-    if (b->place_cost) CHK(hipMemsetAsync(b->place_cost, 0, sizeof(int) * (size_t) S, b->lstream)); // first chunk: order = identity
-    if (hc) CHK(b->hio.slot[hc->slot].out_free.wait_on(b->lstream)); // the call two before this one copied out of it
-    CHK(hipMemsetAsync(out_dev, 0, out_stride * (size_t) S, b->lstream)); // (behind the formatter of the call before: it may be the same buffer)
+    if (!(whole_file || (!sc && b->book.frames_all == 0 && !b->fresh))) return MP3MI_OK;
+    for (const carried_region &r : b->carried) // (each region on the stream that owns it)
+        if (r.zero) CHK(hipMemsetAsync(r.base, 0, r.bytes * (size_t) b->n_streams, r.loop ? b->lstream : b->stream));
+    // streams that per-slot calls began at bitrates of their own end here.  (The host mirror is reset with the copy's enqueue, not
+    // with the call's success: a HIP error further down leaves a call half enqueued, like any MP3MI_ERR_HIP of this function,
+    // and no entry point recovers a batch from that, so the mirror is not rolled back.)
+    if (rates_restore(b) != MP3MI_OK) return MP3MI_ERR_HIP;
+    b->book.frames_all = 0;
+    return MP3MI_OK;
+}
+
+static int control_block(const encode_call &c, bool kept) // (kept: status_dev still holds the status of the streams the last flush ended)
+{
+    mp3mi_batch *b = c.b;
+    const slot_call *sc = c.sc;
     if (sc) {
         // the control block goes up on the front stream, ahead of everything of the call that reads it; the START slots' state is
         // cleared on the stream that owns it: psy state and PCM history before the call's first transform, the loop state, the
@@ -1115,7 +1136,7 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
         CHK(hipGetLastError());
         CHK(hipStreamWaitEvent(b->lstream, b->ev_ctl_up, 0));
         if (kept) { // the last flush ended every stream and reset the state: the ended streams' status stays until their slot STARTs
-            mp3mi_launch_status_scatter(S, (int32_t *) b->loop_state, (int) (sizeof(mp3mi_loop_state) / 4), b->status_dev, b->lstream);
+            mp3mi_launch_status_scatter(b->n_streams, (int32_t *) b->loop_state, (int) (sizeof(mp3mi_loop_state) / 4), b->status_dev, b->lstream);
             CHK(hipGetLastError());
         }
         slot_begin(b, true, sc->dev.list, sc->n_start);
@@ -1125,18 +1146,308 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
             CHK(hipGetLastError());
         }
     }
-    if (!whole_file && (sc ? sc->any_continue : fabs0 > 0)) { // the bytes earlier calls formatted but could not deliver lead the rows
-        mp3mi_launch_carry_in(S, b->carry, b->carry_len, out_dev, out_stride, b->lstream);
+    if (!c.whole_file && (sc ? sc->any_continue : c.cs.fabs0 > 0)) { // the bytes earlier calls formatted but could not deliver lead the rows
+        mp3mi_launch_carry_in(b->n_streams, b->carry, b->carry_len, c.out_dev, c.out_stride, b->lstream);
         CHK(hipGetLastError());
     }
-    const int nchunks = (n_frames + b->chunk_frames - 1) / b->chunk_frames;
-    const int P = b->n_parts, n_items = nchunks * P;
+    return MP3MI_OK;
+}
+
+static int timing_setup(const encode_call &c)
+{
+    mp3mi_batch *b = c.b;
     if (harvest_timing(b, (int) (b->call_no & 1)) != MP3MI_OK) return MP3MI_ERR_HIP; // (the call before the last one)
-    mp3mi_batch::timing_set &ts = b->ts[b->call_no & 1];
-    CHK(grow_events(ts.loop_ev, 2 * (size_t) n_items, 0));
-    ts.launches = n_items;
+    mp3mi_batch::timing_set &ts = *c.ts;
+    CHK(grow_events(ts.loop_ev, 2 * (size_t) c.n_items, 0));
+    ts.launches = c.n_items;
     ts.kernels = 0;
     CHK(hipEventRecord(ts.ev0, b->stream));
+    return MP3MI_OK;
+}
+
+// The whole call's PCM, chunk by chunk, in order on the upload stream: a 2-D copy per chunk (every stream's samples of
+// the chunk's frames; the layout on the device is the caller's).  The chunk's first kernel waits for its copy, so chunk
+// c + 1 crosses PCIe while chunk c is encoded -- and, with calls issued back to back, the next call's first chunk
+// while this call's last one is.
+// A per-slot call with a row map: the caller's rows are dense, one per live slot.  They cross as they are, into the
+// dense device buffer, and behind each chunk's copy k_rows_in spreads the chunk's columns into the slot rows the
+// kernels read -- on the upload stream, so a chunk's rows are in place while the chunk before is encoded.  (The map is
+// in the control block, which the front stream uploads: ev_ctl_up.)
+static int upload_chunks(const encode_call &c)
+{
+    mp3mi_batch *b = c.b;
+    const size_t C = (size_t) b->channels, pcm_pitch = c.pcm_pitch;
+    mp3mi_batch::host_io &H = b->hio;
+    mp3mi_batch::host_io::io_slot &io = H.slot[c.hc->slot];
+    const bool mapped = c.hc->rows_dev != NULL;
+    const size_t R = mapped ? (size_t) c.hc->n_rows : (size_t) b->n_streams;
+    CHK(io.pcm_free.wait_on(H.h2d)); // (the kernels of the call two before this one)
+    for (std::vector<hipEvent_t> *v : {&io.t_up, &io.t_dn}) CHK(grow_events(*v, 2 * (size_t) c.nchunks, 0));
+    for (std::vector<hipEvent_t> *v : {&io.ev_fmt, &io.ev_in}) CHK(grow_events(*v, (size_t) c.nchunks, hipEventDisableTiming));
+    io.n_chunks = c.nchunks;
+    io.bytes_up = io.bytes_dn = 0.0;
+    if (mapped) CHK(hipStreamWaitEvent(H.h2d, b->ev_ctl_up, 0));
+    for (int k = 0; k < c.nchunks; k++) {
+        const int f0 = k * c.cfr, nf = (c.cs.n_frames - f0 < c.cfr) ? c.cs.n_frames - f0 : c.cfr;
+        const size_t off = (size_t) f0 * 1152 * C, width = (size_t) nf * 1152 * C * sizeof(int16_t);
+        int16_t *dst = mapped ? io.pcm_rows : io.pcm;
+        CHK(hipEventRecord(io.t_up[2 * k], H.h2d));
+        CHK(hipMemcpy2DAsync(dst + off, pcm_pitch * sizeof(int16_t), c.hc->pcm + off, pcm_pitch * sizeof(int16_t), width, R,
+                             hipMemcpyHostToDevice, H.h2d));
+        CHK(hipEventRecord(io.t_up[2 * k + 1], H.h2d));
+        io.bytes_up += (double) width * (double) R;
+        if (mapped) {
+            mp3mi_launch_rows_in(c.hc->rows_dev, c.hc->n_rows, io.pcm_rows, io.pcm, pcm_pitch * sizeof(int16_t), off * sizeof(int16_t), width, H.h2d);
+            CHK(hipGetLastError());
+            CHK(hipEventRecord(io.ev_in[k], H.h2d));
+        }
+    }
+    return MP3MI_OK;
+}
+
+// which: 1 the FFTs, 2 k_cw, the partition sums (k_part) and k_psy (passed on as mp3mi_launch_fft's which, whose bit 1 is k_cw)
+static int stage_x(const encode_call &c, int k, int which)
+{
+    mp3mi_batch *b = c.b;
+    const item_view v = c.view(k);
+    const size_t r = v.rec0;
+    if (c.hc && (which & 1) && k % c.P == 0) // the chunk's PCM is up (and in its slots' rows)
+        CHK(hipStreamWaitEvent(b->stream, c.hc->rows_dev ? b->hio.slot[c.hc->slot].ev_in[k / c.P] : b->hio.slot[c.hc->slot].t_up[2 * (k / c.P) + 1], 0));
+    mp3mi_launch_fft(b->T, v.g, c.pcm_dev + v.s0 * c.pcm_pitch, b->energy_l + r * MP3MI_HBLK_P, b->energy_s + r * 3 * MP3MI_HBLK_S,
+                     b->fft_bins + r * MP3MI_FFT_BINS, b->cw_mid + r * 50, b->hist6 + r * 12, b->stream, which);
+    CHK(hipGetLastError());
+    if (which & 2) {
+        // the k_loop that read this region of the slot last (two chunks ago, maybe in the call before)
+        CHK(b->ev_loop[v.ev].wait_on(b->stream));
+        mp3mi_launch_psy(b->T, v.g, b->energy_l + r * MP3MI_HBLK_P, b->energy_s + r * 3 * MP3MI_HBLK_S, b->cw_mid + r * 50, b->hist6 + r * 12,
+                         b->fft_bins + r * MP3MI_FFT_BINS, b->cw_fix, (char *) b->psy_state + v.s0 * c.psy_state_bytes, b->part_eb + r * MP3MI_PART_P,
+                         b->part_cb + r * MP3MI_PART_P, b->psy[v.slot] + r, b->stream);
+        CHK(hipGetLastError());
+    }
+    return MP3MI_OK;
+}
+
+// The call before this one may have left its last k_loop HELD (k_hold): this call's first item then takes the place
+// "the next item" has inside a call -- its transforms run now, in front of that k_loop, the hold is let go behind them,
+// and the rest of the item runs beside that k_loop, behind the gate, like every item after it.
+static int join_or_release(encode_call &c)
+{
+    mp3mi_batch *b = c.b;
+    if (!(b->held && !c.y_after(c.view(0)) && !c.waits_for_upload())) {
+        hold_release(b);
+        return stage_x(c, 0, 3);
+    }
+    if (stage_x(c, 0, 1) != MP3MI_OK) return MP3MI_ERR_HIP;
+    mp3mi_launch_hold_release(b->hold_flag_d, b->hold_seq, b->stream);
+    CHK(hipGetLastError());
+    b->held = false;
+    c.joined = true;
+    return MP3MI_OK;
+}
+
+// ---- front stream: everything that does not depend on the bit reservoir ----
+static int item_front(const encode_call &c, int k, const item_view &v)
+{
+    mp3mi_batch *b = c.b;
+    const mp3mi_geom &g = v.g;
+    const size_t r = v.rec0, C = (size_t) b->channels;
+    const bool follows = k >= 1 || c.joined; // a k_loop runs (or is about to) that this item's kernels go beside
+    // what of stage X runs beside k_loop: all but the FFTs -- k_cw, k_part, k_psy are small in registers and LDS, the
+    // item's FFTs were done before that launch started, and the region k_psy writes was read last by the launch before
+    // it: 238.2 vs 247.2 ms per 4096 x 383 step with them between the launches.
+    const bool beside = !c.y_after(v);
+    if (k >= 1 && !beside) { // (the k_loop before this item's: view(k - 1))
+        const item_view pv = c.view(k - 1);
+        CHK(b->ev_loop[pv.ev].wait_on(b->stream));
+    } else if (follows) // this item's kernels run behind k_loop(k - 1), once that is resident (<= 300 us)
+        mp3mi_launch_gate(b->gate_count, b->gate_first - 16u, 30000u, b->stream);
+    if (beside && follows && stage_x(c, k, 2) != MP3MI_OK) return MP3MI_ERR_HIP;
+    mp3mi_launch_filter(b->T, g, c.pcm_dev + v.s0 * c.pcm_pitch, b->sbs + v.s0 * (size_t) (g.n_gran + 1) * C * 576,
+                        b->debug ? b->sb_dbg + r * 576 : NULL, b->stream);
+    CHK(hipGetLastError());
+    // k_mdct's tail also computes the loop's stateless head and lists the records it could not decide; k_prep works
+    // through the list (MP3MI_TEST_PREP_EXACT: through every record, the reference's way)
+    CHK(hipMemsetAsync(&b->prep_fix->count, 0, sizeof(unsigned), b->stream));
+    mp3mi_launch_mdct(b->T, g, b->psy[v.slot] + r, b->sbs + v.s0 * (size_t) (g.n_gran + 1) * C * 576, b->xr[v.slot] + r * 576,
+                      b->prep[v.slot] + r, b->prep_fix, b->stream);
+    CHK(hipGetLastError());
+    mp3mi_launch_prep(b->T, g, b->xr[v.slot] + r * 576, b->psy[v.slot] + r, b->prep[v.slot] + r, b->prep_exact ? NULL : b->prep_fix, b->prep_exact, b->stream);
+    CHK(hipGetLastError());
+    if (k + 1 < c.n_items) {
+        // (The next item's transforms take whole CUs' LDS: they run BETWEEN two k_loop launches.  Nothing but the queue behind
+        // a busy chip sees to that -- this item's kernels take longer than the k_loop they run beside -- and an explicit wait
+        // for that k_loop's end costs 1.4 ms per step, because the transforms then no longer slip in as its last CUs drain:
+        // profiles/r05_experiments.txt, E7.)
+        if (stage_x(c, k + 1, c.y_after(c.view(k + 1)) ? 3 : 1) != MP3MI_OK) return MP3MI_ERR_HIP;
+    }
+    CHK(hipEventRecord(b->ev_front[v.ev], b->stream));
+    return MP3MI_OK;
+}
+
+// The call's file bytes, behind its last formatter -- a streaming call's behind its k_stream_tail, which settles the lengths
+// -- as ONE copy: rows of the caller's stride when that is the device
+// buffer's (mp3mi_batch_out_stride(b, max_frames): a plain copy, which the DMA engines take), a 2-D copy
+// otherwise.  (A window of columns per chunk -- the bytes that became final with it -- was measured first: the
+// runtime runs such rectangles as copy KERNELS, 11 ms each beside the encoder's own, and the step lost 56 ms;
+// profiles/r04_experiments.txt.  With calls issued back to back this copy runs beside the next call's kernels.)
+// With a row map k_rows_out gathers the listed slots' bytes and lengths into dense rows of the caller's stride first, so
+// that the copy is plain whatever the stride and moves the live rows only.
+static int download(const encode_call &c)
+{
+    mp3mi_batch *b = c.b;
+    const size_t S = (size_t) b->n_streams, out_stride = c.out_stride;
+    mp3mi_batch::host_io &H = b->hio;
+    mp3mi_batch::host_io::io_slot &io = H.slot[c.hc->slot];
+    const bool mapped = c.hc->rows_dev != NULL;
+    const size_t R = mapped ? (size_t) c.hc->n_rows : S;
+    const size_t row = mapped ? c.hc->out_stride : (c.hc->out_stride < out_stride ? c.hc->out_stride : out_stride);
+    if (mapped) {
+        mp3mi_launch_rows_out(c.hc->rows_dev, c.hc->n_rows, c.out_dev, out_stride, c.out_len_dev, io.out_rows, c.hc->out_stride, io.len_rows, b->lstream);
+        CHK(hipGetLastError());
+    }
+    CHK(hipEventRecord(io.ev_fmt[0], b->lstream));
+    CHK(hipStreamWaitEvent(H.d2h, io.ev_fmt[0], 0));
+    CHK(hipEventRecord(io.t_dn[0], H.d2h));
+    if (mapped)
+        CHK(hipMemcpyAsync(c.hc->out, io.out_rows, c.hc->out_stride * R, hipMemcpyDeviceToHost, H.d2h));
+    else if (c.hc->out_stride == out_stride)
+        CHK(hipMemcpyAsync(c.hc->out, c.out_dev, out_stride * S, hipMemcpyDeviceToHost, H.d2h));
+    else
+        CHK(hipMemcpy2DAsync(c.hc->out, c.hc->out_stride, c.out_dev, out_stride, row, S, hipMemcpyDeviceToHost, H.d2h));
+    CHK(hipMemcpyAsync(c.hc->out_len, mapped ? io.len_rows : c.out_len_dev, sizeof(uint32_t) * R, hipMemcpyDeviceToHost, H.d2h));
+    CHK(hipEventRecord(io.t_dn[1], H.d2h));
+    io.bytes_dn += (double) row * (double) R;
+    CHK(io.out_free.record(H.d2h));
+    return MP3MI_OK;
+}
+
+// ---- loop stream: the serial search and the formatter ----
+static int item_loop(const encode_call &c, int k, const item_view &v)
+{
+    mp3mi_batch *b = c.b;
+    const mp3mi_geom &g = v.g;
+    const size_t r = v.rec0;
+    // (what k_loop needs of its own stream is prepared AHEAD of the wait for the front stream -- in the shadow of the transforms that
+    // run between two k_loop launches, not behind them: the ranking of the part's streams by their cost in the chunk before,
+    // 0.19 ms for 4096 streams, and the two counters' reset)
+    mp3mi_loop_place place = {NULL, NULL, NULL, NULL, NULL, NULL, NULL, 0};
+    if (b->place_order) { // rank the part's streams by their cost in the previous chunk, hand the tables to k_loop
+        mp3mi_launch_rank(b->place_cost + v.s0, b->place_order + v.s0, g.n_streams, b->lstream);
+        CHK(hipGetLastError());
+        CHK(hipMemsetAsync(b->place_zero, 0, sizeof(unsigned) * ((size_t) b->n_streams + 2 * MP3MI_PLACE_KEYS + 2), b->lstream));
+        place.order = b->place_order + v.s0; place.cost = b->place_cost + v.s0; place.taken = b->place_zero;
+        place.simd_slots = b->place_zero + b->n_streams; place.simd_idx = place.simd_slots + MP3MI_PLACE_KEYS;
+        place.ticket = place.simd_idx + MP3MI_PLACE_KEYS; place.scan = place.ticket + 1;
+        place.n_simd = b->n_simd;
+    }
+    CHK(hipMemsetAsync(b->gate_count + 1, 0, sizeof(unsigned), b->lstream));
+    CHK(hipStreamWaitEvent(b->lstream, b->ev_front[v.ev], 0));
+    if (b->hold_calls && k == c.n_items - 1 && !c.waits_for_upload()) { // (a per-slot call on host buffers is not held: the next one would not join, above)
+        // the call's LAST k_loop: held until the next call's first transforms are through (its first item then runs beside
+        // this launch), the host lets go (hold_release), or the bound has passed: 20 ms, more for chunks so long that what the
+        // front stream still holds of this item plus the next call's transforms take longer (0.4 ms per frame of a chunk)
+        b->hold_seq++;
+        const unsigned hold_ticks = 100000u * (unsigned) (g.nf * 4 / 10 > 20 ? (g.nf * 4 / 10 < 200 ? g.nf * 4 / 10 : 200) : 20); // 100 MHz
+        mp3mi_launch_hold(b->hold_flag_d, b->hold_seq, hold_ticks, b->lstream);
+        CHK(hipGetLastError());
+        b->held = true;
+    }
+    CHK(hipEventRecord(c.ts->loop_ev[2 * k], b->lstream));
+    {
+        const int n = g.n_streams;
+        b->gate_total += (unsigned) n; // a wavefront per stream counts itself in
+        b->gate_first = b->gate_total; // the census once this launch is resident: the next item's kernels start behind it
+        mp3mi_launch_loop(b->T, g, b->xr[v.slot] + r * 576, b->psy[v.slot] + r, b->prep[v.slot] + r, b->bits_per_frame + v.s0,
+                          (char *) b->loop_state + v.s0 * c.loop_state_bytes, b->ix + r * 576, b->side + v.s0 * (size_t) g.nf,
+                          b->gate_count, place, b->lstream);
+        CHK(hipGetLastError());
+    }
+    c.ts->kernels += 1;
+    CHK(hipEventRecord(c.ts->loop_ev[2 * k + 1], b->lstream));
+    CHK(b->ev_loop[v.ev].record(b->lstream));
+    mp3mi_launch_format(b->T, g, b->ix + r * 576, b->side + v.s0 * (size_t) g.nf, b->bits_per_frame + v.s0, b->bitrate_index + v.s0,
+                        c.out_dev + v.s0 * c.out_stride, c.out_stride, c.out_len_dev + v.s0, (int32_t *) ((char *) b->loop_state + v.s0 * c.loop_state_bytes),
+                        (int) (c.loop_state_bytes / 4), b->voided, b->lstream);
+    CHK(hipGetLastError());
+    if (c.hc && c.whole_file && k == c.n_items - 1 && download(c) != MP3MI_OK) return MP3MI_ERR_HIP;
+    b->last_nf = g.nf;
+    b->last_slot = v.slot;
+    return MP3MI_OK;
+}
+
+// hand over to the next call: PCM history (front stream: behind the last kernels that read the old one) and,
+// for a streaming call, what became final / what waits (loop stream: behind the last k_format)
+static int hand_over(const encode_call &c)
+{
+    mp3mi_batch *b = c.b;
+    const mp3mi_geom g = call_geom(b, c.cs, 0, c.cs.n_frames < c.cfr ? c.cs.n_frames : c.cfr, 0, b->n_streams); // the whole batch's, of chunk 0
+    mp3mi_launch_hist_save(g, c.pcm_dev, b->pcm_hist, b->stream);
+    CHK(hipGetLastError());
+    if (!c.whole_file) {
+        mp3mi_launch_stream_tail(g, 0, (int32_t *) b->loop_state, (int) (sizeof(mp3mi_loop_state) / 4), b->bits_per_frame, c.out_dev,
+                                 c.out_stride, b->out_base, b->carry, b->carry_len, c.out_len_dev, b->voided, b->lstream);
+        CHK(hipGetLastError());
+        if (c.hc && download(c) != MP3MI_OK) return MP3MI_ERR_HIP;
+    }
+    CHK(hipEventRecord(b->ev_hist, b->stream));
+    CHK(hipStreamWaitEvent(b->lstream, b->ev_hist, 0)); // ev_done below then covers both streams
+    if (c.hc) { // (lstream has just joined the front stream: every kernel that reads the slot's PCM is ahead of this)
+        mp3mi_batch::host_io::io_slot &io = b->hio.slot[c.hc->slot];
+        CHK(io.pcm_free.record(b->lstream));
+        io.pending = true;
+        io.hold_of = b->held ? b->hold_seq : 0u;
+    }
+    if (c.sc) CHK(c.sc->blk->free.record(b->lstream)); // (lstream has joined the front stream: every reader of this copy of the control block is ahead of this)
+    b->slot_base = (b->slot_base + c.nchunks) & 1;
+    if (c.whole_file) b->book.close(); // a whole-file call leaves finished streams behind
+    else b->book.frames_all = c.sc ? 0 : c.cs.fabs0 + c.cs.n_frames; // (a per-slot call: slots_impl keeps the slots' frames)
+    CHK(hipEventRecord(c.ts->ev1, b->lstream));
+    c.ts->pending = true;
+    b->call_no++;
+    CHK(b->ev_done.record(b->lstream));
+    CHK(hipGetLastError());
+    return MP3MI_OK;
+}
+
+static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_samples_dev, int n_frames, uint8_t *out_dev,
+                       size_t out_stride, uint32_t *out_len_dev, bool whole_file, const host_call *hc, const slot_call *sc)
+{
+    if (!b || !pcm_dev || !out_dev || !out_len_dev || n_frames <= 0 || n_frames > b->max_frames) return MP3MI_ERR_ARG;
+    if (out_stride < min_out_stride(b, n_frames, !whole_file)) return MP3MI_ERR_ARG;
+    ON_DEVICE(b);
+    const size_t C = (size_t) b->channels;
+    if (b->debug && !b->sb_dbg) {
+        const size_t ngc = (size_t) b->n_streams * 2 * (size_t) b->chunk_frames * C;
+        CHK(dev_alloc(b, &b->sb_dbg, ngc * 576 * sizeof(double)));
+    }
+    // The call before this one may still be running.  Its kernels and this call's share nothing but the batch's own
+    // buffers, and every one of those is either touched on ONE stream only (in-order: the FFT outputs, the subband
+    // samples, the psy state and the PCM history on the front stream; ix, the side information, the loop state, the
+    // carry and the caller's output on the loop stream) or double-buffered across the two (psy / xr / prep: the slots
+    // go on alternating from call to call, and a slot's writer waits for the k_loop that read it last, ev_loop).  So
+    // this call's feed-forward kernels start at once and fill the chip while the last k_loop of the call before -- 4096
+    // wavefronts, serial, nothing beside them -- runs out: back-to-back calls lose no pipeline fill.
+    // a whole-file call starts every stream afresh; a streaming call continues (the first one after create / reset /
+    // flush / a whole-file call starts afresh too)
+    if (fresh_start(b, whole_file, sc) != MP3MI_OK) return MP3MI_ERR_HIP;
+    // (a per-slot call: every slot has its own frame index, in the control block; k_loop counts the frame of a status from the
+    // call's first, and k_stream_tail places it in the stream)
+    const long fabs0 = sc ? 0 : b->book.frames_all;
+    if (sc) n_samples_dev = sc->dev.n_samples;
+    const bool kept = b->status_kept;
+    b->fresh = false;
+    b->status_kept = false;
+    const int nchunks = (n_frames + b->chunk_frames - 1) / b->chunk_frames;
+    const int cfr = (n_frames + nchunks - 1) / nchunks; // equal chunks: a short last one would run without overlap
+    const size_t pcm_pitch = (size_t) n_frames * 1152 * C; // int16 per stream in the caller's buffer
+    encode_call c = {b, pcm_dev, out_dev, out_stride, out_len_dev, whole_file, hc, sc,
+                     {n_frames, n_samples_dev, fabs0, sc ? sc->dev.fabs : NULL, sc ? sc->dev.ctl : NULL, whole_file},
+                     nchunks, cfr, b->n_parts, nchunks * b->n_parts, pcm_pitch, &b->ts[b->call_no & 1], false,
+                     mp3mi_psy_state_size() * C, sizeof(mp3mi_loop_state)};
+    if (b->place_cost) CHK(hipMemsetAsync(b->place_cost, 0, sizeof(int) * (size_t) b->n_streams, b->lstream)); // first chunk: order = identity
+    if (hc) CHK(b->hio.slot[hc->slot].out_free.wait_on(b->lstream)); // the call two before this one copied out of it
+    CHK(hipMemsetAsync(out_dev, 0, out_stride * (size_t) b->n_streams, b->lstream)); // (behind the formatter of the call before: it may be the same buffer)
+    if (control_block(c, kept) != MP3MI_OK || timing_setup(c) != MP3MI_OK) return MP3MI_ERR_HIP;
     // The unit of scheduling is an ITEM: the frames of one chunk of one PART of the streams (a batch of at most
     // mp3mi_loop_resident() streams -- 4096 on an MI355X -- is one part).  Items go through the pipeline one after the
     // other, chunk by chunk and within a chunk part by part, exactly as the chunks of a one-part batch do: every buffer
@@ -1154,251 +1465,13 @@ static int encode_impl(mp3mi_batch *b, const int16_t *pcm_dev, const int32_t *n_
     // k_loop was cut into parts, with a hand-made assignment of kernels to parts for two and for four parts; with three
     // parts k_psy was still running when the second part started and that part took 65 ms instead of 37:
     // profiles/r03_experiments.txt.  12 288 / 16 384 / 20 000 streams: 5.8 -> ... M frames/s.)
-    const int cfr = (n_frames + nchunks - 1) / nchunks; // equal chunks: a short last one would run without overlap
-    const call_shape cs = {n_frames, n_samples_dev, fabs0, sc ? sc->dev.fabs : NULL, sc ? sc->dev.ctl : NULL, whole_file};
-    struct item_view {
-        mp3mi_geom g;      // of the part: n_streams, n_samples / hist / out_base advanced
-        int slot, ev;      // double-buffer slot of the chunk; index of the (slot, part) events
-        size_t s0, rec0;   // first stream; (granule, channel) records of the chunk before the part
-    };
-    auto view = [&](int k) {
-        item_view v;
-        const int c = k / P, part = k % P;
-        const int f0 = c * cfr;
-        const int nf = (n_frames - f0 < cfr) ? n_frames - f0 : cfr;
-        v.s0 = (size_t) part * (size_t) b->part_streams;
-        const int n = S - (int) v.s0 < b->part_streams ? S - (int) v.s0 : b->part_streams;
-        v.g = call_geom(b, cs, f0, nf, v.s0, n);
-        v.slot = (c + b->slot_base) & 1;
-        v.ev = v.slot * P + part;
-        v.rec0 = v.s0 * 2 * (size_t) nf * (size_t) C;
-        return v;
-    };
-    const size_t pcm_pitch = (size_t) n_frames * 1152 * (size_t) C; // int16 per stream in the caller's buffer
-    if (hc) {
-        // The whole call's PCM, chunk by chunk, in order on the upload stream: a 2-D copy per chunk (every stream's samples of
-        // the chunk's frames; the layout on the device is the caller's).  The chunk's first kernel waits for its copy, so chunk
-        // c + 1 crosses PCIe while chunk c is encoded -- and, with calls issued back to back, the next call's first chunk
-        // while this call's last one is.
-        // A per-slot call with a row map: the caller's rows are dense, one per live slot.  They cross as they are, into the
-        // dense device buffer, and behind each chunk's copy k_rows_in spreads the chunk's columns into the slot rows the
-        // kernels read -- on the upload stream, so a chunk's rows are in place while the chunk before is encoded.  (The map is
-        // in the control block, which the front stream uploads: ev_ctl_up.)
-        mp3mi_batch::host_io &H = b->hio;
-        mp3mi_batch::host_io::io_slot &io = H.slot[hc->slot];
-        const bool mapped = hc->rows_dev != NULL;
-        const size_t R = mapped ? (size_t) hc->n_rows : (size_t) S;
-        CHK(io.pcm_free.wait_on(H.h2d)); // (the kernels of the call two before this one)
-        for (std::vector<hipEvent_t> *v : {&io.t_up, &io.t_dn}) CHK(grow_events(*v, 2 * (size_t) nchunks, 0));
-        for (std::vector<hipEvent_t> *v : {&io.ev_fmt, &io.ev_in}) CHK(grow_events(*v, (size_t) nchunks, hipEventDisableTiming));
-        io.n_chunks = nchunks;
-        io.bytes_up = io.bytes_dn = 0.0;
-        if (mapped) CHK(hipStreamWaitEvent(H.h2d, b->ev_ctl_up, 0));
-        for (int c = 0; c < nchunks; c++) {
-            const int f0 = c * cfr, nf = (n_frames - f0 < cfr) ? n_frames - f0 : cfr;
-            const size_t off = (size_t) f0 * 1152 * (size_t) C, width = (size_t) nf * 1152 * (size_t) C * sizeof(int16_t);
-            int16_t *dst = mapped ? io.pcm_rows : io.pcm;
-            CHK(hipEventRecord(io.t_up[2 * c], H.h2d));
-            CHK(hipMemcpy2DAsync(dst + off, pcm_pitch * sizeof(int16_t), hc->pcm + off, pcm_pitch * sizeof(int16_t), width, R,
-                                 hipMemcpyHostToDevice, H.h2d));
-            CHK(hipEventRecord(io.t_up[2 * c + 1], H.h2d));
-            io.bytes_up += (double) width * (double) R;
-            if (mapped) {
-                mp3mi_launch_rows_in(hc->rows_dev, hc->n_rows, io.pcm_rows, io.pcm, pcm_pitch * sizeof(int16_t), off * sizeof(int16_t), width, H.h2d);
-                CHK(hipGetLastError());
-                CHK(hipEventRecord(io.ev_in[c], H.h2d));
-            }
-        }
+    if (hc && upload_chunks(c) != MP3MI_OK) return MP3MI_ERR_HIP;
+    if (join_or_release(c) != MP3MI_OK) return MP3MI_ERR_HIP;
+    for (int k = 0; k < c.n_items; k++) {
+        const item_view v = c.view(k);
+        if (item_front(c, k, v) != MP3MI_OK || item_loop(c, k, v) != MP3MI_OK) return MP3MI_ERR_HIP;
     }
-    const size_t psy_state_bytes = mp3mi_psy_state_size() * (size_t) C, loop_state_bytes = sizeof(mp3mi_loop_state);
-    // which: 1 the FFTs, 2 k_cw, the partition sums (k_part) and k_psy (passed on as mp3mi_launch_fft's which, whose bit 1 is k_cw)
-    auto stage_x = [&](int k, int which) -> int {
-        const item_view v = view(k);
-        const size_t r = v.rec0;
-        if (hc && (which & 1) && k % P == 0) // the chunk's PCM is up (and in its slots' rows)
-            CHK(hipStreamWaitEvent(b->stream, hc->rows_dev ? b->hio.slot[hc->slot].ev_in[k / P] : b->hio.slot[hc->slot].t_up[2 * (k / P) + 1], 0));
-        mp3mi_launch_fft(b->T, v.g, pcm_dev + v.s0 * pcm_pitch, b->energy_l + r * MP3MI_HBLK_P, b->energy_s + r * 3 * MP3MI_HBLK_S,
-                         b->fft_bins + r * MP3MI_FFT_BINS, b->cw_mid + r * 50, b->hist6 + r * 12, b->stream, which);
-        CHK(hipGetLastError());
-        if (which & 2) {
-            // the k_loop that read this region of the slot last (two chunks ago, maybe in the call before)
-            CHK(b->ev_loop[v.ev].wait_on(b->stream));
-            mp3mi_launch_psy(b->T, v.g, b->energy_l + r * MP3MI_HBLK_P, b->energy_s + r * 3 * MP3MI_HBLK_S, b->cw_mid + r * 50, b->hist6 + r * 12,
-                             b->fft_bins + r * MP3MI_FFT_BINS, b->cw_fix, (char *) b->psy_state + v.s0 * psy_state_bytes, b->part_eb + r * MP3MI_PART_P,
-                             b->part_cb + r * MP3MI_PART_P, b->psy[v.slot] + r, b->stream);
-            CHK(hipGetLastError());
-        }
-        return MP3MI_OK;
-    };
-    // A part larger than the resident wavefronts (on the emulator, whose single CU holds 16) keeps every SIMD full to its end,
-    // so the feed-forward kernels of the next item find no freed slots beside it, only cycles to take: there the item's
-    // stage Y waits for the k_loop before it, and nothing of stage X runs beside that k_loop.
-    auto y_after = [&](const item_view &iv) { return iv.g.n_streams > mp3mi_loop_resident(); };
-    // The call before this one may have left its last k_loop HELD (k_hold): this call's first item then takes the place
-    // "the next item" has inside a call -- its transforms run now, in front of that k_loop, the hold is let go behind them,
-    // and the rest of the item runs beside that k_loop, behind the gate, like every item after it.
-    bool joined = false;
-    {
-        const item_view v0 = view(0);
-        // (A per-slot call on host buffers does not join: its first transforms wait for the tick's PCM to cross PCIe, and a
-        // k_loop held for that long -- a tick is one chunk, so the held launch is the whole tick before -- leaves the chip idle
-        // during the upload: 29.7 ms per 4096 x 32 tick against 16.4 resident.  Let go at once, that k_loop runs beside the upload.)
-        if (b->held && !y_after(v0) && !(hc && sc) && !b->feed_host_call) { // (a feeder's tick on host buffers: the same upload, the same rule)
-            if (stage_x(0, 1) != MP3MI_OK) return MP3MI_ERR_HIP;
-            mp3mi_launch_hold_release(b->hold_flag_d, b->hold_seq, b->stream);
-            CHK(hipGetLastError());
-            b->held = false;
-            joined = true;
-        } else {
-            hold_release(b);
-            if (stage_x(0, 3) != MP3MI_OK) return MP3MI_ERR_HIP;
-        }
-    }
-    // The call's file bytes, behind its last formatter -- a streaming call's behind its k_stream_tail, which settles the lengths
-    // -- as ONE copy: rows of the caller's stride when that is the device
-    // buffer's (mp3mi_batch_out_stride(b, max_frames): a plain copy, which the DMA engines take), a 2-D copy
-    // otherwise.  (A window of columns per chunk -- the bytes that became final with it -- was measured first: the
-    // runtime runs such rectangles as copy KERNELS, 11 ms each beside the encoder's own, and the step lost 56 ms;
-    // profiles/r04_experiments.txt.  With calls issued back to back this copy runs beside the next call's kernels.)
-    // With a row map k_rows_out gathers the listed slots' bytes and lengths into dense rows of the caller's stride first, so
-    // that the copy is plain whatever the stride and moves the live rows only.
-    auto download = [&]() -> int {
-        mp3mi_batch::host_io &H = b->hio;
-        mp3mi_batch::host_io::io_slot &io = H.slot[hc->slot];
-        const bool mapped = hc->rows_dev != NULL;
-        const size_t R = mapped ? (size_t) hc->n_rows : (size_t) S;
-        const size_t row = mapped ? hc->out_stride : (hc->out_stride < out_stride ? hc->out_stride : out_stride);
-        if (mapped) {
-            mp3mi_launch_rows_out(hc->rows_dev, hc->n_rows, out_dev, out_stride, out_len_dev, io.out_rows, hc->out_stride, io.len_rows, b->lstream);
-            CHK(hipGetLastError());
-        }
-        CHK(hipEventRecord(io.ev_fmt[0], b->lstream));
-        CHK(hipStreamWaitEvent(H.d2h, io.ev_fmt[0], 0));
-        CHK(hipEventRecord(io.t_dn[0], H.d2h));
-        if (mapped)
-            CHK(hipMemcpyAsync(hc->out, io.out_rows, hc->out_stride * R, hipMemcpyDeviceToHost, H.d2h));
-        else if (hc->out_stride == out_stride)
-            CHK(hipMemcpyAsync(hc->out, out_dev, out_stride * (size_t) S, hipMemcpyDeviceToHost, H.d2h));
-        else
-            CHK(hipMemcpy2DAsync(hc->out, hc->out_stride, out_dev, out_stride, row, (size_t) S, hipMemcpyDeviceToHost, H.d2h));
-        CHK(hipMemcpyAsync(hc->out_len, mapped ? io.len_rows : out_len_dev, sizeof(uint32_t) * R, hipMemcpyDeviceToHost, H.d2h));
-        CHK(hipEventRecord(io.t_dn[1], H.d2h));
-        io.bytes_dn += (double) row * (double) R;
-        CHK(io.out_free.record(H.d2h));
-        return MP3MI_OK;
-    };
-    for (int k = 0; k < n_items; k++) {
-        const item_view v = view(k);
-        const mp3mi_geom &g = v.g;
-        const size_t r = v.rec0;
-        const bool follows = k >= 1 || joined; // a k_loop runs (or is about to) that this item's kernels go beside
-        // what of stage X runs beside k_loop: all but the FFTs -- k_cw, k_part, k_psy are small in registers and LDS, the
-        // item's FFTs were done before that launch started, and the region k_psy writes was read last by the launch before
-        // it: 238.2 vs 247.2 ms per 4096 x 383 step with them between the launches.
-        const bool beside = !y_after(v);
-        // ---- front stream: everything that does not depend on the bit reservoir ----
-        if (k >= 1 && !beside) { // (the k_loop before this item's: view(k - 1))
-            const item_view pv = view(k - 1);
-            CHK(b->ev_loop[pv.ev].wait_on(b->stream));
-        } else if (follows) // this item's kernels run behind k_loop(k - 1), once that is resident (<= 300 us)
-            mp3mi_launch_gate(b->gate_count, b->gate_first - 16u, 30000u, b->stream);
-        if (beside && follows && stage_x(k, 2) != MP3MI_OK) return MP3MI_ERR_HIP;
-        mp3mi_launch_filter(b->T, g, pcm_dev + v.s0 * pcm_pitch, b->sbs + v.s0 * (size_t) (g.n_gran + 1) * (size_t) C * 576,
-                            b->debug ? b->sb_dbg + r * 576 : NULL, b->stream);
-        CHK(hipGetLastError());
-        // k_mdct's tail also computes the loop's stateless head and lists the records it could not decide; k_prep works
-        // through the list (MP3MI_TEST_PREP_EXACT: through every record, the reference's way)
-        CHK(hipMemsetAsync(&b->prep_fix->count, 0, sizeof(unsigned), b->stream));
-        mp3mi_launch_mdct(b->T, g, b->psy[v.slot] + r, b->sbs + v.s0 * (size_t) (g.n_gran + 1) * (size_t) C * 576, b->xr[v.slot] + r * 576,
-                          b->prep[v.slot] + r, b->prep_fix, b->stream);
-        CHK(hipGetLastError());
-        mp3mi_launch_prep(b->T, g, b->xr[v.slot] + r * 576, b->psy[v.slot] + r, b->prep[v.slot] + r, b->prep_exact ? NULL : b->prep_fix, b->prep_exact, b->stream);
-        CHK(hipGetLastError());
-        if (k + 1 < n_items) {
-            // (The next item's transforms take whole CUs' LDS: they run BETWEEN two k_loop launches.  Nothing but the queue behind
-            // a busy chip sees to that -- this item's kernels take longer than the k_loop they run beside -- and an explicit wait
-            // for that k_loop's end costs 1.4 ms per step, because the transforms then no longer slip in as its last CUs drain:
-            // profiles/r05_experiments.txt, E7.)
-            if (stage_x(k + 1, y_after(view(k + 1)) ? 3 : 1) != MP3MI_OK) return MP3MI_ERR_HIP;
-        }
-        CHK(hipEventRecord(b->ev_front[v.ev], b->stream));
-        // ---- loop stream: the serial search and the formatter ----
-        // (what k_loop needs of its own stream is prepared AHEAD of the wait for the front stream -- in the shadow of the transforms that
-        // run between two k_loop launches, not behind them: the ranking of the part's streams by their cost in the chunk before,
-        // 0.19 ms for 4096 streams, and the two counters' reset)
-        mp3mi_loop_place place = {NULL, NULL, NULL, NULL, NULL, NULL, NULL, 0};
-        if (b->place_order) { // rank the part's streams by their cost in the previous chunk, hand the tables to k_loop
-            mp3mi_launch_rank(b->place_cost + v.s0, b->place_order + v.s0, g.n_streams, b->lstream);
-            CHK(hipGetLastError());
-            CHK(hipMemsetAsync(b->place_zero, 0, sizeof(unsigned) * ((size_t) S + 2 * MP3MI_PLACE_KEYS + 2), b->lstream));
-            place.order = b->place_order + v.s0; place.cost = b->place_cost + v.s0; place.taken = b->place_zero;
-            place.simd_slots = b->place_zero + S; place.simd_idx = place.simd_slots + MP3MI_PLACE_KEYS;
-            place.ticket = place.simd_idx + MP3MI_PLACE_KEYS; place.scan = place.ticket + 1;
-            place.n_simd = b->n_simd;
-        }
-        CHK(hipMemsetAsync(b->gate_count + 1, 0, sizeof(unsigned), b->lstream));
-        CHK(hipStreamWaitEvent(b->lstream, b->ev_front[v.ev], 0));
-        if (b->hold_calls && k == n_items - 1 && !(hc && sc) && !b->feed_host_call) { // (a per-slot call on host buffers is not held: the next one would not join, above)
-            // the call's LAST k_loop: held until the next call's first transforms are through (its first item then runs beside
-            // this launch), the host lets go (hold_release), or the bound has passed: 20 ms, more for chunks so long that what the
-            // front stream still holds of this item plus the next call's transforms take longer (0.4 ms per frame of a chunk)
-            b->hold_seq++;
-            const unsigned hold_ticks = 100000u * (unsigned) (g.nf * 4 / 10 > 20 ? (g.nf * 4 / 10 < 200 ? g.nf * 4 / 10 : 200) : 20); // 100 MHz
-            mp3mi_launch_hold(b->hold_flag_d, b->hold_seq, hold_ticks, b->lstream);
-            CHK(hipGetLastError());
-            b->held = true;
-        }
-        CHK(hipEventRecord(ts.loop_ev[2 * k], b->lstream));
-        {
-            const int n = g.n_streams;
-            b->gate_total += (unsigned) n; // a wavefront per stream counts itself in
-            b->gate_first = b->gate_total; // the census once this launch is resident: the next item's kernels start behind it
-            mp3mi_launch_loop(b->T, g, b->xr[v.slot] + r * 576, b->psy[v.slot] + r, b->prep[v.slot] + r, b->bits_per_frame + v.s0,
-                              (char *) b->loop_state + v.s0 * loop_state_bytes, b->ix + r * 576, b->side + v.s0 * (size_t) g.nf,
-                              b->gate_count, place, b->lstream);
-            CHK(hipGetLastError());
-        }
-        ts.kernels += 1;
-        CHK(hipEventRecord(ts.loop_ev[2 * k + 1], b->lstream));
-        CHK(b->ev_loop[v.ev].record(b->lstream));
-        mp3mi_launch_format(b->T, g, b->ix + r * 576, b->side + v.s0 * (size_t) g.nf, b->bits_per_frame + v.s0, b->bitrate_index + v.s0,
-                            out_dev + v.s0 * out_stride, out_stride, out_len_dev + v.s0, (int32_t *) ((char *) b->loop_state + v.s0 * loop_state_bytes),
-                            (int) (loop_state_bytes / 4), b->voided, b->lstream);
-        CHK(hipGetLastError());
-        if (hc && whole_file && k == n_items - 1 && download() != MP3MI_OK) return MP3MI_ERR_HIP;
-        b->last_nf = g.nf;
-        b->last_slot = v.slot;
-    }
-    {   // hand over to the next call: PCM history (front stream: behind the last kernels that read the old one) and,
-        // for a streaming call, what became final / what waits (loop stream: behind the last k_format)
-        const mp3mi_geom g = call_geom(b, cs, 0, n_frames < cfr ? n_frames : cfr, 0, S); // the whole batch's, of chunk 0
-        mp3mi_launch_hist_save(g, pcm_dev, b->pcm_hist, b->stream);
-        CHK(hipGetLastError());
-        if (!whole_file) {
-            mp3mi_launch_stream_tail(g, 0, (int32_t *) b->loop_state, (int) (sizeof(mp3mi_loop_state) / 4), b->bits_per_frame, out_dev,
-                                     out_stride, b->out_base, b->carry, b->carry_len, out_len_dev, b->voided, b->lstream);
-            CHK(hipGetLastError());
-            if (hc && download() != MP3MI_OK) return MP3MI_ERR_HIP;
-        }
-        CHK(hipEventRecord(b->ev_hist, b->stream));
-        CHK(hipStreamWaitEvent(b->lstream, b->ev_hist, 0)); // ev_done below then covers both streams
-    }
-    if (hc) { // (lstream has just joined the front stream: every kernel that reads the slot's PCM is ahead of this)
-        mp3mi_batch::host_io::io_slot &io = b->hio.slot[hc->slot];
-        CHK(io.pcm_free.record(b->lstream));
-        io.pending = true;
-        io.hold_of = b->held ? b->hold_seq : 0u;
-    }
-    if (sc) CHK(sc->blk->free.record(b->lstream)); // (lstream has joined the front stream: every reader of this copy of the control block is ahead of this)
-    b->slot_base = (b->slot_base + nchunks) & 1;
-    if (whole_file) b->book.close(); // a whole-file call leaves finished streams behind
-    else b->book.frames_all = sc ? 0 : fabs0 + n_frames; // (a per-slot call: slots_impl keeps the slots' frames)
-    CHK(hipEventRecord(ts.ev1, b->lstream));
-    ts.pending = true;
-    b->call_no++;
-    CHK(b->ev_done.record(b->lstream));
-    CHK(hipGetLastError());
-    return MP3MI_OK;
+    return hand_over(c);
 }
 
 extern "C" int mp3mi_batch_sync(mp3mi_batch *b)

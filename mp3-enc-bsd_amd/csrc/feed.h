@@ -208,6 +208,47 @@ extern "C" int mp3mi_feed_lanes(const mp3mi_feed *f, int32_t *pending_host, int6
     return n;
 }
 
+// Steps 5 and 6 of a tick, of either feeder: the streams that do not encode leave their slots, the parked lanes that encode enter
+// free ones.  The SLOT lists go to the export and the import, the LANE lists -- park_dev / resume_dev: their device copies, in the
+// tick's upload block -- to the scatter and the gather between the dense blocks and the records per lane (mp3mi_feed_tick: a lane
+// is its slot, and the lists are the same).  after: the lanes behind the tick, which take the leaving streams' tickets.
+static int feed_park_resume(mp3mi_feed *f, const std::vector<int32_t> &park_slots, const std::vector<int32_t> &park_lanes, const int32_t *park_dev,
+                            const std::vector<int32_t> &resume_slots, const std::vector<int32_t> &resume_lanes, const int32_t *resume_dev,
+                            std::vector<mp3mi_feed::lane> &after)
+{
+    mp3mi_batch *b = f->b;
+    // the one-region tables of the records per lane: region bytes = the part's size, so lane l's part lies at base + l * bytes
+    mp3mi_park_table tf, tl;
+    memset(&tf, 0, sizeof(tf));
+    memset(&tl, 0, sizeof(tl));
+    tf.r[0] = {f->rec_front, (uint32_t) f->front_bytes, 0u};
+    tl.r[0] = {f->rec_loop, (uint32_t) (f->state_bytes - f->front_bytes), (uint32_t) f->front_bytes};
+    tf.n = f->front_bytes ? 1 : 0;
+    tl.n = f->state_bytes > f->front_bytes ? 1 : 0;
+    std::vector<mp3mi_slot_ticket> tk(park_lanes.size() > resume_lanes.size() ? park_lanes.size() : resume_lanes.size());
+    int rc = MP3MI_OK;
+    // ---- 5. the streams that do not encode leave their slots: the SLOT list to the export, the LANE list to the scatter ----
+    if (!park_slots.empty()) {
+        rc = mp3mi_batch_slots_export(b, (int) park_slots.size(), park_slots.data(), 1, f->park_block, f->state_bytes, tk.data());
+        if (rc == MP3MI_OK) {
+            for (size_t i = 0; i < park_lanes.size(); i++) after[park_lanes[i]].ticket = tk[i];
+            mp3mi_launch_slot_park(park_dev, (int) park_lanes.size(), tf, f->park_block, f->state_bytes, 0, b->stream);
+            mp3mi_launch_slot_park(park_dev, (int) park_lanes.size(), tl, f->park_block, f->state_bytes, 0, b->lstream);
+            if (hipGetLastError() != hipSuccess) rc = MP3MI_ERR_HIP;
+        }
+    }
+    // ---- 6. the parked lanes that encode enter the free slots -- slots this tick's export vacated among them ----
+    if (rc == MP3MI_OK && !resume_slots.empty()) {
+        for (size_t i = 0; i < resume_lanes.size(); i++) tk[i] = f->lanes[resume_lanes[i]].ticket;
+        mp3mi_launch_slot_park(resume_dev, (int) resume_lanes.size(), tf, f->resume_block, f->state_bytes, 1, b->stream);
+        mp3mi_launch_slot_park(resume_dev, (int) resume_lanes.size(), tl, f->resume_block, f->state_bytes, 1, b->lstream);
+        if (hipGetLastError() != hipSuccess) rc = MP3MI_ERR_HIP;
+        if (rc == MP3MI_OK)
+            rc = mp3mi_batch_slots_import(b, (int) resume_slots.size(), resume_slots.data(), f->resume_block, f->state_bytes, tk.data());
+    }
+    return rc;
+}
+
 extern "C" int mp3mi_feed_tick(mp3mi_feed *f, const int16_t *pcm_dev, size_t pcm_pitch, const uint8_t *ctl_host, const int32_t *n_push_host,
                                const int32_t *kbps_host, uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev)
 {
@@ -294,35 +335,9 @@ extern "C" int mp3mi_feed_tick(mp3mi_feed *f, const int16_t *pcm_dev, size_t pcm
         CHK(hipEventRecord(f->ev_up, b->stream));
         if (lists) CHK(hipStreamWaitEvent(b->lstream, f->ev_up, 0));
     }
-    // the one-region tables of the records per lane: region bytes = the part's size, so lane s's part lies at base + s * bytes
-    mp3mi_park_table tf, tl;
-    memset(&tf, 0, sizeof(tf));
-    memset(&tl, 0, sizeof(tl));
-    tf.r[0] = {f->rec_front, (uint32_t) f->front_bytes, 0u};
-    tl.r[0] = {f->rec_loop, (uint32_t) (f->state_bytes - f->front_bytes), (uint32_t) f->front_bytes};
-    tf.n = f->front_bytes ? 1 : 0;
-    tl.n = f->state_bytes > f->front_bytes ? 1 : 0;
-    std::vector<mp3mi_slot_ticket> tk(park.size() > resume.size() ? park.size() : resume.size());
-    int rc = MP3MI_OK;
     b->feed_call = true;
-    // ---- 5. the lanes that sit out leave their slots ----
-    if (!park.empty()) {
-        rc = mp3mi_batch_slots_export(b, (int) park.size(), park.data(), 1, f->park_block, f->state_bytes, tk.data());
-        if (rc == MP3MI_OK) {
-            for (size_t i = 0; i < park.size(); i++) nl[park[i]].ticket = tk[i];
-            mp3mi_launch_slot_park(park_dev, (int) park.size(), tf, f->park_block, f->state_bytes, 0, b->stream);
-            mp3mi_launch_slot_park(park_dev, (int) park.size(), tl, f->park_block, f->state_bytes, 0, b->lstream);
-            if (hipGetLastError() != hipSuccess) rc = MP3MI_ERR_HIP;
-        }
-    }
-    // ---- 6. the parked lanes that are ready come back ----
-    if (rc == MP3MI_OK && !resume.empty()) {
-        for (size_t i = 0; i < resume.size(); i++) tk[i] = f->lanes[resume[i]].ticket;
-        mp3mi_launch_slot_park(resume_dev, (int) resume.size(), tf, f->resume_block, f->state_bytes, 1, b->stream);
-        mp3mi_launch_slot_park(resume_dev, (int) resume.size(), tl, f->resume_block, f->state_bytes, 1, b->lstream);
-        if (hipGetLastError() != hipSuccess) rc = MP3MI_ERR_HIP;
-        if (rc == MP3MI_OK) rc = mp3mi_batch_slots_import(b, (int) resume.size(), resume.data(), f->resume_block, f->state_bytes, tk.data());
-    }
+    // ---- 5. the lanes that sit out leave their slots; 6. the parked lanes that are ready come back ----
+    int rc = feed_park_resume(f, park, park, park_dev, resume, resume, resume_dev, nl);
     // ---- 7. one per-slot call on the feeder's rows: the ready lanes; every other slot is closed ----
     if (rc == MP3MI_OK && any_ready)
         rc = mp3mi_batch_encode_slots_kbps(b, f->rows, f->tick_frames, ctl.data(), ns.data(), kb.data(), out_dev, out_stride, out_len_dev);
@@ -661,36 +676,9 @@ static int feed_tick_lanes_impl(mp3mi_feed *f, int n_rows, const int32_t *row_la
         FCHK(hipEventRecord(f->ev_up, b->stream));
         if (lists) FCHK(hipStreamWaitEvent(b->lstream, f->ev_up, 0));
     }
-    // the one-region tables of the records per lane: lane l's part lies at base + l * bytes
-    mp3mi_park_table tf, tl;
-    memset(&tf, 0, sizeof(tf));
-    memset(&tl, 0, sizeof(tl));
-    tf.r[0] = {f->rec_front, (uint32_t) f->front_bytes, 0u};
-    tl.r[0] = {f->rec_loop, (uint32_t) (f->state_bytes - f->front_bytes), (uint32_t) f->front_bytes};
-    tf.n = f->front_bytes ? 1 : 0;
-    tl.n = f->state_bytes > f->front_bytes ? 1 : 0;
-    std::vector<mp3mi_slot_ticket> tk(park_lanes.size() > resume_lanes.size() ? park_lanes.size() : resume_lanes.size());
-    int rc = MP3MI_OK;
     b->feed_call = true;
-    // ---- 5. the streams that do not encode leave their slots: the SLOT list to the export, the LANE list to the scatter ----
-    if (!park_slots.empty()) {
-        rc = mp3mi_batch_slots_export(b, (int) park_slots.size(), park_slots.data(), 1, f->park_block, f->state_bytes, tk.data());
-        if (rc == MP3MI_OK) {
-            for (size_t i = 0; i < park_lanes.size(); i++) f->lanes[park_lanes[i]].ticket = tk[i];
-            mp3mi_launch_slot_park(park_dev, (int) park_lanes.size(), tf, f->park_block, f->state_bytes, 0, b->stream);
-            mp3mi_launch_slot_park(park_dev, (int) park_lanes.size(), tl, f->park_block, f->state_bytes, 0, b->lstream);
-            if (hipGetLastError() != hipSuccess) rc = MP3MI_ERR_HIP;
-        }
-    }
-    // ---- 6. the parked lanes that encode enter the free slots -- slots this tick's export vacated among them (above) ----
-    if (rc == MP3MI_OK && !resume_slots.empty()) {
-        for (size_t i = 0; i < resume_lanes.size(); i++) tk[i] = f->lanes[resume_lanes[i]].ticket;
-        mp3mi_launch_slot_park(resume_dev, (int) resume_lanes.size(), tf, f->resume_block, f->state_bytes, 1, b->stream);
-        mp3mi_launch_slot_park(resume_dev, (int) resume_lanes.size(), tl, f->resume_block, f->state_bytes, 1, b->lstream);
-        if (hipGetLastError() != hipSuccess) rc = MP3MI_ERR_HIP;
-        if (rc == MP3MI_OK)
-            rc = mp3mi_batch_slots_import(b, (int) resume_slots.size(), resume_slots.data(), f->resume_block, f->state_bytes, tk.data());
-    }
+    // ---- 5. the streams that do not encode leave their slots; 6. the parked lanes that encode enter the free slots ----
+    int rc = feed_park_resume(f, park_slots, park_lanes, park_dev, resume_slots, resume_lanes, resume_dev, f->lanes);
     // ---- 7. one per-slot call on the feeder's rows: the chosen lanes' slots; every other slot is closed ----
     b->feed_host_call = hc != NULL;
     if (rc == MP3MI_OK && any_ready)
