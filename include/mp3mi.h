@@ -383,8 +383,8 @@ int mp3mi_batch_slots_import(mp3mi_batch *b, int n, const int32_t *slots_host, c
  *   mp3mi_feed_host_io_stats  over the host ticks so far, waiting for them: h2d_bytes, exactly sum(n_push) * channels * 2; d2h_bytes,
  *                        exactly n_out * (out_stride + 4) per tick; the copies' event times; calls, the ticks.
  * A feeder that never makes a host tick creates no stream, no event and no buffer for them.
- * Not yet: Layers I and II (mp3mi_l12.h), a status query per lane, and a direct path for a parked record between a lane and a slot
- * (the records of a tick pass through a dense block). */
+ * Not yet: a status query per lane, and, for Layer III, a direct path for a parked record between a lane and a slot (the records of a
+ * tick pass through a dense block).  Layers I and II have a feeder of their own, with that path: mp3mi_l12_feed_* (mp3mi_l12.h). */
 typedef struct mp3mi_feed mp3mi_feed;
 int mp3mi_feed_create(mp3mi_feed **out, mp3mi_batch *b, int tick_frames, int max_push);
 void mp3mi_feed_destroy(mp3mi_feed *f);

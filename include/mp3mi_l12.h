@@ -184,6 +184,102 @@ int mp3mi_l12_batch_slots_export(mp3mi_l12_batch *b, int n, const int32_t *slots
 int mp3mi_l12_batch_slots_import(mp3mi_l12_batch *b, int n, const int32_t *slots_host, const void *state_dev, size_t state_stride,
                                  const mp3mi_l12_slot_ticket *tickets_host);
 
+/* The feeder: any number of samples per call.  A per-slot call wants a full call of samples from every open slot; real streams
+ * arrive in packets of 160 or 960 samples, in bursts, in whatever a decoder upstream hands over.  A feeder has n_lanes LANES in front
+ * of the batch's n_streams slots, in any relation (fewer, as many, more).  A lane keeps a FIFO of samples ON THE DEVICE; the rows of
+ * every tick are cut there (k12_feed, csrc/k_format.hip); a slot is lent to a lane for the ticks in which it encodes.  It touches no
+ * encoding kernel: a tick ends in one mp3mi_l12_batch_encode_slots_kbps call on rows the feeder owns.  A frame is 384 (Layer I) or
+ * 1152 (Layer II) samples per channel; a TICK is tick_frames of them.
+ *   mp3mi_l12_feed_create    a feeder for batch b -- on which no stream is open, and which has no feeder yet -- that encodes tick_frames
+ *                        frames (1 .. the batch's max_frames) per encoding lane and tick and takes up to max_push (>= 1) samples per
+ *                        lane and call.  n_lanes >= 1; max_rows in 1 .. n_lanes: the most lanes that may push in one tick (it sizes
+ *                        the upload blocks); ring_samples: the pending samples per channel a lane's FIFO holds, at least tick_frames *
+ *                        frame + max_push, 0: exactly that.  A lane that is ready but waits for a slot keeps taking pushes until its
+ *                        FIFO is full, so a server sizes it for the wait it accepts.
+ *   mp3mi_l12_feed_capacity  the pending samples per channel a lane's FIFO holds (ring_samples, or the least).  A lane's ring on the
+ *                        device is 1792 samples per channel longer: the samples a stream has encoded last stay there, and they are all
+ *                        a stream of these layers carries from call to call -- so a stream that sits out a tick leaves its slot
+ *                        without a copy, and comes back to any slot by one copy out of its own ring.
+ *   mp3mi_l12_feed_n_lanes   the lanes; mp3mi_l12_feed_lanes takes arrays of that many entries.
+ *   mp3mi_l12_feed_tick      the pushes come as ROWS: row r is lane row_lane_host[r] (strictly increasing, each in 0 .. n_lanes-1;
+ *                        n_rows in 0 .. max_rows), its samples row r of pcm_dev, device, int16 [n_rows][pcm_pitch][channels] in WAV
+ *                        order, pcm_pitch >= max_push: the lane brings the row's first n_push_host[r] samples per channel (0 ..
+ *                        max_push).  ctl_host, n_push_host and kbps_host are HOST arrays indexed by row.  A lane that no row names
+ *                        pushes nothing and has ctl 0; it may encode all the same (it drains, or gets a slot at last).  With n_rows
+ *                        == 0 the four row arrays and pcm_dev may be NULL; with n_rows > 0 none of them may.  All host arrays are
+ *                        copied before the call returns.
+ *     ctl_host[r]   MP3MI_SLOT_START: a new stream begins in the lane with this call's first pushed sample, at kbps_host[r]: 0, or a
+ *                   bitrate of the batch's layer that is not above the batch's ceiling (the rules of
+ *                   mp3mi_l12_batch_encode_slots_kbps, checked here).  A stream open in the lane is abandoned with its pending
+ *                   samples, as mp3mi_l12_batch_encode_slots abandons one.  The batch sees the START in the first tick in which the
+ *                   lane encodes.
+ *                   MP3MI_SLOT_END: this call's samples are the stream's last.  From here the lane DRAINS: tick_frames frames per
+ *                   tick in which it encodes while more than tick_frames * frame samples are pending; in the first with that many or
+ *                   fewer (0 too) the batch gets its END with exactly that count, and the lane closes.  START | END with few samples
+ *                   is a one-call file.
+ *     kbps_host[r]  of a row without START: 0, or the bitrate of the stream open in the lane once that is known (below).
+ *     Ready.  A lane is READY when its pending samples and the pushed ones make a tick, or when it is ending (draining, with a tick or
+ *     less pending).  A lane that is not ready delivers nothing; its samples stay pending, nothing of it is lost, and a stream it
+ *     holds in the batch leaves its slot (it is parked) until the lane encodes again.
+ *     Who encodes.  If no more than n_streams lanes are ready, all encode.  Otherwise the n_streams lanes encode whose current
+ *     unbroken spell of being ready began in the earliest tick, ties going to the lower lane; a lane that encodes and is still ready
+ *     begins a new spell in the next tick.  So no ready lane encodes twice while another that was ready before it has not encoded
+ *     once.  A ready lane that gets no slot keeps its samples, delivers nothing, is parked if its stream is in a slot, and shows bit
+ *     3 in mp3mi_l12_feed_lanes' flags until the tick in which it encodes.
+ *     Where.  A chosen lane whose stream is in a slot keeps the slot.  Every other stream in a slot leaves it.  The other chosen
+ *     lanes take the free slots -- those vacated in this very tick among them --, the lowest free slot going to the lowest lane: a
+ *     parked stream is resumed there, a stream the batch has not seen STARTs there.  A START at kbps 0 means the create-time bitrate
+ *     of the slot in which the stream first encodes; until then only kbps 0 may be passed with the lane's pushes.
+ *     Output is by SLOT, as mp3mi_l12_batch_encode_slots writes it: out_dev [n_streams][out_stride], out_stride >=
+ *     mp3mi_l12_batch_out_stride(b, tick_frames), and out_len_dev [n_streams].  slot_lane_host [n_streams] is filled before the call
+ *     returns (host bookkeeping, no device wait): entry i is the lane that encodes in slot i in this tick, or -1, and out_len_dev[i]
+ *     is 0 where it is -1.  A tick in which nothing encodes launches no encoding kernel and zeroes out_len_dev in stream order.
+ *     The bytes a LANE delivers from a stream's START through the tick that closes it, gathered slot by slot through slot_lane_host
+ *     and concatenated, are byte for byte what mp3mi_l12_batch_encode gives for the stream's samples as one stream of a ragged
+ *     whole-file call at its bitrate -- however the samples were cut into pushes, however often the stream sat out a tick, and in
+ *     whichever slots it encoded.
+ *     MP3MI_ERR_ARG, with nothing enqueued and feeder and batch unchanged -- the check runs over all rows first --: n_rows outside
+ *     0 .. max_rows; a row map out of order or out of range; a NULL row array or pcm_dev with n_rows > 0; a NULL out_dev,
+ *     out_len_dev or slot_lane_host; unknown ctl bits; a push or an END on a closed lane without START; START, END or a push on a
+ *     draining lane; n_push outside 0 .. max_push; pending + push above mp3mi_l12_feed_capacity (a waiting lane whose FIFO is full);
+ *     pcm_pitch < max_push; out_stride too small; a kbps that breaks the rules above.
+ *     The call waits for nothing but the fence of its own upload block (the tick four before, as a rule long through) and what the
+ *     per-slot call itself waits for (its control block, two turns before): ticks may be issued back to back.
+ *   mp3mi_l12_feed_lanes     host bookkeeping only, no wait: per lane the pending samples, the frames encoded so far (-1: closed) and
+ *                        flags -- bit 0 parked, bit 1 draining, bit 2 started but not yet in the batch, bit 3 ready and waiting for
+ *                        a slot.  Returns the number of lanes that are not closed.
+ *   mp3mi_l12_feed_destroy   resets the batch (streams in lanes are abandoned) and detaches; mp3mi_l12_batch_destroy on a batch with
+ *                        a feeder attached frees the feeder with it (do not destroy it afterwards).
+ * While a feeder is attached the batch's streams are the feeder's: mp3mi_l12_batch_encode, _encode_next, _encode_slots(_kbps), _flush,
+ * _reset, _slots_export, _slots_import, _set_mode, _set_error_protection and _set_header return MP3MI_ERR_ARG; mp3mi_l12_batch_sync,
+ * _slot_frames, _slot_kbps and the timing accessors work as ever (a parked lane's slot reads as closed).  A batch that never gets a
+ * feeder allocates, copies and launches exactly what it did without.  Not here: ticks on host buffers, a status query per lane. */
+typedef struct mp3mi_l12_feed mp3mi_l12_feed;
+int mp3mi_l12_feed_create(mp3mi_l12_feed **out, mp3mi_l12_batch *b, int n_lanes, int max_rows, int tick_frames, int max_push,
+                          int ring_samples);
+void mp3mi_l12_feed_destroy(mp3mi_l12_feed *f);
+size_t mp3mi_l12_feed_capacity(const mp3mi_l12_feed *f);
+int mp3mi_l12_feed_n_lanes(const mp3mi_l12_feed *f);
+int mp3mi_l12_feed_tick(mp3mi_l12_feed *f, int n_rows, const int32_t *row_lane_host, const int16_t *pcm_dev, size_t pcm_pitch,
+                        const uint8_t *ctl_host, const int32_t *n_push_host, const int32_t *kbps_host, uint8_t *out_dev, size_t out_stride,
+                        uint32_t *out_len_dev, int32_t *slot_lane_host);
+int mp3mi_l12_feed_lanes(const mp3mi_l12_feed *f, int32_t *pending_host, int64_t *frames_host, uint8_t *flags_host);
+
+/* Self-test hook: k12_feed alone, as mp3mi_l12_feed_tick launches it (csrc/format_debug.cpp), on n_lanes rings [ring_pitch][channels]
+ * of `cap` samples, n_push_rows push rows [push_pitch][channels], n_slots dense rows [row_pitch][channels] of row_samples samples and
+ * the slots' two history rows, hist [n_slots][1792][channels] and fb_hist [n_slots][1056][channels]; pitches in samples per channel,
+ * those of rings and rows multiples of 16 bytes.  desc: n_active descriptors of eight uint32 {head, pending, n_push, take, lane,
+ * push_row, slot, resume}, resume 0 or 0x80000000 | n_hist.  The first `take` samples of ring[head .. head + pending) ++ push[0 ..
+ * n_push) go to row `slot`; all n_push samples are appended to the ring at (head + pending) % cap; a resuming descriptor also writes
+ * the slot's history rows: the n_hist samples before head with zeros in front, and the last 1056 of the same.  The arrays go up and
+ * come back whole.  MP3MI_ERR_ARG, and nothing is launched, where a descriptor breaks a rule the tick keeps: head < cap; 1792 +
+ * pending + n_push <= cap; take <= pending + n_push and <= row_samples; n_push <= push_pitch; lane, push_row and slot inside their
+ * arrays; n_hist <= 1792 and no other bit in word 7; no lane twice, no push row of a pushing descriptor twice, no slot of a taking or
+ * resuming descriptor twice. */
+int mp3mi_debug_l12_feed(int channels, int n_active, int n_lanes, int n_push_rows, int n_slots, int cap, int row_samples,
+                         const uint32_t *desc, int16_t *ring, size_t ring_pitch, int16_t *push, size_t push_pitch, int16_t *rows,
+                         size_t row_pitch, int16_t *hist, int16_t *fb_hist);
+
 /* Two-tier decisions (mp3mi.h, MP3MI_TEST_PHASE_EXACT | _PSY_EXACT | _CW_EXACT): force the exact tier; bytes must not change */
 int mp3mi_l12_batch_set_test_flags(mp3mi_l12_batch *b, unsigned flags);
 

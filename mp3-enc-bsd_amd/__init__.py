@@ -166,6 +166,15 @@ def lib():
                                                    ctypes.c_void_p]
         L.mp3mi_l12_batch_slots_import.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         L.mp3mi_l12_batch_total_timing.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]
+        L.mp3mi_l12_feed_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p] + [ctypes.c_int] * 5
+        L.mp3mi_l12_feed_destroy.argtypes = [ctypes.c_void_p]
+        L.mp3mi_l12_feed_destroy.restype = None
+        L.mp3mi_l12_feed_capacity.restype = ctypes.c_size_t
+        L.mp3mi_l12_feed_capacity.argtypes = [ctypes.c_void_p]
+        L.mp3mi_l12_feed_n_lanes.argtypes = [ctypes.c_void_p]
+        L.mp3mi_l12_feed_tick.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+        L.mp3mi_l12_feed_lanes.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.mp3mi_l12_batch_kernel_timing.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.mp3mi_version.restype = ctypes.c_char_p
         L.mp3mi_source_hash.restype = ctypes.c_char_p
@@ -732,6 +741,13 @@ class BatchL12:
         self._check(self.L.mp3mi_l12_batch_slots_import(self.h, len(sl), sl.ctypes.data, state.data_ptr(), state.stride(0), ctypes.addressof(arr)),
                     "mp3mi_l12_batch_slots_import")
 
+    def feeder(self, tick_frames, max_push, lanes=None, max_rows=None, ring_samples=0):
+        """A feeder in front of this batch (mp3mi_l12_feed_create): lanes that take any number of samples per call (up to max_push)
+        and encode tick_frames frames per tick in the slots the feeder lends them.  lanes None: one lane per slot; max_rows: the most
+        lanes that push in one tick (None: all); ring_samples: the pending samples a lane's FIFO holds (0: tick_frames * frame +
+        max_push).  While it is attached the batch's streams are the feeder's.  Returns the FeedL12."""
+        return FeedL12(self, tick_frames, max_push, lanes, max_rows, ring_samples)
+
     def sync(self):
         self._check(self.L.mp3mi_l12_batch_sync(self.h), "mp3mi_l12_batch_sync")
 
@@ -749,8 +765,91 @@ class BatchL12:
 
     def close(self):
         if self.h:
+            feed = getattr(self, "_feed", None)
+            if feed is not None:
+                feed.close()
             self.L.mp3mi_l12_batch_destroy(self.h)
             self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FeedL12:
+    """The feeder of a BatchL12 (include/mp3mi_l12.h, mp3mi_l12_feed_*): a device FIFO per lane, so that every stream may bring any
+    number of samples per call; a slot is lent to a lane for the ticks in which it encodes.  Made by BatchL12.feeder()."""
+
+    def __init__(self, batch, tick_frames, max_push, lanes=None, max_rows=None, ring_samples=0):
+        self.batch, self.L = batch, batch.L
+        self.tick_frames, self.max_push = tick_frames, max_push
+        self.h = ctypes.c_void_p()
+        lanes = batch.n_streams if lanes is None else lanes
+        rc = self.L.mp3mi_l12_feed_create(ctypes.byref(self.h), batch.h, lanes, lanes if max_rows is None else max_rows, tick_frames,
+                                          max_push, ring_samples)
+        if rc != 0:
+            raise Mp3miError("mp3mi_l12_feed_create failed with %d" % rc)
+        batch._feed = self
+
+    @property
+    def n_lanes(self):
+        return self.L.mp3mi_l12_feed_n_lanes(self.h)
+
+    @property
+    def capacity(self):
+        """pending samples per channel a lane's FIFO holds (the 1792 samples of history in the ring come on top)"""
+        return self.L.mp3mi_l12_feed_capacity(self.h)
+
+    def tick(self, pcm, out, out_len, rows, start=None, end=None, n_push=None, kbps=None):
+        """One tick (mp3mi_l12_feed_tick).  rows: the lanes that push, strictly increasing; pcm: int16 cuda tensor [len(rows), pitch * C]
+        or [len(rows), pitch, C], pitch >= max_push (None without rows); start, end, n_push, kbps: per ROW -- start[r]: a new stream
+        begins in the lane with the row's samples, at kbps[r] (0 / None: the create-time bitrate of the slot it first encodes in);
+        end[r]: they are the stream's last.  out uint8 cuda [S, stride >= batch.out_stride(tick_frames)] and out_len int32 cuda [S] are
+        by SLOT.  Returns the int32 array [S] of the lane that encodes in each slot in this tick, -1 where none does (host
+        bookkeeping).  Nothing is waited for."""
+        import numpy as np
+        S, C = self.batch.n_streams, self.batch.channels
+        rl = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        R = len(rl)
+        assert out.is_cuda and out_len.is_cuda and out.is_contiguous() and out.shape[0] == S
+        ctl = np.zeros(R, np.uint8)
+        if start is not None:
+            ctl |= np.asarray(start, dtype=bool).reshape(R).astype(np.uint8) * 1  # MP3MI_SLOT_START
+        if end is not None:
+            ctl |= np.asarray(end, dtype=bool).reshape(R).astype(np.uint8) * 2  # MP3MI_SLOT_END
+        ns = np.zeros(R, np.int32) if n_push is None else np.ascontiguousarray(n_push, dtype=np.int32).reshape(R)
+        kb = np.zeros(R, np.int32) if kbps is None else np.ascontiguousarray(kbps, dtype=np.int32).reshape(R)
+        pitch = 0
+        if R:
+            assert pcm.is_cuda and pcm.is_contiguous() and pcm.shape[0] == R
+            pitch = pcm.numel() // (R * C)
+        slot_lane = np.full(S, -1, np.int32)
+        rc = self.L.mp3mi_l12_feed_tick(self.h, R, rl.ctypes.data if R else None, pcm.data_ptr() if R else None, pitch,
+                                        ctl.ctypes.data if R else None, ns.ctypes.data if R else None, kb.ctypes.data if R else None,
+                                        out.data_ptr(), out.shape[1], out_len.data_ptr(), slot_lane.ctypes.data)
+        if rc != 0:
+            raise Mp3miError("mp3mi_l12_feed_tick failed with %d" % rc)
+        return slot_lane
+
+    def lanes(self):
+        """(pending int32 [n_lanes], frames int64 [n_lanes] (-1: closed), flags uint8 [n_lanes]: 1 parked, 2 draining, 4 started but not
+        yet in the batch, 8 ready and waiting for a slot; lanes that are not closed) -- host bookkeeping, no device wait"""
+        import numpy as np
+        n = self.n_lanes
+        p, f, g = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.uint8)
+        rc = self.L.mp3mi_l12_feed_lanes(self.h, p.ctypes.data, f.ctypes.data, g.ctypes.data)
+        if rc < 0:
+            raise Mp3miError("mp3mi_l12_feed_lanes failed with %d" % rc)
+        return p, f, g, rc
+
+    def close(self):
+        """resets the batch and detaches (mp3mi_l12_feed_destroy)"""
+        if self.h:
+            self.L.mp3mi_l12_feed_destroy(self.h)
+            self.h = ctypes.c_void_p()
+            self.batch._feed = None
 
     def __del__(self):
         try:

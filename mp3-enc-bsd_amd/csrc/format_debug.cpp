@@ -12,7 +12,9 @@
 #include <utility>
 #include <vector>
 #include "host_util.h"
+#include "l12_dev.h"
 #include "mp3mi.h"
+#include "mp3mi_l12.h"
 
 static const int FD_SLEN1[16] = {0, 0, 0, 0, 3, 1, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4};                      // src/l3bitstream.c:171-172
 static const int FD_SLEN2[16] = {0, 1, 2, 3, 0, 1, 2, 3, 1, 2, 3, 1, 2, 3, 2, 3};
@@ -296,5 +298,58 @@ extern "C" int mp3mi_debug_feed_packed(int channels, int n_active, int n_lanes, 
     D.fetch(ring, dring, n_ring);
     D.fetch(packed, dpush, n_pushed);
     D.fetch(rows, drows, n_rows);
+    return D.rc();
+}
+
+// The self-test hook mp3mi_debug_l12_feed (include/mp3mi_l12.h): k12_feed alone, through the launcher mp3mi_l12_feed_tick uses, on
+// given rings (one per lane), push rows, dense rows and the two history rows per slot ([n_slots][1792][C] and [n_slots][1056][C],
+// dense), whole up and whole back like the hooks above.  The rules the feeder's tick keeps are checked here: a descriptor set that
+// breaks one launches nothing.
+extern "C" int mp3mi_debug_l12_feed(int channels, int n_active, int n_lanes, int n_push_rows, int n_slots, int cap, int row_samples,
+                                    const uint32_t *desc, int16_t *ring, size_t ring_pitch, int16_t *push, size_t push_pitch, int16_t *rows,
+                                    size_t row_pitch, int16_t *hist, int16_t *fb_hist)
+{
+    if (!have_device()) return MP3MI_ERR_NO_DEVICE;
+    if ((channels != 1 && channels != 2) || n_active <= 0 || n_lanes <= 0 || n_push_rows <= 0 || n_slots <= 0 || n_active > n_lanes || cap <= 0 ||
+        row_samples <= 0 || !desc || !ring || !push || !rows || !hist || !fb_hist)
+        return MP3MI_ERR_ARG;
+    const size_t C = (size_t) channels, esz = 2 * C, A = (size_t) n_active;
+    const uint64_t keep = L12_PCM_HIST;
+    if (ring_pitch < (size_t) cap || row_pitch < (size_t) row_samples || push_pitch == 0 || ring_pitch * esz % 16 != 0 || row_pitch * esz % 16 != 0)
+        return MP3MI_ERR_ARG;
+    std::vector<char> lane_seen((size_t) n_lanes, 0), row_seen((size_t) n_push_rows, 0), slot_seen((size_t) n_slots, 0);
+    size_t most = 0;
+    for (size_t i = 0; i < A; i++) {
+        const uint32_t *d = desc + 8 * i;
+        const uint64_t head = d[0], pending = d[1], n_push = d[2], take = d[3];
+        const bool resume = d[7] & MP3MI_L12_FEED_RESUME;
+        if (head >= (uint64_t) cap || keep + pending + n_push > (uint64_t) cap || take > pending + n_push || take > (uint64_t) row_samples ||
+            n_push > push_pitch)
+            return MP3MI_ERR_ARG;
+        if (d[4] >= (uint32_t) n_lanes || d[5] >= (uint32_t) n_push_rows || d[6] >= (uint32_t) n_slots) return MP3MI_ERR_ARG;
+        if (resume ? (d[7] & ~MP3MI_L12_FEED_RESUME) > keep : d[7] != 0) return MP3MI_ERR_ARG;
+        if (lane_seen[d[4]] || (n_push && row_seen[d[5]]) || ((take || resume) && slot_seen[d[6]])) return MP3MI_ERR_ARG;
+        lane_seen[d[4]] = 1;
+        if (n_push) row_seen[d[5]] = 1;
+        if (take || resume) slot_seen[d[6]] = 1;
+        size_t longest = (size_t) (take > n_push ? take : n_push);
+        if (resume && longest < (size_t) keep) longest = (size_t) keep;
+        most = longest * esz > most ? longest * esz : most;
+    }
+    const size_t n_ring = (size_t) n_lanes * ring_pitch * C, n_pushed = (size_t) n_push_rows * push_pitch * C, n_rows = (size_t) n_slots * row_pitch * C;
+    const size_t n_hist = (size_t) n_slots * L12_PCM_HIST * C, n_fb = (size_t) n_slots * MP3MI_PCM_HIST * C;
+    hook_bufs D;
+    const uint32_t *ddesc = D.copy_of(desc, 8 * A);
+    int16_t *dring = D.copy_of(ring, n_ring), *dpush = D.copy_of(push, n_pushed), *drows = D.copy_of(rows, n_rows);
+    int16_t *dhist = D.copy_of(hist, n_hist), *dfb = D.copy_of(fb_hist, n_fb);
+    if (!D.ok) return D.rc();
+    mp3mi_launch_l12_feed(ddesc, n_active, dring, ring_pitch * esz, cap, channels, dpush, push_pitch * esz, drows, row_pitch * esz, dhist, L12_PCM_HIST,
+                          dfb, MP3MI_PCM_HIST, most, 0);
+    D.sync();
+    D.fetch(ring, dring, n_ring);
+    D.fetch(push, dpush, n_pushed);
+    D.fetch(rows, drows, n_rows);
+    D.fetch(hist, dhist, n_hist);
+    D.fetch(fb_hist, dfb, n_fb);
     return D.rc();
 }

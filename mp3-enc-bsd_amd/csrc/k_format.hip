@@ -835,6 +835,83 @@ void mp3mi_launch_feed_packed(const void *desc, const void *work, int n_items, i
                        ring_pitch_bytes, (unsigned) cap, (unsigned) (2 * channels), (const uint8_t *) packed, (uint8_t *) rows, row_pitch_bytes);
 }
 
+// ---- the feeder of Layers I and II (mp3mi_l12_feed_tick, csrc/l12_feed.h) ----
+// k12_feed is k_feed_lanes with two differences.  The ring KEEPS HISTORY: a stream of these layers carries nothing from call to call
+// but the samples before the call's first, so the samples behind `head` stay where they are -- the host keeps keep + pending +
+// n_push <= cap for every descriptor, keep being the longer history row -- and ALL n_push samples are appended at (head + pending)
+// % cap, those the row takes straight from the push included: they are the history of a later tick.  The row's samples come from
+// ring[head ..) and then from the push, as in feed_move; the host's new head is (head + take) % cap.  And RESUME is part of the
+// cut: word 7 of a descriptor is 0, or bit 31 with n_hist below it, and then the slot's two live history rows are written too --
+// hist_a[slot] ([len_a][C]) the n_hist samples before head with zeros in front, hist_b[slot] ([len_b][C], len_b <= len_a) the last
+// len_b of the same samples -- what a state record of the parked stream would hold.  The spans that are read (history, pending:
+// behind head + pending) and the span that is written (the append: from there on, short of the history) never meet, the rows by
+// slot and the history rows by slot belong to one descriptor each: nothing a workgroup writes is read by another in the launch.
+// At most nine plain copies per lane and two runs of zeros; no LDS.
+MP3MI_DEVFN void feed_zero(uint8_t *dst, size_t n, size_t lane, size_t step) // n bytes of zeros, both ends aligned to 2; as feed_copy deals them
+{
+    if (n == 0) return;
+    const uintptr_t d0 = (uintptr_t) dst, dv0 = d0 & ~(uintptr_t) 15;
+    const size_t n_vec = (size_t) ((d0 + n + 15 - dv0) / 16);
+    const uint4 zero = {0u, 0u, 0u, 0u};
+    for (size_t v = lane; v < n_vec; v += step) {
+        const uintptr_t dv = dv0 + 16 * v;
+        if (dv >= d0 && dv + 16 <= d0 + n) *(uint4 *) dv = zero;
+        else {
+            const uintptr_t lo = dv > d0 ? dv : d0, hi = dv + 16 < d0 + n ? dv + 16 : d0 + n;
+            for (uintptr_t p = lo; p < hi; p += 2) *(uint16_t *) p = 0;
+        }
+    }
+}
+
+// One history row of len samples: the last min(n_hist, len) samples before head, zeros in front of them
+MP3MI_DEVFN void feed_hist(uint8_t *dst, size_t len, const uint8_t *rg, size_t head, size_t n_hist, size_t cap, size_t esz, size_t lane, size_t step)
+{
+    const size_t n = n_hist < len ? n_hist : len, z = len - n;
+    feed_zero(dst, z * esz, lane, step);
+    const size_t from = (head + cap - n) % cap; // (n <= len <= cap)
+    const size_t h1 = n < cap - from ? n : cap - from;
+    feed_copy(dst + z * esz, rg + from * esz, h1 * esz, lane, step);
+    feed_copy(dst + (z + h1) * esz, rg, (n - h1) * esz, lane, step);
+}
+
+// Workgroup (i, y): the i-th lane that moves in the tick -- descriptor {head, pending, n_push, take | lane, push_row, slot, resume},
+// one uniform 32-byte load -- and every gridDim.y-th vector of each of its copies
+__global__ void __launch_bounds__(256) k12_feed(const uint4 *__restrict__ desc, uint8_t *ring, size_t ring_pitch, unsigned cap, unsigned esz,
+                                                const uint8_t *__restrict__ push, size_t push_pitch, uint8_t *__restrict__ rows, size_t row_pitch,
+                                                uint8_t *__restrict__ hist_a, unsigned len_a, uint8_t *__restrict__ hist_b, unsigned len_b)
+{
+    const uint4 d = desc[2 * (size_t) blockIdx.x], w = desc[2 * (size_t) blockIdx.x + 1];
+    const size_t head = d.x, pending = d.y, n_push = d.z, take = d.w, e = esz, n_cap = cap;
+    const bool resume = w.w >> 31;
+    if (n_push == 0 && take == 0 && !resume) return;
+    const size_t lane = (size_t) blockIdx.y * 256 + threadIdx.x, step = (size_t) 256 * gridDim.y;
+    uint8_t *rg = ring + (size_t) w.x * ring_pitch, *row = rows + (size_t) w.z * row_pitch;
+    const uint8_t *ps = push + (size_t) w.y * push_pitch;
+    const size_t from_ring = take < pending ? take : pending, from_push = take - from_ring;
+    const size_t r1 = from_ring < n_cap - head ? from_ring : n_cap - head;
+    feed_copy(row, rg + head * e, r1 * e, lane, step);
+    feed_copy(row + r1 * e, rg, (from_ring - r1) * e, lane, step);
+    feed_copy(row + from_ring * e, ps, from_push * e, lane, step);
+    const size_t at = (head + pending) % n_cap, a1 = n_push < n_cap - at ? n_push : n_cap - at;
+    feed_copy(rg + at * e, ps, a1 * e, lane, step);
+    feed_copy(rg, ps + a1 * e, (n_push - a1) * e, lane, step);
+    if (resume) {
+        const size_t n_hist = w.w & 0x7FFFFFFFu, slot = w.z;
+        feed_hist(hist_a + slot * len_a * e, len_a, rg, head, n_hist, n_cap, e, lane, step);
+        feed_hist(hist_b + slot * len_b * e, len_b, rg, head, n_hist, n_cap, e, lane, step);
+    }
+}
+
+void mp3mi_launch_l12_feed(const void *desc, int n_active, int16_t *ring, size_t ring_pitch_bytes, int cap, int channels, const int16_t *push,
+                           size_t push_pitch_bytes, int16_t *rows, size_t row_pitch_bytes, int16_t *hist_a, int len_a, int16_t *hist_b, int len_b,
+                           size_t most_bytes, hipStream_t st)
+{
+    if (n_active <= 0) return;
+    hipLaunchKernelGGL(k12_feed, dim3((unsigned) n_active, (unsigned) feed_grid_y(most_bytes)), dim3(256), 0, st, (const uint4 *) desc, (uint8_t *) ring,
+                       ring_pitch_bytes, (unsigned) cap, (unsigned) (2 * channels), (const uint8_t *) push, push_pitch_bytes, (uint8_t *) rows,
+                       row_pitch_bytes, (uint8_t *) hist_a, (unsigned) len_a, (uint8_t *) hist_b, (unsigned) len_b);
+}
+
 // the last MP3MI_PCM_HIST samples of the call (a frame has 1152 > MP3MI_PCM_HIST) are the next call's history
 __global__ void __launch_bounds__(256) k_hist_save(mp3mi_geom geo, const int16_t *__restrict__ pcm, int16_t *__restrict__ hist)
 {

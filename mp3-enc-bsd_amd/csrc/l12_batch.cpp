@@ -15,6 +15,8 @@
 #include "l12_host.h"
 #include "mp3mi_l12.h"
 
+static void l12_feed_drop(mp3mi_l12_feed *f); // (l12_feed.h, at the end of this file)
+
 struct mp3mi_l12_batch {
     int device;
     int layer, n_streams, rate_idx, rate_hz, channels, max_frames, chunk_frames;
@@ -61,7 +63,14 @@ struct mp3mi_l12_batch {
     typedef upload_ring<uint8_t, 2> ctl_ring;
     ctl_ring ctl;
     size_t ctl_cap[2];
+    // the feeder attached to the batch (mp3mi_l12_feed_create; l12_feed.h), NULL: none.  While one is, the batch's streams are the
+    // feeder's: the calls that begin, move or end streams, or change what a frame's header says, are the feeder's alone (feed_call:
+    // the call comes from it)
+    mp3mi_l12_feed *feed;
+    bool feed_call;
 };
+// A call the caller may not make while a feeder is attached
+static inline bool l12_feeders_call(const mp3mi_l12_batch *b) { return b && b->feed && !b->feed_call; }
 
 // The control block of a per-slot call, one array per slot after the other: what the kernels read of it (l12_geom) and the list of
 // the slots the call STARTs (k12_slot_begin)
@@ -133,6 +142,7 @@ extern "C" int mp3mi_l12_batch_create(mp3mi_l12_batch **out, int layer, int n_st
     memset((void *) &b->ctl, 0, sizeof(b->ctl));
     b->ctl_cap[0] = b->ctl_cap[1] = 0;
     b->ceil_kbps = 0; b->rate_dirty = false;
+    b->feed = NULL; b->feed_call = false;
     if (hipGetDevice(&b->device) != hipSuccess) { delete b; return MP3MI_ERR_HIP; }
     b->cfg_h.resize((size_t) n_streams);
     b->max_frame_bytes = 0;
@@ -193,6 +203,7 @@ extern "C" void mp3mi_l12_batch_destroy(mp3mi_l12_batch *b)
     {
         device_scope sc(b->device);
         if (b->stream) (void) hipStreamSynchronize(b->stream);
+        if (b->feed) l12_feed_drop(b->feed); // (a batch that goes with its feeder attached)
         (void) hipFree(b->T3); (void) hipFree(b->T); (void) hipFree(b->cfg); (void) hipFree(b->erp);
         (void) hipFree(b->snr); (void) hipFree(b->sbs); (void) hipFree(b->dbg);
         for (int i = 0; i < 2; i++) { (void) hipFree(b->hist[i]); (void) hipFree(b->fb_hist[i]); }
@@ -211,20 +222,20 @@ extern "C" void mp3mi_l12_batch_destroy(mp3mi_l12_batch *b)
 
 extern "C" int mp3mi_l12_batch_set_mode(mp3mi_l12_batch *b, int mode)
 {
-    if (!b || mode < 0 || mode > 3) return MP3MI_ERR_ARG;
+    if (!b || mode < 0 || mode > 3 || l12_feeders_call(b)) return MP3MI_ERR_ARG;
     if ((b->channels == 1) != (mode == MP3MI_MODE_MONO)) return MP3MI_ERR_ARG;
     b->mode = mode;
     return MP3MI_OK;
 }
 extern "C" int mp3mi_l12_batch_set_error_protection(mp3mi_l12_batch *b, int on)
 {
-    if (!b) return MP3MI_ERR_ARG;
+    if (!b || l12_feeders_call(b)) return MP3MI_ERR_ARG;
     b->crc = on != 0;
     return MP3MI_OK;
 }
 extern "C" int mp3mi_l12_batch_set_header(mp3mi_l12_batch *b, int copyright, int original, int emphasis)
 {
-    if (!b || emphasis < 0 || emphasis > 3) return MP3MI_ERR_ARG;
+    if (!b || emphasis < 0 || emphasis > 3 || l12_feeders_call(b)) return MP3MI_ERR_ARG;
     b->hdr_flags = ((copyright != 0) << 3) | ((original != 0) << 2) | emphasis;
     return MP3MI_OK;
 }
@@ -341,7 +352,7 @@ static int l12_rates_restore(mp3mi_l12_batch *b)
 static int l12_encode_impl(mp3mi_l12_batch *b, const int16_t *pcm_dev, const int32_t *n_samples_dev, int n_frames,
                            uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev, bool whole_file, const l12_slot_call *sc = NULL)
 {
-    if (!b || !pcm_dev || !out_dev || !out_len_dev || n_frames < 1 || n_frames > b->max_frames) return MP3MI_ERR_ARG;
+    if (!b || !pcm_dev || !out_dev || !out_len_dev || n_frames < 1 || n_frames > b->max_frames || l12_feeders_call(b)) return MP3MI_ERR_ARG;
     if (out_stride < mp3mi_l12_batch_out_stride(b, n_frames)) return MP3MI_ERR_ARG;
     ON_DEVICE(b);
     { const int rc = l12_close_timing(b); if (rc != MP3MI_OK) return rc; }
@@ -443,7 +454,7 @@ static bool l12_kbps_ok(const mp3mi_l12_batch *b, int32_t kbps, l12_stream_cfg *
 static int l12_slots_impl(mp3mi_l12_batch *b, const int16_t *pcm_dev, int n_frames, const uint8_t *ctl_host, const int32_t *n_samples_host,
                           const int32_t *kbps_host, uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev)
 {
-    if (!b || !pcm_dev || !ctl_host || !out_dev || !out_len_dev || n_frames < 1 || n_frames > b->max_frames) return MP3MI_ERR_ARG;
+    if (!b || !pcm_dev || !ctl_host || !out_dev || !out_len_dev || n_frames < 1 || n_frames > b->max_frames || l12_feeders_call(b)) return MP3MI_ERR_ARG;
     if (out_stride < mp3mi_l12_batch_out_stride(b, n_frames)) return MP3MI_ERR_ARG;
     const int S = b->n_streams;
     std::vector<int64_t> f((size_t) S);
@@ -524,11 +535,28 @@ extern "C" size_t mp3mi_l12_batch_slot_state_bytes(const mp3mi_l12_batch *b)
     return b ? (size_t) b->channels * (L12_PCM_HIST + MP3MI_PCM_HIST) * sizeof(int16_t) : 0;
 }
 
+// The host halves of an export with close and of an import, for the public calls and for the feeder (l12_feed.h), which parks a
+// stream by the first alone and resumes it by the second and its own kernel.  f: the slots as slot_book::now gives them; the caller
+// settles the book.  Leave: the stream open in slot s is gone without a flush and takes its bitrate with it (cfg follows at the
+// slot's next START).  Enter: a stream at `frames` frames and kbps is open in closed slot s, and cfg[s] stands at kbps -- the
+// caller has sent a rate entry up where it lagged (l12_cfg_lags) and settles rate_dirty.
+static inline void l12_book_leave(mp3mi_l12_batch *b, int64_t *f, size_t s)
+{
+    f[s] = -1;
+    b->slot_kbps_h[s] = b->kbps_h[s];
+}
+static inline bool l12_cfg_lags(const mp3mi_l12_batch *b, size_t s, int32_t kbps) { return kbps != b->dev_kbps_h[s]; }
+static inline void l12_book_enter(mp3mi_l12_batch *b, int64_t *f, size_t s, int64_t frames, int32_t kbps)
+{
+    f[s] = frames;
+    b->slot_kbps_h[s] = b->dev_kbps_h[s] = kbps;
+}
+
 // What export and import ask of their arguments alike
 static bool l12_park_args_ok(const mp3mi_l12_batch *b, int n, const int32_t *slots_host, const void *state_dev, size_t state_stride,
                              const void *tickets)
 {
-    if (!b || !slots_host || !state_dev || !tickets || n < 1 || n > b->n_streams) return false;
+    if (!b || !slots_host || !state_dev || !tickets || n < 1 || n > b->n_streams || l12_feeders_call(b)) return false;
     if (state_stride < mp3mi_l12_batch_slot_state_bytes(b) || state_stride % 16 != 0 || (uintptr_t) state_dev % 16 != 0) return false;
     std::vector<char> seen((size_t) b->n_streams, 0);
     for (int i = 0; i < n; i++) {
@@ -589,10 +617,7 @@ extern "C" int mp3mi_l12_batch_slots_export(mp3mi_l12_batch *b, int n, const int
         t.error_protection = b->crc;
         t.kbps = b->slot_kbps_h[s];
         t.frames = f[s];
-        if (close) { // the stream takes its bitrate with it (cfg follows at the slot's next START)
-            f[s] = -1;
-            b->slot_kbps_h[s] = b->kbps_h[s];
-        }
+        if (close) l12_book_leave(b, f.data(), s);
     }
     // (the whole-batch counter cannot say "all but these": the per-slot bookkeeping takes over; slot_book::settle hands back as ever)
     b->book.settle(f.data());
@@ -619,20 +644,16 @@ extern "C" int mp3mi_l12_batch_slots_import(mp3mi_l12_batch *b, int n, const int
             t.hdr_flags != b->hdr_flags || t.error_protection != b->crc || t.reserved != 0)
             return MP3MI_ERR_ARG;
         if (!l12_kbps_ok(b, t.kbps, &val[(size_t) i]) || t.frames < 0) return MP3MI_ERR_ARG;
-        n_rate += t.kbps != b->dev_kbps_h[s];
+        n_rate += l12_cfg_lags(b, s, t.kbps);
     }
     ON_DEVICE(b);
     // cfg of a resumed stream is rebuilt here, from the ticket's checked bitrate: nothing of a device record is used as an index
     const int rc = l12_park_run(b, n, slots_host, const_cast<void *>(state_dev), state_stride, 0, n_rate, [&](l12_rate_entry *rt) {
         for (int i = 0; i < n; i++)
-            if (tickets_host[i].kbps != b->dev_kbps_h[(size_t) slots_host[i]]) l12_rate_set(rt++, slots_host[i], val[(size_t) i]);
+            if (l12_cfg_lags(b, (size_t) slots_host[i], tickets_host[i].kbps)) l12_rate_set(rt++, slots_host[i], val[(size_t) i]);
     });
     if (rc != MP3MI_OK) return rc;
-    for (int i = 0; i < n; i++) {
-        const size_t s = (size_t) slots_host[i];
-        f[s] = tickets_host[i].frames;
-        b->slot_kbps_h[s] = b->dev_kbps_h[s] = tickets_host[i].kbps;
-    }
+    for (int i = 0; i < n; i++) l12_book_enter(b, f.data(), (size_t) slots_host[i], tickets_host[i].frames, tickets_host[i].kbps);
     if (n_rate > 0) b->rate_dirty = b->dev_kbps_h != b->kbps_h;
     // the per-slot bookkeeping from here on, also on a batch nothing has run on yet (slot_book::settle hands back only with every
     // slot open at one frame count, and then the whole-batch path continues them from the same history)
@@ -650,6 +671,7 @@ extern "C" int mp3mi_l12_batch_slot_frames(const mp3mi_l12_batch *b, int64_t *fr
 extern "C" int mp3mi_l12_batch_encode_next(mp3mi_l12_batch *b, const int16_t *pcm_dev, int n_frames, uint8_t *out_dev, size_t out_stride,
                                            uint32_t *out_len_dev)
 {
+    if (l12_feeders_call(b)) return MP3MI_ERR_ARG;
     if (b && b->book.on) {
         // per-slot bookkeeping in force: with no stream open every slot starts (the whole-batch start); otherwise the open streams
         // go on and the other slots stay closed
@@ -666,7 +688,7 @@ extern "C" int mp3mi_l12_batch_encode_next(mp3mi_l12_batch *b, const int16_t *pc
 
 extern "C" int mp3mi_l12_batch_flush(mp3mi_l12_batch *b, uint8_t *out_dev, size_t out_stride, uint32_t *out_len_dev)
 {
-    if (!b || !out_dev || !out_len_dev || out_stride < 1) return MP3MI_ERR_ARG;
+    if (!b || !out_dev || !out_len_dev || out_stride < 1 || l12_feeders_call(b)) return MP3MI_ERR_ARG;
     ON_DEVICE(b);
     const uint8_t *slot_ctl = NULL;
     mp3mi_l12_batch::ctl_ring::entry *blk = NULL;
@@ -690,7 +712,7 @@ extern "C" int mp3mi_l12_batch_flush(mp3mi_l12_batch *b, uint8_t *out_dev, size_
 
 extern "C" int mp3mi_l12_batch_reset(mp3mi_l12_batch *b)
 {
-    if (!b) return MP3MI_ERR_ARG;
+    if (!b || l12_feeders_call(b)) return MP3MI_ERR_ARG;
     l12_streams_over(b);
     return MP3MI_OK;
 }
@@ -764,3 +786,5 @@ extern "C" int mp3mi_l12_encode_host(int layer, int n_streams, int rate_hz, int 
     mp3mi_l12_batch_destroy(b);
     return rc;
 }
+
+#include "l12_feed.h"

@@ -213,6 +213,16 @@ static inline size_t mp3mi_feed_work_list(const uint32_t *desc, size_t n_active,
 }
 void mp3mi_launch_feed_packed(const void *desc, const void *work, int n_items, int16_t *ring, size_t ring_pitch_bytes, int cap, int channels,
                               const int16_t *packed, int16_t *rows, size_t row_pitch_bytes, hipStream_t st);
+/* k12_feed (mp3mi_l12_feed_tick): k_feed_lanes for Layers I and II, whose rings keep history.  A descriptor's word 7 is 0, or
+   MP3MI_L12_FEED_RESUME | n_hist: then the kernel also writes rows `slot` of hist_a ([n_slots][len_a][channels]) and hist_b
+   ([n_slots][len_b][channels], len_b <= len_a) -- the n_hist <= len_a samples before head with zeros in front, and the last len_b
+   of the same.  All n_push samples are appended at (head + pending) % cap.  The rules of k_feed_lanes per descriptor and launch,
+   with len_a + pending + n_push <= cap in place of pending + n_push <= cap: checked on the host.  most_bytes counts a resuming
+   descriptor's len_a samples too */
+#define MP3MI_L12_FEED_RESUME 0x80000000u
+void mp3mi_launch_l12_feed(const void *desc, int n_active, int16_t *ring, size_t ring_pitch_bytes, int cap, int channels, const int16_t *push,
+                           size_t push_pitch_bytes, int16_t *rows, size_t row_pitch_bytes, int16_t *hist_a, int len_a, int16_t *hist_b, int len_b,
+                           size_t most_bytes, hipStream_t st);
 /* status[s] = the status word of stream s (a gather out of the strided state records) */
 void mp3mi_launch_status_gather(int n_streams, const int32_t *loop_state, int loop_state_words, int32_t *status, hipStream_t st);
 /* the reverse, for the streams a flush ended: their status words go back into the cleared state records, marked as reported */
